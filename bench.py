@@ -19,7 +19,13 @@ Usage: python bench.py --gpus N --steps K --warmup W
   --path single | mr   which Domain::sync runs: cstone_hip_domain_sync_scratch (one rank only) or the multi-rank
                        cstone_hip_domain_mr_sync (default for N > 1; with N = 1 an RCCL world of one rank)
   --dist uniform | plummer | clustered   the cloud (cstone_amd/clouds.py)
-Prints ONE JSON line on rank 0.
+  --full               everything beyond the headline figure as well: the stage table of further syncs, the extras (sort
+                       variants, other motions, findNeighbors, BASELINE configs[1] / [2], the N-GPU code path on one
+                       rank), the digit pass measured on its own and the invariants of the multi-rank run, the CPU baseline
+  --dump-outputs DIR   after the timed steps: what the last timed sync handed back to its caller (keys, x, y, z, h; a
+                       fixed, seeded sample of at most 2^20 particles) as DIR/<name>.npy in float64
+Prints ONE JSON line on rank 0.  Without --full a run sets up, warms up, times the --steps syncs, writes its outputs (if
+asked to) and prints the line: metric, value, unit, ms_per_step, ... and the roofline of the timed syncs themselves.
 """
 import argparse
 import json
@@ -63,7 +69,14 @@ def parse():
                    help="start the ranks, let each print its RANK / WORLD_SIZE / LOCAL_RANK and leave (no GPU work): the "
                         "check that --gpus N really starts N ranks")
     p.add_argument("--master-port", type=int, default=0, help="rendezvous port of the ranks this process starts (0: a free one)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: stage table, extras, CPU baseline, invariants")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the arrays the last timed sync returned (a fixed, seeded sample) as DIR/<name>.npy")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_ranks(args):
@@ -429,6 +442,34 @@ def cpu_baseline(n_sample, key_bits, real_bits, curve, bucket_focus, min_seconds
                       f"halo discovery, gathers), bucket {bucket_focus}"}
 
 
+DUMP_SAMPLE = 1 << 20  # particles per --dump-outputs: seven float64 arrays of them stay below 64 MB
+
+
+def dump_outputs(out_dir, arrays, key_bits, prefix="", sample=DUMP_SAMPLE, extra=None):
+    """--dump-outputs: the arrays a caller of the timed path received from its last sync as float64 .npy files -- all of
+    each when it is short, else the same fixed, seeded sample of indices (np.random.default_rng(0), written as index.npy)
+    of each.  64-bit keys are split into their two 32-bit halves (keys_hi, keys_lo), which float64 holds exactly."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = arrays["keys"].numel()
+    idx = np.unique(np.random.default_rng(0).integers(0, n, sample)) if n > sample else np.arange(n)
+    sel = torch.from_numpy(idx).to(arrays["keys"].device)
+    out = {"index": idx.astype(np.float64)}
+    keys = arrays["keys"][sel].cpu().numpy().view(np.uint64 if key_bits == 64 else np.uint32)
+    if key_bits == 64:
+        out["keys_hi"] = (keys >> np.uint64(32)).astype(np.float64)
+        out["keys_lo"] = (keys & np.uint64(0xFFFFFFFF)).astype(np.float64)
+    else:
+        out["keys"] = keys.astype(np.float64)
+    for name in ("x", "y", "z", "h"):
+        out[name] = arrays[name][sel].cpu().numpy().astype(np.float64)
+    out.update(extra or {})
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def main():
     args = parse()
     launched = os.environ.get("WORLD_SIZE") is not None  # under torch.distributed.run (the driver's, or our own child)
@@ -549,12 +590,24 @@ def main():
         after = pipe.dom.stats()
         timed_stats = {k: after[k] - stats_before[k] for k in ("resorts", "resort_fallbacks", "box_redos",
                                                                 "full_sort_fallbacks")} | {"last_movers": after["last_movers"]}
-    # every stage of a sync, on args.steps further syncs of the same kind (not part of `value`)
-    ctx.profile_enable(0 if args.no_stage_timers else 1)
-    ctx.profile_reset()
-    run_syncs(args.steps, move)
-    stage_ms = {s: ctx.profile_get(s)[0] / args.steps for s in cstone_amd.STAGES}
+    if args.dump_outputs:
+        # what the last timed sync handed back to its caller (the multi-rank sync: assigned particles and halos)
+        if distributed:
+            r = pipe.last
+            dump_outputs(args.dump_outputs, r, args.key_bits, prefix=f"rank{rank}_" if world > 1 else "",
+                         sample=DUMP_SAMPLE // world, extra={"range": [r["start"], r["end"]]})
+        else:
+            assert pipe._keys_ptr.value == pipe.keys.data_ptr()  # the keys are sorted in the caller's buffer
+            dump_outputs(args.dump_outputs, dict(keys=pipe.keys, x=pipe.x, y=pipe.y, z=pipe.z, h=pipe.h), args.key_bits)
+    stage_ms = None
+    if args.full:
+        # every stage of a sync, on args.steps further syncs of the same kind (not part of `value`)
+        ctx.profile_enable(0 if args.no_stage_timers else 1)
+        ctx.profile_reset()
+        run_syncs(args.steps, move)
+        stage_ms = {s: ctx.profile_get(s)[0] / args.steps for s in cstone_amd.STAGES}
     radix_stats = None
+    invariants_ok = None
     resorted = timed_stages["resort_leaves"][1] > 0
     if resorted:
         # what is left of the radix pass inside such syncs are the small sorts of the octree build: not the kernel's case
@@ -563,7 +616,7 @@ def main():
         radix_stats = (timed_stages["sort_pass"][0], timed_stages["sort_pass"][1], timed_spreads["sort_pass"],
                        timed_stages["sort_pass_iota"][0], timed_stages["sort_pass_iota"][1],
                        timed_spreads["sort_pass_iota"], "the digit passes of the timed syncs")
-    if distributed:
+    if distributed and args.full:
         # On several ranks a sync also launches the pass kernel on small inputs (the newcomers, the tree's node keys), so
         # the average over ALL launches says nothing about the dominant kernel: it is measured on its own, on as many
         # random pairs as this rank holds, right after the timed region.
@@ -585,6 +638,8 @@ def main():
         timed_stages["sort_pass"] = timed_stages["sort_pass_iota"] = (0.0, 0)
         del rk, rv, work
         invariants_ok = pipe.invariants(n_local * world)
+    elif distributed:
+        radix_stats = None  # the timed syncs' pass launches include the small sorts (see above): no digit-pass figure
     # what the output says about the headline pipeline (later sections replace `pipe`)
     head = {"f_leaves": pipe.f_leaves, "g_leaves": pipe.g_leaves,
             "n_scratch": len(pipe.scratch) if hasattr(pipe, "scratch") else 1}
@@ -592,7 +647,7 @@ def main():
         head.update(assigned=pipe.assigned, halos=pipe.halos, stats=dict(pipe.stats), transport=pipe.transport,
                     rccl_ranks=pipe.rccl_ranks, resorts=int(pipe.dom.view().resorts))
     extras = {}
-    if not distributed and not args.no_variants:
+    if args.full and not distributed and not args.no_variants:
         # the same syncs with the radix sort forced over ALL key digits (what the reference's GPU path does every time;
         # by default Domain::sync sorts the digits above the previous tree's leaf level and finishes the rest in runs)
         def timed_variant(before_step=None):
@@ -651,10 +706,10 @@ def main():
             "every particle displaced by <= 0.1 h and NOT kept inside [0, 1]: the box changes with every sync (syncs.box_redos "
             "= speculative encodes thrown away; after one of them the extents are measured first), all keys change, the "
             "radix path sorts")
-    if not distributed and args.neighbor_targets > 0:
+    if args.full and not distributed and args.neighbor_targets > 0:
         extras["find_neighbors"] = [pipe.find_neighbors(args.neighbor_targets, 0),
                                     pipe.find_neighbors(args.neighbor_targets, 128)]
-    if not distributed and not args.no_plummer:
+    if args.full and not distributed and not args.no_plummer:
         # BASELINE configs[1]: 10^7 uniform particles, encode + radix sort (all digits) + cornerstone tree from the root +
         # linked octree, no halos, every stage through its own C-ABI entry (the kernel-level seam of the reference)
         n1 = min(10_000_000, n_local)
@@ -732,7 +787,7 @@ def main():
                                              "note": "the same cloud with nothing moving between the syncs (round 3's number)"},
                              "find_neighbors": pl.find_neighbors(args.neighbor_targets, 0)
                              if args.neighbor_targets > 0 else None}
-    if not distributed and world == 1 and not args.no_mr_extra:
+    if args.full and not distributed and world == 1 and not args.no_mr_extra:
         # the curve's first point must be comparable with the others: the same cloud through the code path the N-GPU runs
         # take (cstone_hip_domain_mr_sync, collectives served by RCCL with a communicator of ONE rank)
         keep = pipe
@@ -775,7 +830,8 @@ def main():
         # section 3) over its launch time measured live with HIP events on the context's stream (stage timers).  The
         # top-level fields are those of the kernel with the largest total time inside the timed syncs.
         models = [  # (kernel, stage, bytes per particle and launch, what the bytes are)
-            ("encodeResortKernel" if stage_ms.get("resort_leaves", 0) > 0 else "encodeHistogramKernel", "encode",
+            ("encodeResortKernel" if (stage_ms.get("resort_leaves", 0) > 0 if stage_ms else resorted)
+             else "encodeHistogramKernel", "encode",
              3 * rbytes + 2 * kbytes, "x, y, z and the old key read, the new key written"),
             (("leafSortWaveKernel<LeafFields> (keys + x, y, z, h in one pass)", "resort_leaves", 2 * kbytes + 4 + 8 * rbytes,
               "key, x, y, z, h read; key, old index, x, y, z, h written at the leaf's new place (four scratch arrays: the "
@@ -918,26 +974,29 @@ def main():
                                    f"displaced by <= 0.1 h per coordinate (outside the timed intervals, each sync is "
                                    f"bracketed on its own); the arrays a sync returns go into the next one; particles "
                                    f"still inside their leaf are ordered leaf by leaf, the others are binned "
-                                   f"(csrc/resort.hpp) -- the same order as sorting all keys; extras: the radix sort "
-                                   f"instead (sorted_from_scratch / all_digits_sorted), other motions (moving_particles, "
-                                   f"zero_motion)"
+                                   f"(csrc/resort.hpp) -- the same order as sorting all keys"
+                                   + ("" if not args.full else
+                                      "; extras: the radix sort instead (sorted_from_scratch / all_digits_sorted), other "
+                                      "motions (moving_particles, zero_motion)")
                                    + ("" if not distributed else
                                       f"; {world} rank(s): SFC domain decomposition, particle exchange, locally essential "
                                       f"tree and halo exchange with all_to_all over RCCL"),
                        "particles_per_gpu": n_local, "focus_leaves": head["f_leaves"], "global_leaves": head["g_leaves"],
                        "path": path, "dist": args.dist, "self_launched": os.environ.get("CSTONE_BENCH_SELF_LAUNCHED") == "1",
                        **({"syncs_timed": timed_stats} if timed_stats else {}),
-                       **({"invariants_ok": invariants_ok, "rank0_assigned": head["assigned"], "rank0_halos": head["halos"],
+                       **({"invariants_ok": invariants_ok} if invariants_ok is not None else {}),
+                       **({"rank0_assigned": head["assigned"], "rank0_halos": head["halos"],
                            "rank0_exchange": head["stats"], "rccl_ranks": head["rccl_ranks"],
                            "rank0_syncs_resorted_total": head["resorts"],
                            "orchestration": "libcstone_hip (cstone_hip_domain_mr_sync)",
                            "transport": head["transport"]} if distributed else {})},
             "roofline": roofline,
-            "stage_ms_per_step": stage_ms,
             "first_sync_ms": first_sync_ms,
-            "extras": extras,
         }
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
+        if args.full:
+            out["stage_ms_per_step"] = stage_ms
+            out["extras"] = extras
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(int(args.cpu_sample), args.key_bits, args.real_bits, args.curve,
                                                args.bucket_focus)
         sys.stdout.flush()

@@ -47,10 +47,61 @@ def test_bench_failed_rank_fails_the_launcher():
     assert r.returncode != 0
 
 
+def test_bench_refuses_zero_steps():
+    """--steps sets the number of timed syncs: none at all is refused before anything touches the GPU"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=120, cwd=ROOT)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+DUMPED = ["index.npy", "keys_hi.npy", "keys_lo.npy", "x.npy", "y.npy", "z.npy", "h.npy"]
+
+
+def _dumped(d):
+    import numpy as np
+
+    assert sorted(os.listdir(d)) == sorted(DUMPED)
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in DUMPED) <= 64 << 20
+    a = {f[:-4]: np.load(os.path.join(d, f)) for f in DUMPED}
+    assert all(v.dtype == np.float64 and v.shape == a["index"].shape for v in a.values())
+    return a
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """without --full only the headline figure is measured (no stage table of further syncs, no extras, no CPU baseline);
+    --dump-outputs writes a seeded sample of what the last timed sync returned (keys in SFC order), and a second run with
+    the same arguments writes the same arrays"""
+    import numpy as np
+
+    runs = []
+    for rep in range(2):
+        d = str(tmp_path / f"run{rep}")
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--particles", "2e6", "--steps", "3", "--warmup", "1",
+               "--dump-outputs", d]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        j = _json_line(r.stdout)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+            assert k in j, k
+        assert "extras" not in j and "stage_ms_per_step" not in j and "cpu_baseline" not in j
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["dtype"] == "u64/f64" and j["higher_is_better"] is True
+        assert j["value"] > 0 and abs(j["value"] - 2e6 / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+        a = _dumped(d)
+        idx = a["index"]
+        assert idx.size > 1e5 and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 2e6
+        keys = (a["keys_hi"].astype(np.uint64) << np.uint64(32)) | a["keys_lo"].astype(np.uint64)
+        assert np.all(keys[1:] >= keys[:-1])
+        assert all(((a[c] >= 0) & (a[c] <= 1)).all() for c in "xyz") and (a["h"] > 0).all()
+        runs.append(a)
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k]), k
+
+
 @pytest.mark.gpu
 def test_bench_single_rank_contract():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--particles", "2e6", "--steps", "2", "--warmup", "1",
-           "--cpu-sample", "2e5", "--neighbor-targets", "1e5"]
+           "--cpu-sample", "2e5", "--neighbor-targets", "1e5", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _json_line(r.stdout)
@@ -79,7 +130,7 @@ def test_bench_two_ranks_rehearsal():
     env = dict(os.environ, CSTONE_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29790", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--particles", "2e6",
-           "--steps", "2", "--warmup", "1"]
+           "--steps", "2", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _json_line(r.stdout)
@@ -102,7 +153,7 @@ def test_bench_gpus_2_without_a_launcher():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--particles", "2e6", "--steps", "2",
-           "--warmup", "1", "--dist", "clustered"]
+           "--warmup", "1", "--dist", "clustered", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _json_line(r.stdout)
@@ -128,7 +179,7 @@ def test_bench_two_ranks_rccl():
     env.pop("CSTONE_BENCH_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29791", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--particles", "4e6",
-           "--steps", "3", "--warmup", "1"]
+           "--steps", "3", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _json_line(r.stdout)
@@ -137,14 +188,17 @@ def test_bench_two_ranks_rccl():
 
 
 @pytest.mark.gpu
-def test_bench_native_rccl_world_of_one():
+def test_bench_native_rccl_world_of_one(tmp_path):
     """the multi-rank domain over RCCL served from C++ inside the library (csrc/comm_rccl.hip), rehearsed with a world of
     ONE rank on the one-GPU box: the same entry points, callbacks and stream ordering as the N-GPU run (all-reduce,
-    all-gather and the grouped send/recv with no peer)"""
+    all-gather and the grouped send/recv with no peer); --dump-outputs writes what its last timed sync returned"""
+    import numpy as np
+
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("CSTONE_BENCH_BACKEND", None)
+    d = str(tmp_path / "out")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--particles", "2e6", "--steps", "2", "--warmup", "1",
-           "--path", "mr", "--dist", "plummer"]
+           "--path", "mr", "--dist", "plummer", "--full", "--dump-outputs", d]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _json_line(r.stdout)
@@ -152,3 +206,7 @@ def test_bench_native_rccl_world_of_one():
     assert j["config"]["invariants_ok"] is True and j["config"]["rank0_assigned"] == 2000000
     assert j["config"]["orchestration"].startswith("libcstone_hip")
     assert j["config"]["rccl_ranks"] == 1 and j["config"]["path"] == "mr" and j["config"]["dist"] == "plummer"
+    assert np.array_equal(np.load(os.path.join(d, "range.npy")), [0, 2000000])  # [start, end): one rank, no halos
+    a = {f[:-4]: np.load(os.path.join(d, f)) for f in DUMPED}
+    keys = (a["keys_hi"].astype(np.uint64) << np.uint64(32)) | a["keys_lo"].astype(np.uint64)
+    assert keys.size > 1e5 and np.all(keys[1:] >= keys[:-1]) and (a["h"] > 0).all()

@@ -26,12 +26,15 @@ def _need_exe():
             pytest.skip("oracle/_ref/ref_domain_gpu not built (no /root/reference here)")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference headers")
 def test_shim_defines_every_seam_symbol_the_reference_domain_needs():
     """CPU: the reference's Domain<GpuTag> translation unit + the shim link against libcstone_hip.so with no undefined
-    cstone:: symbol left (the link step of oracle/Makefile is the check; here: the binary exists and resolves)"""
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "refdomain"], check=True)
-    assert os.path.exists(EXE)
+    cstone:: symbol left (the link step of oracle/Makefile is the check; here: the binary exists and resolves).  Where the
+    reference headers are absent, the binary the build made where they were is checked"""
+    if os.path.isdir(REF):
+        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "refdomain"], check=True)
+        assert os.path.exists(EXE)
+    elif not os.path.exists(EXE):
+        pytest.skip("needs the reference headers or oracle/_ref/ref_domain_gpu built from them")
     r = subprocess.run(["ldd", "-r", EXE], capture_output=True, text=True)
     undefined = [l for l in (r.stdout + r.stderr).splitlines() if "undefined symbol" in l and "cstone" in l]
     assert not undefined, undefined[:5]

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of the switches of a steady-state sync on one box (gpurun): every line is one bench.py / mr_bench.py run
 cd "$(dirname "$0")/.."
-run() { echo "== $*"; env "$@" python bench.py --steps 10 --warmup 2 --no-plummer --no-cpu-baseline --no-mr-extra --no-variants --neighbor-targets 0 2>/dev/null | python -c "
+run() { echo "== $*"; env "$@" python bench.py --full --steps 10 --warmup 2 --no-plummer --no-cpu-baseline --no-mr-extra --no-variants --neighbor-targets 0 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][0])
 print(round(d['ms_per_step'],3), {k:round(v,3) for k,v in d['stage_ms_per_step'].items() if v>0.005})"; }

@@ -5,11 +5,11 @@ cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out/prof_r4
 rm -rf $O; mkdir -p $O
 # the bench's own command under the kernel trace (its JSON line belongs next to the kernel stats)
-timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $O/bench -o bench --output-format csv -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-plummer --no-mr-extra > $O/bench_stdout.log 2>&1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $O/bench -o bench --output-format csv -- python3 $R/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-plummer --no-mr-extra > $O/bench_stdout.log 2>&1
 echo "bench trace done" > $O/progress.log
 # HBM traffic of every kernel of the timed loop (bench.py, 3 timed syncs with drifting particles), one counter per run
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c -d $O/benchpmc_$c -o p --output-format csv -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-plummer --no-mr-extra --no-variants --neighbor-targets 0 > /dev/null 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c -d $O/benchpmc_$c -o p --output-format csv -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-plummer --no-mr-extra --no-variants --neighbor-targets 0 > /dev/null 2>&1
   echo "bench pmc $c done" >> $O/progress.log
 done
 # the multi-rank sync at the per-GPU size of the 8-GPU strong-scaling point, RCCL world of one rank
@@ -27,6 +27,6 @@ echo "mr api trace done" >> $O/progress.log
 timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $O/sort -o sort --output-format csv -- python3 $R/tools/sort_bench.py > $O/sort_stdout.log 2>&1
 echo "sort trace done" >> $O/progress.log
 # roctx ranges of the stages (cstone_hip_profile_markers): the stage table of a sync from the marker trace
-CSTONE_BENCH_MARKERS=1 timeout -k 10 300 rocprofv3 --marker-trace --kernel-trace -d $O/markers -o m --output-format csv -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-plummer --no-mr-extra --no-variants --neighbor-targets 0 > $O/markers_stdout.log 2>&1
+CSTONE_BENCH_MARKERS=1 timeout -k 10 300 rocprofv3 --marker-trace --kernel-trace -d $O/markers -o m --output-format csv -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-plummer --no-mr-extra --no-variants --neighbor-targets 0 > $O/markers_stdout.log 2>&1
 echo "marker trace done" >> $O/progress.log
 ls $O
