@@ -56,7 +56,7 @@ const char* stageName(int stage)
                                                    "cstone:link_octree", "cstone:halos",       "cstone:neighbors",
                                                    "cstone:minmax",      "cstone:sort_pass_iota", "cstone:resort_bins",
                                                    "cstone:resort_leaves", "cstone:gather_h",  "cstone:place",
-                                                   "cstone:stage15"};
+                                                   "cstone:multipoles", "cstone:gravity"};
     return stage >= 0 && stage < CSTONE_NUM_STAGES ? names[stage] : "cstone:?";
 }
 } // namespace

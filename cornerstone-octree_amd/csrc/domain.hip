@@ -130,6 +130,8 @@ struct DomainBase
     virtual void setSpeculativeBox(bool on)              = 0;
     virtual int reapplySync(const void* in, size_t n, int elemBytes, void* out) = 0;
     virtual int updateExpansionCenters(const void* x, const void* y, const void* z, const void* m, int massBits) = 0;
+    virtual int computeGravity(const void* x, const void* y, const void* z, const void* m, int massBits, int order,
+                               double G, double eps2, void* ax, void* ay, void* az, void* phi) = 0;
     virtual void stats(cstone_hip_domain_stats* out)     = 0;
 };
 
@@ -685,6 +687,45 @@ public:
         return cstone_hip_ctx_sync(ctx_);
     }
 
+    /*! Barnes-Hut gravity on the focus tree (csrc/gravity.hip): the multipoles about the current expansion centres, then
+     *  the group walk over the end_index particles.  The target groups follow from the sync's tree and are kept until
+     *  the next sync. */
+    int computeGravity(const void* x, const void* y, const void* z, const void* m, int massBits, int order, double G,
+                       double eps2, void* ax, void* ay, void* az, void* phi) override
+    {
+        if (!haveExpansion_)
+            return fail(ctx_, CSTONE_E_ARG,
+                        "domain_compute_gravity: no expansion centres (sync_grav or update_expansion_centers after the "
+                        "last sync)");
+        if (box_.bc[0] == 1 || box_.bc[1] == 1 || box_.bc[2] == 1)
+            return fail(ctx_, CSTONE_E_ARG, "domain_compute_gravity: periodic boundaries need Ewald summation, which is "
+                                            "not provided");
+        if ((massBits != 32 && massBits != 64) || !x || !y || !z || !m || !ax || !ay || !az)
+            return fail(ctx_, CSTONE_E_ARG, "domain_compute_gravity: bad argument");
+        const int kb = 8 * sizeof(K), rb = 8 * sizeof(T);
+        const NodeIdx L = fLeaves_, I = (L - 1) / 7, M = L + I;
+        if (groupsSync_ != syncs_)
+        {
+            CS_TRY(groups_.ensure(ctx_, size_t(endIndex_ + 1) * sizeof(uint32_t)));
+            uint32_t numGroups = 0;
+            CS_TRY(cstone_hip_compute_group_splits(ctx_, kb, rb, 0, endIndex_, x, y, z, fTree_.p, L,
+                                                   layout_.as<uint32_t>(), &box_, 64, CSTONE_GRAVITY_GROUP_TOL,
+                                                   groups_.as<uint32_t>(), size_t(endIndex_) + 1, &numGroups));
+            numGroups_  = numGroups;
+            groupsSync_ = syncs_;
+        }
+        CS_TRY(fMultipoles_.ensure(ctx_, size_t(M) * 8 * sizeof(T)));
+        int32_t levels[maxLevel<K>() + 2];
+        CS_TRY(copyToHost(ctx_, levels, fLevelRange_.p, sizeof levels));
+        CS_TRY(cstone_hip_upsweep_multipoles(ctx_, rb, massBits, x, y, z, m, fLti_.as<int32_t>() + I, L,
+                                             layout_.as<uint32_t>(), int(maxLevel<K>()), levels, fChild_.as<int32_t>(),
+                                             M, fExpansion_.p, fMultipoles_.p));
+        return cstone_hip_compute_gravity(ctx_, rb, massBits, x, y, z, m, 0, endIndex_, groups_.as<uint32_t>(),
+                                          numGroups_, &box_, fChild_.as<int32_t>(), fItl_.as<int32_t>(),
+                                          layout_.as<uint32_t>(), fExpansion_.p, fMultipoles_.p, order, G, eps2, ax,
+                                          ay, az, phi, nullptr, nullptr);
+    }
+
     /*! Domain::reapplySync (R/domain/domain.hpp:334-378) without an exchange: the kept particles in SFC order */
     int reapplySync(const void* in, size_t n, int elemBytes, void* out) override
     {
@@ -907,6 +948,9 @@ private:
     DevBuf fPrefixes_, fChild_, fParents_, fLevelRange_, fItl_, fLti_, fCenters_, fSizes_;
     DevBuf fExpansion_;          // T[M][4]: centre of mass + MAC radius^2 per node (updateExpansionCenters)
     bool haveExpansion_ = false; // ... of the tree of the last sync
+    DevBuf fMultipoles_;         // T[M][8]: multipoles about the expansion centres (computeGravity)
+    DevBuf groups_;              // u32[numGroups_ + 1]: target groups of computeGravity, from the sync number groupsSync_
+    uint32_t numGroups_ = 0, groupsSync_ = 0;
     DevBuf ops_, ops2_, leafOps_, layout_, radii_, flags_;
 };
 
@@ -1010,6 +1054,14 @@ int cstone_hip_domain_sync_grav(cstone_hip_domain* dom, void** keys, void** x, v
     *m = pp[num_props];
     if (rc != CSTONE_OK) return rc;
     return dom->impl->updateExpansionCenters(*x, *y, *z, *m, mass_bits);
+}
+
+int cstone_hip_domain_compute_gravity(cstone_hip_domain* dom, const void* x, const void* y, const void* z,
+                                      const void* m, int mass_bits, int order, double G, double eps2, void* ax, void* ay,
+                                      void* az, void* phi)
+{
+    if (!dom) return CSTONE_E_ARG;
+    return dom->impl->computeGravity(x, y, z, m, mass_bits, order, G, eps2, ax, ay, az, phi);
 }
 
 int cstone_hip_domain_view_get(cstone_hip_domain* dom, cstone_hip_domain_view* out)

@@ -1,0 +1,368 @@
+// Barnes-Hut gravity on a linked octree that carries expansion centres (cstone_hip_domain_sync_grav /
+// _update_expansion_centers, or any tree with centres and MAC radii in the same T[M][4] layout): the multipole upsweep
+// and the group walk behind cstone_hip_upsweep_multipoles / cstone_hip_compute_gravity.  The reference leaves this step
+// to its client (Ryoanji); the MAC is its evaluateMac (R/traversal/macs.hpp, the function above evaluateMacPbc).
+//
+// Multipoles: T[8] per node = (M, Qxx, Qxy, Qxz, Qyy, Qyz, Qzz, 0), traceless Cartesian quadrupole about the node's
+// expansion centre.  Leaves from their particles (one thread per leaf), internal nodes one level at a time from the
+// sum of their 8 children shifted to the parent's centre (parallel-axis term; the dipole about a centre of mass is 0).
+//
+// Walk: ONE wave per target group (up to 64 consecutive particles, one target per lane; longer groups are walked 64 at
+// a time).  The MAC is taken against the box of the wave's targets, so every decision is wave-uniform: the node
+// stack lives in LDS, node data (centre, MAC radius, multipole) comes through scalar loads, and a node is either
+// applied as a multipole to all 64 lanes (M2P) or, for an opened leaf, its particles are fetched with one coalesced
+// load per array and handed round with v_readlane (P2P), the inner loop touching no memory.
+// Compiled with -ffp-contract=off like the rest of the library: the MAC arithmetic is the one the tests restate.
+#include <algorithm>
+
+#include "ctx.hpp"
+#include "device_keys.hpp"
+
+namespace cship
+{
+
+namespace
+{
+
+constexpr int GW_BLOCK = 256;
+constexpr int GW_WAVES = GW_BLOCK / 64;
+constexpr int GW_STACK = 160; // >= 7 * 21 + 1: the deepest a depth-first walk of an octree of 21 levels gets
+
+__device__ __forceinline__ int32_t uniform(int32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+
+__device__ __forceinline__ float readLane(float v, int k)
+{
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k));
+}
+__device__ __forceinline__ double readLane(double v, int k)
+{
+    long long b = __double_as_longlong(v);
+    int lo      = __builtin_amdgcn_readlane(int(b), k);
+    int hi      = __builtin_amdgcn_readlane(int(b >> 32), k);
+    return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
+}
+
+template<class T>
+__device__ __forceinline__ T waveMin(T v)
+{
+    for (int o = 32; o > 0; o >>= 1)
+        v = min(v, __shfl_xor(v, o));
+    return v;
+}
+template<class T>
+__device__ __forceinline__ T waveMax(T v)
+{
+    for (int o = 32; o > 0; o >>= 1)
+        v = max(v, __shfl_xor(v, o));
+    return v;
+}
+
+//! multipole of every leaf from its particles layout[leaf] .. layout[leaf + 1], stored at its node index
+template<class T, class Tm>
+__global__ __launch_bounds__(256) void leafMultipolesKernel(const T* __restrict__ x, const T* __restrict__ y,
+                                                            const T* __restrict__ z, const Tm* __restrict__ m,
+                                                            const NodeIdx* __restrict__ leafToInternal, NodeIdx numLeaves,
+                                                            const uint32_t* __restrict__ layout,
+                                                            const T* __restrict__ centers, T* __restrict__ mp)
+{
+    const NodeIdx leaf = blockIdx.x * 256 + threadIdx.x;
+    if (leaf >= numLeaves) return;
+    const NodeIdx n = leafToInternal[leaf];
+    const T cx = centers[4 * size_t(n)], cy = centers[4 * size_t(n) + 1], cz = centers[4 * size_t(n) + 2];
+    T M = 0, qxx = 0, qxy = 0, qxz = 0, qyy = 0, qyz = 0, qzz = 0;
+    for (uint32_t i = layout[leaf]; i < layout[leaf + 1]; ++i)
+    {
+        const T w  = T(m[i]);
+        const T dx = x[i] - cx, dy = y[i] - cy, dz = z[i] - cz;
+        const T r2 = dx * dx + dy * dy + dz * dz;
+        M += w;
+        qxx += w * (T(3) * dx * dx - r2);
+        qxy += w * (T(3) * dx * dy);
+        qxz += w * (T(3) * dx * dz);
+        qyy += w * (T(3) * dy * dy - r2);
+        qyz += w * (T(3) * dy * dz);
+        qzz += w * (T(3) * dz * dz - r2);
+    }
+    T* out = mp + 8 * size_t(n);
+    out[0] = M, out[1] = qxx, out[2] = qxy, out[3] = qxz, out[4] = qyy, out[5] = qyz, out[6] = qzz, out[7] = T(0);
+}
+
+//! one level of the upsweep: internal nodes [firstCell, lastCell) from their 8 children, shifted to the node's centre
+template<class T>
+__global__ __launch_bounds__(256) void upsweepMultipolesKernel(NodeIdx firstCell, NodeIdx lastCell,
+                                                               const NodeIdx* __restrict__ childOffsets,
+                                                               const T* __restrict__ centers, T* __restrict__ mp)
+{
+    const NodeIdx cell = firstCell + blockIdx.x * 256 + threadIdx.x;
+    if (cell >= lastCell) return;
+    const NodeIdx child = childOffsets[cell];
+    if (!child) return;
+    const T cx = centers[4 * size_t(cell)], cy = centers[4 * size_t(cell) + 1], cz = centers[4 * size_t(cell) + 2];
+    T M = 0, qxx = 0, qxy = 0, qxz = 0, qyy = 0, qyz = 0, qzz = 0;
+    for (int k = 0; k < 8; ++k)
+    {
+        const size_t c = size_t(child + k);
+        const T* q     = mp + 8 * c;
+        const T mc     = q[0];
+        const T sx = centers[4 * c] - cx, sy = centers[4 * c + 1] - cy, sz = centers[4 * c + 2] - cz;
+        const T s2 = sx * sx + sy * sy + sz * sz;
+        M += mc;
+        qxx += q[1] + mc * (T(3) * sx * sx - s2);
+        qxy += q[2] + mc * (T(3) * sx * sy);
+        qxz += q[3] + mc * (T(3) * sx * sz);
+        qyy += q[4] + mc * (T(3) * sy * sy - s2);
+        qyz += q[5] + mc * (T(3) * sy * sz);
+        qzz += q[6] + mc * (T(3) * sz * sz - s2);
+    }
+    T* out = mp + 8 * size_t(cell);
+    out[0] = M, out[1] = qxx, out[2] = qxy, out[3] = qxz, out[4] = qyy, out[5] = qyz, out[6] = qzz, out[7] = T(0);
+}
+
+/*! The walk of one target group per wave (see the head of the file).  Outputs are indexed by i - first; lanes without a
+ *  target (the tail of a group) take the group's first particle as a stand-in and write nothing. */
+template<class T, class Tm, bool QUAD>
+__global__ __launch_bounds__(GW_BLOCK) void gravityWalkKernel(
+    const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ z, const Tm* __restrict__ m, uint32_t first,
+    uint32_t last, const uint32_t* __restrict__ groups, uint32_t numGroups, const NodeIdx* __restrict__ childOffsets,
+    const NodeIdx* __restrict__ internalToLeaf, const uint32_t* __restrict__ layout, const T* __restrict__ centers,
+    const T* __restrict__ mp, T G, T eps2, T* __restrict__ ax, T* __restrict__ ay, T* __restrict__ az,
+    T* __restrict__ phi, uint32_t* __restrict__ p2pCounts, uint32_t* __restrict__ m2pCounts, int* __restrict__ errors)
+{
+    __shared__ NodeIdx stacks[GW_WAVES][GW_STACK];
+    const int lane = int(threadIdx.x & 63u), wave = int(threadIdx.x >> 6);
+    NodeIdx* stack = stacks[wave];
+
+    const uint32_t g = blockIdx.x * GW_WAVES + wave;
+    if (g >= numGroups) return;
+    const uint32_t gs = max(first, uint32_t(uniform(int32_t(groups[g]))));
+    const uint32_t ge = min(last, uint32_t(uniform(int32_t(groups[g + 1]))));
+
+    for (uint32_t chunk = gs; chunk < ge; chunk += 64)
+    {
+        const uint32_t cend = min(ge, chunk + 64u);
+        const bool valid    = chunk + lane < cend;
+        const uint32_t i    = valid ? chunk + lane : chunk;
+        const T xi = x[i], yi = y[i], zi = z[i];
+
+        // the box of the targets: centre (lo + hi) / 2, half-size (hi - lo) / 2 (identical in every lane)
+        const T lox = waveMin(xi), loy = waveMin(yi), loz = waveMin(zi);
+        const T hix = waveMax(xi), hiy = waveMax(yi), hiz = waveMax(zi);
+        const T tcx = (lox + hix) * T(0.5), tcy = (loy + hiy) * T(0.5), tcz = (loz + hiz) * T(0.5);
+        const T tsx = (hix - lox) * T(0.5), tsy = (hiy - loy) * T(0.5), tsz = (hiz - loz) * T(0.5);
+
+        T axi = 0, ayi = 0, azi = 0, phii = 0;
+        uint32_t nP2P = 0, nM2P = 0;
+
+        if (lane == 0) stack[0] = 0;
+        int top = 1;
+        while (top > 0)
+        {
+            --top;
+            const NodeIdx node = uniform(stack[top]);
+            const T* c         = centers + 4 * size_t(node);
+            const T macSq      = c[3];
+            if (macSq == T(0)) continue; // massless, empty node (set_mac leaves 0 exactly for those)
+            const T cx = c[0], cy = c[1], cz = c[2];
+
+            // evaluateMac: minimum distance of the target box to the expansion centre against the MAC radius
+            T dX = fabs(tcx - cx) - tsx, dY = fabs(tcy - cy) - tsy, dZ = fabs(tcz - cz) - tsz;
+            dX += fabs(dX), dY += fabs(dY), dZ += fabs(dZ);
+            dX *= T(0.5), dY *= T(0.5), dZ *= T(0.5);
+            const T R2      = dX * dX + (dY * dY + dZ * dZ); // right fold, as traverseNeighbors
+            const bool open = uniform(int(R2 < fabs(macSq))) != 0;
+
+            if (!open)
+            {
+                // M2P, d = r_i - c_n
+                const T* q  = mp + 8 * size_t(node);
+                const T M   = q[0];
+                const T dx = xi - cx, dy = yi - cy, dz = zi - cz;
+                const T r2   = dx * dx + dy * dy + dz * dz + eps2;
+                const T rinv = T(1) / sqrt(r2);
+                const T rinv2 = rinv * rinv;
+                const T mr3   = M * rinv * rinv2;
+                if constexpr (QUAD)
+                {
+                    const T qx  = q[1] * dx + q[2] * dy + q[3] * dz;
+                    const T qy  = q[2] * dx + q[4] * dy + q[5] * dz;
+                    const T qz  = q[3] * dx + q[5] * dy + q[6] * dz;
+                    const T dqd = dx * qx + dy * qy + dz * qz;
+                    const T r5  = rinv2 * rinv2 * rinv;
+                    const T f   = mr3 + T(2.5) * dqd * r5 * rinv2;
+                    axi += r5 * qx - f * dx;
+                    ayi += r5 * qy - f * dy;
+                    azi += r5 * qz - f * dz;
+                    phii -= M * rinv + T(0.5) * dqd * r5;
+                }
+                else
+                {
+                    axi -= mr3 * dx;
+                    ayi -= mr3 * dy;
+                    azi -= mr3 * dz;
+                    phii -= M * rinv;
+                }
+                ++nM2P;
+                continue;
+            }
+
+            const NodeIdx child = uniform(childOffsets[node]);
+            if (child != 0)
+            {
+                if (top + 8 > GW_STACK)
+                {
+                    if (lane == 0) atomicOr(errors, 4); // traversal stack overflow: the call reports CSTONE_E_INTERNAL
+                    break;
+                }
+                if (lane < 8) stack[top + lane] = child + 7 - lane; // child 0 is popped first
+                top += 8;
+                continue;
+            }
+
+            // P2P with every particle of the opened leaf, d = r_j - r_i, the target itself skipped
+            const NodeIdx leaf = uniform(internalToLeaf[node]);
+            const uint32_t jb  = uint32_t(uniform(int32_t(layout[leaf])));
+            const uint32_t je  = uint32_t(uniform(int32_t(layout[leaf + 1])));
+            for (uint32_t base = jb; base < je; base += 64)
+            {
+                const int cnt = int(min(64u, je - base));
+                T xl = T(0), yl = T(0), zl = T(0), ml = T(0);
+                if (lane < cnt)
+                {
+                    xl = x[base + lane], yl = y[base + lane], zl = z[base + lane];
+                    ml = T(m[base + lane]);
+                }
+                for (int k = 0; k < cnt; ++k)
+                {
+                    const T dx = readLane(xl, k) - xi, dy = readLane(yl, k) - yi, dz = readLane(zl, k) - zi;
+                    const T mj = readLane(ml, k);
+                    const T r2 = dx * dx + dy * dy + dz * dz + eps2;
+                    T rinv     = T(1) / sqrt(r2);
+                    rinv       = (base + uint32_t(k) == i) ? T(0) : rinv;
+                    const T mr  = mj * rinv;
+                    const T mr3 = mr * rinv * rinv;
+                    axi += mr3 * dx;
+                    ayi += mr3 * dy;
+                    azi += mr3 * dz;
+                    phii -= mr;
+                }
+            }
+            nP2P += (je - jb) - ((i >= jb && i < je) ? 1u : 0u);
+        }
+
+        if (valid)
+        {
+            const uint32_t t = i - first;
+            ax[t] = G * axi, ay[t] = G * ayi, az[t] = G * azi;
+            if (phi) phi[t] = G * phii;
+            if (p2pCounts) p2pCounts[t] = nP2P;
+            if (m2pCounts) m2pCounts[t] = nM2P;
+        }
+    }
+}
+
+template<class T, class Tm>
+int upsweepMultipoles(cstone_hip_ctx* ctx, const void* x, const void* y, const void* z, const void* m,
+                      const int32_t* leafToInternal, int numLeaves, const uint32_t* layout, int numLevels,
+                      const int32_t* levelRangeHost, const int32_t* childOffsets, const void* centers, void* multipoles)
+{
+    hipLaunchKernelGGL((leafMultipolesKernel<T, Tm>), gridFor(size_t(numLeaves), 256), 256, 0, ctx->stream,
+                       (const T*)x, (const T*)y, (const T*)z, (const Tm*)m, leafToInternal, numLeaves, layout,
+                       (const T*)centers, (T*)multipoles);
+    for (int level = numLevels - 1; level >= 0; --level)
+    {
+        const int first = levelRangeHost[level], last = levelRangeHost[level + 1];
+        if (last <= first) continue;
+        hipLaunchKernelGGL(upsweepMultipolesKernel<T>, gridFor(size_t(last - first), 256), 256, 0, ctx->stream, first,
+                           last, childOffsets, (const T*)centers, (T*)multipoles);
+    }
+    CS_HIP(ctx, hipGetLastError());
+    return CSTONE_OK;
+}
+
+template<class T, class Tm>
+int launchGravity(cstone_hip_ctx* ctx, const void* x, const void* y, const void* z, const void* m, uint32_t first,
+                  uint32_t last, const uint32_t* groups, uint32_t numGroups, const int32_t* childOffsets,
+                  const int32_t* internalToLeaf, const uint32_t* layout, const void* centers, const void* multipoles,
+                  int order, double G, double eps2, void* ax, void* ay, void* az, void* phi, uint32_t* p2p,
+                  uint32_t* m2p)
+{
+    const unsigned grid = gridFor(numGroups, GW_WAVES);
+    int* errors         = ctx->devScalars + 63;
+    if (order == 2)
+        hipLaunchKernelGGL((gravityWalkKernel<T, Tm, true>), grid, GW_BLOCK, 0, ctx->stream, (const T*)x, (const T*)y,
+                           (const T*)z, (const Tm*)m, first, last, groups, numGroups, childOffsets, internalToLeaf,
+                           layout, (const T*)centers, (const T*)multipoles, T(G), T(eps2), (T*)ax, (T*)ay, (T*)az,
+                           (T*)phi, p2p, m2p, errors);
+    else
+        hipLaunchKernelGGL((gravityWalkKernel<T, Tm, false>), grid, GW_BLOCK, 0, ctx->stream, (const T*)x, (const T*)y,
+                           (const T*)z, (const Tm*)m, first, last, groups, numGroups, childOffsets, internalToLeaf,
+                           layout, (const T*)centers, (const T*)multipoles, T(G), T(eps2), (T*)ax, (T*)ay, (T*)az,
+                           (T*)phi, p2p, m2p, errors);
+    CS_HIP(ctx, hipGetLastError());
+    return CSTONE_OK;
+}
+
+bool badBits(int bits) { return bits != 32 && bits != 64; }
+
+} // namespace
+
+} // namespace cship
+
+using namespace cship;
+
+extern "C"
+{
+
+int cstone_hip_upsweep_multipoles(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
+                                  const void* z, const void* m, const int32_t* leaf_to_internal, int num_leaves,
+                                  const uint32_t* layout, int num_levels, const int32_t* level_range_host,
+                                  const int32_t* child_offsets, int num_nodes, const void* expansion_centers,
+                                  void* multipoles)
+{
+    if (!ctx || badBits(real_bits) || badBits(mass_bits) || num_leaves < 1 || num_nodes < num_leaves || num_levels < 0 ||
+        !x || !y || !z || !m || !leaf_to_internal || !layout || !level_range_host || !child_offsets ||
+        !expansion_centers || !multipoles)
+        return fail(ctx, CSTONE_E_ARG, "upsweep_multipoles: bad argument");
+    for (int level = 0; level < num_levels; ++level)
+        if (level_range_host[level] < 0 || level_range_host[level + 1] < level_range_host[level] ||
+            level_range_host[level + 1] > num_nodes)
+            return fail(ctx, CSTONE_E_ARG, "upsweep_multipoles: level_range_host is not a range of [0, num_nodes)");
+    StageTimer timer(ctx, CSTONE_STAGE_MULTIPOLES);
+#define CSTONE_UPSWEEP(T, Tm)                                                                                          \
+    upsweepMultipoles<T, Tm>(ctx, x, y, z, m, leaf_to_internal, num_leaves, layout, num_levels, level_range_host,      \
+                             child_offsets, expansion_centers, multipoles)
+    if (real_bits == 64) return mass_bits == 64 ? CSTONE_UPSWEEP(double, double) : CSTONE_UPSWEEP(double, float);
+    return mass_bits == 64 ? CSTONE_UPSWEEP(float, double) : CSTONE_UPSWEEP(float, float);
+#undef CSTONE_UPSWEEP
+}
+
+int cstone_hip_compute_gravity(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
+                               const void* z, const void* m, uint32_t first, uint32_t last, const uint32_t* groups,
+                               uint32_t num_groups, const cstone_box* box_host, const int32_t* child_offsets,
+                               const int32_t* internal_to_leaf, const uint32_t* layout, const void* expansion_centers,
+                               const void* multipoles, int order, double G, double eps2, void* ax, void* ay, void* az,
+                               void* phi, uint32_t* p2p_counts, uint32_t* m2p_counts)
+{
+    if (!ctx || badBits(real_bits) || badBits(mass_bits) || (order != 0 && order != 2) || !(eps2 >= 0.0) ||
+        last < first || !x || !y || !z || !m || (num_groups && !groups) || !box_host || !child_offsets ||
+        !internal_to_leaf || !layout || !expansion_centers || !multipoles || !ax || !ay || !az)
+        return fail(ctx, CSTONE_E_ARG, "compute_gravity: bad argument");
+    if (box_host->bc[0] == 1 || box_host->bc[1] == 1 || box_host->bc[2] == 1)
+        return fail(ctx, CSTONE_E_ARG, "compute_gravity: periodic boundaries need Ewald summation, which is not provided");
+    if (last == first || num_groups == 0) return CSTONE_OK;
+    {
+        StageTimer timer(ctx, CSTONE_STAGE_GRAVITY);
+#define CSTONE_GRAVITY(T, Tm)                                                                                          \
+    launchGravity<T, Tm>(ctx, x, y, z, m, first, last, groups, num_groups, child_offsets, internal_to_leaf, layout,     \
+                         expansion_centers, multipoles, order, G, eps2, ax, ay, az, phi, p2p_counts, m2p_counts)
+        int rc;
+        if (real_bits == 64) rc = mass_bits == 64 ? CSTONE_GRAVITY(double, double) : CSTONE_GRAVITY(double, float);
+        else rc = mass_bits == 64 ? CSTONE_GRAVITY(float, double) : CSTONE_GRAVITY(float, float);
+#undef CSTONE_GRAVITY
+        CS_TRY(rc);
+    }
+    // a stack overflow of the walk sets the sticky error word: report it here instead of returning a partial result
+    return cstone_hip_ctx_sync(ctx);
+}
+
+} // extern "C"

@@ -20,6 +20,7 @@ MORTON, HILBERT = 0, 1
 STAGES = {
     "encode": 0, "sort_hist": 1, "sort_pass": 2, "gather": 3, "node_counts": 4, "rebalance": 5, "link_octree": 6,
     "halos": 7, "neighbors": 8, "minmax": 9, "sort_pass_iota": 10, "resort_bins": 11, "resort_leaves": 12, "gather_h": 13, "place": 14,
+    "multipoles": 15, "gravity": 16,
 }
 
 EXPORTS = [
@@ -56,7 +57,11 @@ EXPORTS = [
     "cstone_hip_lower_bound_u32", "cstone_hip_sequence_u64", "cstone_hip_scan_u32_to_u64",
     "cstone_hip_domain_set_sort_mode", "cstone_hip_domain_set_speculative_box", "cstone_hip_test_hooks",
     "cstone_hip_domain_mr_set_sort_mode", "cstone_hip_find_neighbors_interleaved",
+    # Barnes-Hut gravity (csrc/gravity.hip)
+    "cstone_hip_upsweep_multipoles", "cstone_hip_compute_gravity", "cstone_hip_domain_compute_gravity",
 ]
+
+GRAVITY_GROUP_TOL = 2.0  # CSTONE_GRAVITY_GROUP_TOL: tol_factor of the target groups of cstone_hip_domain_compute_gravity
 
 
 class CBox(C.Structure):
@@ -541,6 +546,46 @@ class Context:
             _ptr(octree["child_offsets"]), _ptr(octree["internal_to_leaf"]), _ptr(layout), _ptr(centers), _ptr(sizes),
             C.c_float(ext), C.c_uint32(ngmax), _ptr(nidx), _ptr(nc)), "find_neighbors_groups")
         return nidx, nc
+
+    # ---- gravity
+    def upsweep_multipoles(self, x, y, z, m, leaf_to_internal, layout, level_range, child_offsets, expansion_centers,
+                           multipoles=None):
+        """multipoles (num_nodes, 8) = (M, Qxx, Qxy, Qxz, Qyy, Qyz, Qzz, 0) about the expansion centres (num_nodes, 4);
+        leaf_to_internal: the LEAF part of the map (num_leaves = layout.numel() - 1 entries), level_range: the level
+        ranges of the linked octree (host sequence or tensor, every level that exists)"""
+        torch = _torch()
+        nn = expansion_centers.numel() // 4
+        levels = np.ascontiguousarray(np.asarray(level_range.cpu() if hasattr(level_range, "cpu") else level_range,
+                                                 dtype=np.int32))
+        if multipoles is None:
+            multipoles = torch.zeros((nn, 8), dtype=x.dtype, device=x.device)
+        self._chk(self.lib.cstone_hip_upsweep_multipoles(
+            self.h, C.c_int(x.element_size() * 8), C.c_int(m.element_size() * 8), _ptr(x), _ptr(y), _ptr(z), _ptr(m),
+            _ptr(leaf_to_internal), C.c_int(layout.numel() - 1), _ptr(layout), C.c_int(levels.size - 1),
+            levels.ctypes.data_as(C.c_void_p), _ptr(child_offsets), C.c_int(nn), _ptr(expansion_centers),
+            _ptr(multipoles)), "upsweep_multipoles")
+        return multipoles
+
+    def compute_gravity(self, x, y, z, m, first, last, groups, box, child_offsets, internal_to_leaf, layout,
+                        expansion_centers, multipoles, order=2, G=1.0, eps2=0.0, potential=True, counts=False):
+        """(ax, ay, az, phi, p2p_counts, m2p_counts) of the targets [first, last) (phi None unless potential, the counts
+        None unless counts); groups: num_groups + 1 indices as compute_group_splits returns them"""
+        torch = _torch()
+        nt = last - first
+
+        def out(dt):
+            return torch.zeros(nt, dtype=dt, device=x.device)
+
+        ax, ay, az = out(x.dtype), out(x.dtype), out(x.dtype)
+        phi = out(x.dtype) if potential else None
+        p2p, m2p = (out(torch.int32), out(torch.int32)) if counts else (None, None)
+        self._chk(self.lib.cstone_hip_compute_gravity(
+            self.h, C.c_int(x.element_size() * 8), C.c_int(m.element_size() * 8), _ptr(x), _ptr(y), _ptr(z), _ptr(m),
+            C.c_uint32(first), C.c_uint32(last), _ptr(groups), C.c_uint32(groups.numel() - 1), C.byref(box),
+            _ptr(child_offsets), _ptr(internal_to_leaf), _ptr(layout), _ptr(expansion_centers), _ptr(multipoles),
+            C.c_int(order), C.c_double(G), C.c_double(eps2), _ptr(ax), _ptr(ay), _ptr(az), _ptr(phi), _ptr(p2p),
+            _ptr(m2p)), "compute_gravity")
+        return ax, ay, az, phi, p2p, m2p
 
 
 _DEFAULT = None

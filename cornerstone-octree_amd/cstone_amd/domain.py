@@ -131,6 +131,23 @@ class Domain:
                                                                      C.c_int(m.element_size() * 8))
         self.ctx._chk(rc, "domain_update_expansion_centers")
 
+    def gravity(self, x, y, z, m, G=1.0, eps=0.0, order=2, potential=True):
+        """Barnes-Hut gravity on the focus tree (cstone_hip_domain_compute_gravity) after sync_grav /
+        update_expansion_centers: (ax, ay, az, phi) of the end_index particles, phi None unless potential; x, y, z, m laid
+        out like the last sync's results"""
+        import torch
+
+        ne = self.view().end_index
+        ax, ay, az = [torch.zeros(ne, dtype=x.dtype, device=x.device) for _ in range(3)]
+        phi = torch.zeros(ne, dtype=x.dtype, device=x.device) if potential else None
+        rc = self.ctx.lib.cstone_hip_domain_compute_gravity(
+            self.h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(z.data_ptr()), C.c_void_p(m.data_ptr()),
+            C.c_int(m.element_size() * 8), C.c_int(order), C.c_double(G), C.c_double(float(eps) * float(eps)),
+            C.c_void_p(ax.data_ptr()), C.c_void_p(ay.data_ptr()), C.c_void_p(az.data_ptr()),
+            C.c_void_p(phi.data_ptr() if phi is not None else 0))
+        self.ctx._chk(rc, "domain_compute_gravity")
+        return ax, ay, az, phi
+
     def reapply_sync(self, field):
         """Domain::reapplySync: field (n rows of the last sync's input, 1..32 bytes each) in the order of the result"""
         import torch

@@ -1097,6 +1097,27 @@ public:
     {
         return mr_ ? mr_->expansionCenters() : static_cast<const T*>(view().expansion_centers);
     }
+    /*! Barnes-Hut gravity on the focus tree (cstone_hip_domain_compute_gravity): accelerations and, if phi is not null,
+     *  potentials of the endIndex() particles (the vectors are resized to that), from the expansion centres of
+     *  updateExpansionCenters after the last sync; x, y, z, m laid out like the result arrays of that sync.  eps: Plummer
+     *  softening length; order 0: monopoles, 2: monopoles + quadrupoles.  Open boundaries, one rank. */
+    template<class Tm>
+    void computeGravity(const DeviceVector<T>& x, const DeviceVector<T>& y, const DeviceVector<T>& z,
+                        const DeviceVector<Tm>& m, DeviceVector<T>& ax, DeviceVector<T>& ay, DeviceVector<T>& az,
+                        DeviceVector<T>* phi, T G, T eps, int order = 2)
+    {
+        static_assert(std::is_same_v<Tm, float> || std::is_same_v<Tm, double>);
+        if (mr_) throw std::runtime_error("computeGravity: one rank only");
+        const std::size_t ne = endIndex();
+        ax.resize(ne);
+        ay.resize(ne);
+        az.resize(ne);
+        if (phi) phi->resize(ne);
+        Context::check(cstone_hip_domain_compute_gravity(dom_, x.data(), y.data(), z.data(), m.data(), int(sizeof(Tm)) * 8,
+                                                         order, double(G), double(eps) * double(eps), ax.data(),
+                                                         ay.data(), az.data(), phi ? phi->data() : nullptr),
+                       "Domain::computeGravity");
+    }
     //! R/domain/domain.hpp:411: stores the flag like the reference does (its member convergeTrees, :661, has no reader
     //! there either: the trees converge on the first sync and take one update step per sync afterwards)
     void setTreeConv(bool flag) { convergeTrees_ = flag; }

@@ -94,7 +94,9 @@ extern "C"
 #define CSTONE_STAGE_GATHER_H 13      /* gather of h fused with the halo radii of Domain::sync: 4 + 2 T bytes per particle */
 #define CSTONE_STAGE_PLACE 14         /* multi-rank sync: keys, x, y, z, h of the kept particles to their final slots in one
                                         pass (placeColumnsKernel): 4 + 2 K + 8 T bytes per particle (+ 4 with a merge) */
-#define CSTONE_NUM_STAGES 16
+#define CSTONE_STAGE_MULTIPOLES 15    /* cstone_hip_upsweep_multipoles: leaf multipoles + one launch per tree level */
+#define CSTONE_STAGE_GRAVITY 16       /* cstone_hip_compute_gravity: the Barnes-Hut group walk */
+#define CSTONE_NUM_STAGES 17
     /* on: 0 off, 1 every stage, 2 only ENCODE, SORT_PASS(_IOTA), RESORT_LEAVES, GATHER(_H), HALOS, NEIGHBORS (the kernels that
      * move the particle arrays: eight brackets per sync instead of forty) */
     int cstone_hip_profile_enable(cstone_hip_ctx* ctx, int on);
@@ -847,6 +849,54 @@ extern "C"
                                           _update_expansion_centers (FocusedOctree::expansionCenters), else NULL */
     } cstone_hip_domain_mr_octree;
     int cstone_hip_domain_mr_octree_get(cstone_hip_domain_mr* dom, cstone_hip_domain_mr_octree* out);
+
+    /* ---------------------------------------------------------------------------------------------
+     * Barnes-Hut gravity on a linked octree with expansion centres (the step the reference leaves to its client, Ryoanji):
+     * single rank, open boundaries, monopole + traceless Cartesian quadrupole, Plummer softening.  Coordinates, centres,
+     * multipoles and results are real_bits (float | double), masses mass_bits (float | double); sums run in real_bits.
+     * upsweep_multipoles : multipoles[n][8] = (M, Qxx, Qxy, Qxz, Qyy, Qyz, Qzz, 0) of every node n about its expansion
+     *                 centre c_n = expansion_centers[n].xyz: M = sum m_j, Q_ab = sum m_j (3 d_a d_b - |d|^2 delta_ab),
+     *                 d = r_j - c_n.  Leaves from their particles layout[leaf] .. layout[leaf + 1] (leaf_to_internal: the
+     *                 LEAF part of the map, num_leaves entries, like leaf_source_centers), internal nodes level by level
+     *                 from level_range_host (num_levels + 1 entries, like upsweep_centers) as the sum of their children
+     *                 shifted to c_n: Q += Q_child + M_child (3 s_a s_b - |s|^2 delta_ab), s = c_child - c_n
+     * compute_gravity : for every target i of the groups [groups[g], groups[g + 1]) clipped to [first, last) -- one wave
+     *                 per group, longer groups 64 targets at a time, each such run with its own box -- a depth-first walk
+     *                 from the root: a node with expansion_centers[n][3] (MAC radius^2) == 0 is skipped; a node is OPENED
+     *                 iff R2 < |macSq_n| with the target box of evaluateMac (R/traversal/macs.hpp): centre (lo + hi) / 2,
+     *                 half-size (hi - lo) / 2 of the run's coordinates, dX = max(|tc - c_n| - ts, 0) componentwise,
+     *                 R2 = dx dx + (dy dy + dz dz); a node that is not opened is applied as a multipole (M2P), an opened
+     *                 leaf particle by particle (P2P, the target itself skipped), the children of an opened internal node
+     *                 are walked.  r^2 = |d|^2 + eps2;  P2P: a_i += G m_j d / r^3, phi_i -= G m_j / r (d = r_j - r_i);
+     *                 M2P (d = r_i - c_n): a += G [-M d / r^3 + Q d / r^5 - 5/2 (d.Q.d) d / r^7],
+     *                 phi -= G [M / r + 1/2 (d.Q.d) / r^5]; order 0 drops the Q terms (monopole), order 2 keeps them.
+     *                 ax, ay, az, phi (nullable) and the optional per-target interaction counts p2p_counts / m2p_counts
+     *                 (u32) are indexed by i - first and OVERWRITTEN; particles outside every group are left untouched.
+     *                 Periodic axes are refused (CSTONE_E_ARG: Ewald summation is not provided).  Synchronises the stream;
+     *                 a traversal stack overflow sets the sticky error word and the call returns CSTONE_E_INTERNAL.
+     * domain_compute_gravity : the two above on the domain's focus tree and its current expansion centres (CSTONE_E_ARG
+     *                 without them: no sync_grav / update_expansion_centers since the last sync; CSTONE_E_ARG for a
+     *                 periodic axis).  x, y, z, m: laid out like the last sync's results (what update_expansion_centers
+     *                 takes); the target groups (compute_group_splits, group size 64, tol_factor
+     *                 CSTONE_GRAVITY_GROUP_TOL) are computed once per sync, the multipoles on every call; end_index values
+     *                 are written to ax, ay, az and phi (nullable).  One rank only: the multipoles of a multi-rank focus
+     *                 tree would need the exchange of FocusLet::updateGrav.
+     * ------------------------------------------------------------------------------------------- */
+#define CSTONE_GRAVITY_GROUP_TOL 2.0f
+    int cstone_hip_upsweep_multipoles(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
+                                      const void* z, const void* m, const int32_t* leaf_to_internal, int num_leaves,
+                                      const uint32_t* layout, int num_levels, const int32_t* level_range_host,
+                                      const int32_t* child_offsets, int num_nodes, const void* expansion_centers,
+                                      void* multipoles);
+    int cstone_hip_compute_gravity(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
+                                   const void* z, const void* m, uint32_t first, uint32_t last, const uint32_t* groups,
+                                   uint32_t num_groups, const cstone_box* box_host, const int32_t* child_offsets,
+                                   const int32_t* internal_to_leaf, const uint32_t* layout, const void* expansion_centers,
+                                   const void* multipoles, int order, double G, double eps2, void* ax, void* ay,
+                                   void* az, void* phi, uint32_t* p2p_counts, uint32_t* m2p_counts);
+    int cstone_hip_domain_compute_gravity(cstone_hip_domain* dom, const void* x, const void* y, const void* z,
+                                          const void* m, int mass_bits, int order, double G, double eps2, void* ax,
+                                          void* ay, void* az, void* phi);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,104 @@
+"""Barnes-Hut gravity (csrc/gravity.hip) on the MI355X: one JSON line per configuration.
+
+For every cloud x precision x size: Domain.sync_grav, then the multipole upsweep (cstone_hip_upsweep_multipoles) and the
+group walk (cstone_hip_compute_gravity, order 2, theta 0.5) timed with device events after warm-up, the mean P2P / M2P
+interactions per target (from the walk's own counters, in a separate call), interactions/s and FLOP/s.
+
+FLOP per interaction, as the kernel writes them (-ffp-contract=off: no FMA; sqrt and the division count one each):
+  P2P  21: d 3, r^2 + eps^2 6, sqrt 1, 1/r 1, m/r 1, m/r^3 2, a 6, phi 1
+  M2P  54: d 3, r^2 + eps^2 6, sqrt 1, 1/r 1, 1/r^2 1, M/r^3 2, Q d 15, d.Q.d 5, 1/r^5 2, the d coefficient 4, a 9, phi 5
+
+    python tools/gravity_bench.py [--sizes 1e6 1e7] [--clouds plummer uniform] [--reals 64 32] [--reps 5]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "cornerstone-octree_amd"))
+
+P2P_FLOP, M2P_FLOP = 21, 54
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--sizes", nargs="+", type=float, default=[1e6, 1e7])
+    p.add_argument("--clouds", nargs="+", default=["plummer", "uniform"])
+    p.add_argument("--reals", nargs="+", type=int, default=[64, 32])
+    p.add_argument("--theta", type=float, default=0.5)
+    p.add_argument("--reps", type=int, default=5)
+    p.add_argument("--warmup", type=int, default=2)
+    a = p.parse_args()
+
+    import numpy as np
+    import torch
+
+    import cstone_amd
+    from cstone_amd.clouds import make_cloud
+    from cstone_amd.domain import Domain
+
+    ctx = cstone_amd.Context(0)
+    for n in [int(s) for s in a.sizes]:
+        for cloud in a.clouds:
+            for rb in a.reals:
+                dt = torch.float64 if rb == 64 else torch.float32
+                x, y, z, h, lim = make_cloud(cloud, n, n, "cuda", dt, 7)
+                m = torch.full((n,), 1.0 / n, dtype=dt, device="cuda")
+                dom = Domain(ctx, cstone_amd.HILBERT, 64, rb, 4096, 64, a.theta, cstone_amd.make_cbox(lim))
+                keys = torch.zeros(n, dtype=torch.int64, device="cuda")
+                scratch = [torch.empty_like(x) for _ in range(3)]
+                keys, x, y, z, h, m, scratch, _ = dom.sync_grav(keys, x, y, z, h, m, scratch)
+                v = dom.view()
+                L, M, ne = v.num_focus_leaves, v.num_focus_nodes, v.end_index
+
+                def dev(ptr, count, np_dt):
+                    return torch.from_numpy(dom.fetch(ptr, count, np_dt)).cuda()
+
+                child = dev(v.child_offsets, M + 1, np.int32)
+                itl = dev(v.internal_to_leaf, M, np.int32)
+                lti = dev(v.leaf_to_internal, M, np.int32)[M - L:].contiguous()
+                layout = dev(v.layout, L + 1, np.int32)
+                leaves = dev(v.focus_leaves, L + 1, np.int64)
+                levels = dom.fetch(v.level_range, 23, np.int32)
+                centers = dev(v.expansion_centers, 4 * M, np.float64 if rb == 64 else np.float32)
+                groups = ctx.compute_group_splits(0, ne, x, y, z, leaves, layout, v.box, 64,
+                                                  cstone_amd.GRAVITY_GROUP_TOL)
+                mp = ctx.upsweep_multipoles(x, y, z, m, lti, layout, levels, child, centers)
+
+                def timed(fn):
+                    for _ in range(a.warmup):
+                        fn()
+                    ts = []
+                    for _ in range(a.reps):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        fn()
+                        e1.record()
+                        e1.synchronize()
+                        ts.append(e0.elapsed_time(e1))
+                    return float(np.median(ts)), float(min(ts))
+
+                up_ms, up_min = timed(lambda: ctx.upsweep_multipoles(x, y, z, m, lti, layout, levels, child, centers,
+                                                                     multipoles=mp))
+                walk = lambda: ctx.compute_gravity(x, y, z, m, 0, ne, groups, v.box, child, itl, layout, centers, mp,
+                                                   order=2, potential=True)  # noqa: E731
+                walk_ms, walk_min = timed(walk)
+                *_, p2p, m2p = ctx.compute_gravity(x, y, z, m, 0, ne, groups, v.box, child, itl, layout, centers, mp,
+                                                   order=2, potential=True, counts=True)
+                p2p_mean, m2p_mean = p2p.double().mean().item(), m2p.double().mean().item()
+                inter = (p2p_mean + m2p_mean) * ne
+                flop = (p2p_mean * P2P_FLOP + m2p_mean * M2P_FLOP) * ne
+                print(json.dumps(dict(
+                    n=n, cloud=cloud, real_bits=rb, theta=a.theta, leaves=L, groups=int(groups.numel() - 1),
+                    upsweep_ms=round(up_ms, 4), walk_ms=round(walk_ms, 3), walk_ms_min=round(walk_min, 3),
+                    p2p_per_target=round(p2p_mean, 1), m2p_per_target=round(m2p_mean, 1),
+                    interactions_per_s=float(f"{inter / (walk_ms * 1e-3):.4g}"),
+                    flop_per_s=float(f"{flop / (walk_ms * 1e-3):.4g}"))), flush=True)
+                del dom, x, y, z, h, m, keys, scratch, mp, groups
+                torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
