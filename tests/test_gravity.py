@@ -59,8 +59,12 @@ def m2p(dx, dy, dz, mp, order, eps2):
 
 
 def walk_reference(t, lo, hi, order, G=1.0, eps2=0.0):
-    """the walk of cstone_hip_compute_gravity for the targets [lo, hi) (at most 64: one wave) restated:
-    (a, phi, p2p counts, m2p counts) per target.  t: the dict of tree_state()"""
+    """the walk of cstone_hip_compute_gravity for the target group [lo, hi) restated: (a, phi, p2p counts, m2p counts)
+    per target.  A group longer than 64 is walked as the kernel does, one run of 64 targets at a time, each run with its
+    own box.  t: the dict of tree_state() (or of a hand-built tree with the same keys)"""
+    if hi - lo > 64:
+        runs = [walk_reference(t, s, min(hi, s + 64), order, G, eps2) for s in range(lo, hi, 64)]
+        return tuple(np.concatenate(parts) for parts in zip(*runs))
     rdt = t["rdt"]
     xs, ys, zs = t["x"], t["y"], t["z"]
     ctr = t["centers"]
@@ -142,7 +146,8 @@ def uniform_cloud(n, seed):
     return x, y, z, np.full(n, 1.0 / n)
 
 
-def grav_domain(hip, x, y, z, m, rb=64, mass_bits=64, theta=0.5, kb=64, bucket_focus=64, bc=(0, 0, 0), bucket=None):
+def grav_domain(hip, x, y, z, m, rb=64, mass_bits=64, theta=0.5, kb=64, bucket_focus=64, bc=(0, 0, 0), bucket=None,
+                curve=None):
     """a single-rank domain after sync_grav of the cloud: (domain, xd, yd, zd, md) with the synced device arrays"""
     import torch
 
@@ -155,7 +160,8 @@ def grav_domain(hip, x, y, z, m, rb=64, mass_bits=64, theta=0.5, kb=64, bucket_f
     lo, hi = float(min(a.min() for a in (x, y, z))), float(max(a.max() for a in (x, y, z)))
     lim = [lo - 0.1 * (hi - lo), hi + 0.1 * (hi - lo)] * 3  # (an open box is measured by the first sync anyway)
     bucket = 64 * bucket_focus if bucket is None else bucket
-    dom = Domain(hip, cstone_amd.HILBERT, kb, rb, bucket, bucket_focus, theta, cstone_amd.make_cbox(lim, bc))
+    curve = cstone_amd.HILBERT if curve is None else curve
+    dom = Domain(hip, curve, kb, rb, bucket, bucket_focus, theta, cstone_amd.make_cbox(lim, bc))
     t = [torch.from_numpy(a.astype(rdt)).cuda() for a in (x, y, z)]
     h = torch.full((n,), 0.01, dtype=tdt, device="cuda")
     mbuf = torch.zeros(n * (rb // mass_bits), dtype=torch.float64 if mass_bits == 64 else torch.float32, device="cuda")
@@ -311,7 +317,8 @@ def test_upsweep_multipoles_equal_the_direct_formula(hip, rb, mass_bits):
 @pytest.mark.parametrize("rb", [64, 32])
 def test_walk_equals_the_restatement_exactly(hip, rb):
     """per-target P2P / M2P counts equal the NumPy restatement's exactly (same group boxes, same MAC arithmetic, no
-    contraction); accelerations and potentials to rounding (only the order of the sums differs)"""
+    contraction); accelerations and potentials to rounding (only the order of the sums differs): measured on the MI355X
+    6e-15 in f64, 4.3e-6 (a) and 2.7e-6 (phi) in f32, so the f32 bound is 2e-5"""
     x, y, z, m = clustered_cloud(40000, 12)
     dom, xd, yd, zd, md = grav_domain(hip, x, y, z, m, rb, rb, theta=0.5, bucket_focus=16)
     s = tree_state(hip, dom, xd, yd, zd, md)
@@ -321,7 +328,7 @@ def test_walk_equals_the_restatement_exactly(hip, rb):
     g = groups.cpu().numpy().astype(np.int64)
     assert g[0] == 0 and g[-1] == s["view"].end_index and (np.diff(g) <= 64).all()
     rng = np.random.default_rng(1)
-    tol = 1e-10 if rb == 64 else 1e-4
+    tol = 1e-10 if rb == 64 else 2e-5
     worst_a = worst_p = 0.0
     for k in rng.choice(g.size - 1, 60, replace=False):
         ra, rphi, rp2p, rm2p = walk_reference(s, g[k], g[k + 1], 2, G=0.7, eps2=eps2)
@@ -356,6 +363,9 @@ def test_opening_everything_is_the_direct_sum(hip):
 # Figures of this test on the MI355X (n = 40000, theta = 0.5, f64, 4096 targets; relative |da| against the direct sum):
 #   plummer  monopole median 9.1e-04  quadrupole median 5.1e-05  p99 2.3e-04
 #   uniform  monopole median 4.3e-04  quadrupole median 1.2e-04  p99 8.3e-04
+# and relative |dphi|:
+#   plummer  monopole median 2.2e-04  quadrupole median 6.5e-06  p99 3.8e-05
+#   uniform  monopole median 4.0e-05  quadrupole median 9.3e-06  p99 3.8e-05
 # (10^6 Plummer, 512 targets: quadrupole median 1.0e-04, p99 4.7e-04)
 @pytest.mark.gpu
 @pytest.mark.parametrize("cloud", ["plummer", "uniform"])
@@ -366,15 +376,20 @@ def test_accuracy_against_the_direct_sum(hip, cloud):
     s = tree_state(hip, dom, xd, yd, zd, md)
     groups = groups_of(hip, s, xd, yd, zd)
     tg = np.random.default_rng(4).choice(n, 4096, replace=False)
-    ra, _ = direct_sum(s["x"], s["y"], s["z"], s["m"], tg)
-    e = {}
+    ra, rphi = direct_sum(s["x"], s["y"], s["z"], s["m"], tg)
+    e, ep = {}, {}
     for order in (0, 2):
-        a, _, _, _ = gpu_gravity(hip, s, xd, yd, zd, md, groups, order=order)
+        a, phi, _, _ = gpu_gravity(hip, s, xd, yd, zd, md, groups, order=order)
         e[order] = rel_err(a[tg], ra)
+        ep[order] = np.abs(phi[tg] - rphi) / np.abs(rphi)
     med0, med2, p99 = np.median(e[0]), np.median(e[2]), np.percentile(e[2], 99)
-    print(f"{cloud}: monopole median {med0:.1e}  quadrupole median {med2:.1e}  p99 {p99:.1e}")
+    pmed0, pmed2, pp99 = np.median(ep[0]), np.median(ep[2]), np.percentile(ep[2], 99)
+    print(f"{cloud}: monopole median {med0:.1e}  quadrupole median {med2:.1e}  p99 {p99:.1e}; potential: monopole "
+          f"median {pmed0:.1e}  quadrupole median {pmed2:.1e}  p99 {pp99:.1e}")
     assert med2 < med0
     assert med2 <= 1e-3 and p99 <= 1e-2
+    assert pmed2 < pmed0
+    assert pmed2 <= 5e-5 and pp99 <= 2e-4
 
 
 @pytest.mark.gpu
