@@ -359,6 +359,9 @@ struct MrBase
                      const int* propBytes, int numProps, const void* keysIn, const void* mass = nullptr,
                      int massBits = 0) = 0;
     virtual int updateExpansionCenters(const void* x, const void* y, const void* z, const void* m, int massBits) = 0;
+    virtual int computeGravity(const void* x, const void* y, const void* z, const void* m, int massBits, int order,
+                               double G, double eps2, void* ax, void* ay, void* az, void* phi) = 0;
+    virtual int multipoles(const void** out, int32_t* numNodes)                           = 0;
     virtual int view(cstone_hip_domain_mr_view* out)                                     = 0;
     virtual void setHaloFactor(float f)                                                  = 0;
     virtual int exchangeHalos(void* array, int elemBytes)                                = 0;
@@ -553,6 +556,62 @@ public:
                                               massBits, gTree_.as<K>(), gLeavesHost_.data(), gLeaves_);
         haveExpansionCenters_ = rc == CSTONE_OK;
         return rc;
+    }
+
+    /*! Barnes-Hut gravity on the locally essential tree (csrc/gravity.hip): the multipoles of every node of the focus
+     *  tree about the current expansion centres (FocusLet::updateMultipoles, with its exchanges), then the LET walk over
+     *  the assigned particles.  x, y, z, m are laid out like the result arrays and read on the halo ranges too; the
+     *  caller has exchanged the halos of m.  Whatever makes the call fail on its arguments is decided before the first
+     *  collective, from state that is the same on every rank, so nobody is left waiting. */
+    int computeGravity(const void* x, const void* y, const void* z, const void* m, int massBits, int order, double G,
+                       double eps2, void* ax, void* ay, void* az, void* phi) override
+    {
+        if (!useLet_)
+            return fail(ctx_, CSTONE_E_ARG, "domain_mr_compute_gravity: needs the locally essential tree "
+                                            "(CSTONE_MR_HALOS_LET)");
+        if (firstCall_ || !let_ || !haveExpansionCenters_)
+            return fail(ctx_, CSTONE_E_ARG,
+                        "domain_mr_compute_gravity: no expansion centres (sync_grav or update_expansion_centers after "
+                        "the last sync)");
+        if (box_.bc[0] == 1 || box_.bc[1] == 1 || box_.bc[2] == 1)
+            return fail(ctx_, CSTONE_E_ARG, "domain_mr_compute_gravity: periodic boundaries need Ewald summation, which "
+                                            "is not provided");
+        // (a rank without particles may pass null arrays, like an empty rank of a sync)
+        const bool null = view_.num_particles_with_halos > 0 && (!x || !y || !z || !m || !ax || !ay || !az);
+        if ((massBits != 32 && massBits != 64) || (order != 0 && order != 2) || !(eps2 >= 0.0) || null)
+            return fail(ctx_, CSTONE_E_ARG, "domain_mr_compute_gravity: bad argument");
+        FocusLet<K, T>& t     = *let_;
+        const uint32_t si = view_.start_index, ei = view_.end_index;
+        const size_t mb   = size_t(massBits / 8);
+        if (gravGroupsSync_ != syncs_)
+        {
+            CS_TRY(gravGroups_.ensure(ctx_, size_t(ei - si + 1) * sizeof(uint32_t)));
+            uint32_t numGroups = 0;
+            if (ei > si)
+                CS_TRY(cstone_hip_compute_group_splits(ctx_, kb, rb, si, ei, x, y, z, t.leaves(), t.numLeaves(), t.layout(),
+                                                       &box_, 64, CSTONE_GRAVITY_GROUP_TOL, gravGroups_.as<uint32_t>(),
+                                                       size_t(ei - si) + 1, &numGroups));
+            gravNumGroups_  = numGroups;
+            gravGroupsSync_ = syncs_;
+        }
+        CS_TRY(t.updateMultipoles(static_cast<const T*>(x) + si, static_cast<const T*>(y) + si,
+                                  static_cast<const T*>(z) + si, static_cast<const char*>(m) + si * mb, massBits,
+                                  gTree_.as<K>(), gLeavesHost_.data(), gLeaves_));
+        if (ei == si) return CSTONE_OK;
+        const size_t off = size_t(si) * sizeof(T);
+        return cstone_hip_compute_gravity_let(
+            ctx_, rb, massBits, x, y, z, m, si, ei, gravGroups_.as<uint32_t>(), gravNumGroups_, &box_, t.childOffsets(),
+            t.internalToLeaf(), t.layout(), t.expansionCenters(), t.multipoles(), order, G, eps2,
+            static_cast<char*>(ax) + off, static_cast<char*>(ay) + off, static_cast<char*>(az) + off,
+            phi ? static_cast<char*>(phi) + off : nullptr, nullptr, nullptr, nullptr);
+    }
+
+    int multipoles(const void** out, int32_t* numNodes) override
+    {
+        const bool have = useLet_ && let_ && !firstCall_ && haveExpansionCenters_;
+        *out            = have ? let_->multipoles() : nullptr;
+        *numNodes       = have ? let_->numNodes() : 0;
+        return CSTONE_OK;
     }
 
     ~MultiRankDomain() override
@@ -1988,6 +2047,9 @@ private:
     int cutRedos_        = 0; // syncs whose assignment changed: cut points asked for twice
     float centerDriftTol_      = 1.05f; // Domain::centerDriftTol_ (R/domain/domain.hpp:665)
     bool haveExpansionCenters_ = false; // the last sync was a syncGrav (or updateExpansionCenters followed it)
+    DevBuf gravGroups_;                 // u32[gravNumGroups_ + 1]: target groups of computeGravity over the assigned range
+    uint32_t gravNumGroups_ = 0;
+    int gravGroupsSync_     = -1;       // ... computed for this sync
     bool overlapPlace_   = std::getenv("CSTONE_MR_NO_PLACE_OVERLAP") == nullptr; // x, y, z placed on the second stream
     bool placeForked_    = false; // ... and not joined yet
     DevBuf fTree_, fCounts_, fTmp_;
@@ -2121,6 +2183,20 @@ int cstone_hip_domain_mr_update_expansion_centers(cstone_hip_domain_mr* dom, con
 {
     if (!dom) return CSTONE_E_ARG;
     return dom->impl->updateExpansionCenters(x, y, z, m, mass_bits);
+}
+
+int cstone_hip_domain_mr_compute_gravity(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z,
+                                         const void* m, int mass_bits, int order, double G, double eps2, void* ax,
+                                         void* ay, void* az, void* phi)
+{
+    if (!dom) return CSTONE_E_ARG;
+    return dom->impl->computeGravity(x, y, z, m, mass_bits, order, G, eps2, ax, ay, az, phi);
+}
+
+int cstone_hip_domain_mr_multipoles_get(cstone_hip_domain_mr* dom, const void** multipoles, int32_t* num_nodes)
+{
+    if (!dom || !multipoles || !num_nodes) return CSTONE_E_ARG;
+    return dom->impl->multipoles(multipoles, num_nodes);
 }
 
 int cstone_hip_domain_mr_sync(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z, const void* h,

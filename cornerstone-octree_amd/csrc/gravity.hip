@@ -13,6 +13,15 @@
 // applied as a multipole to all 64 lanes (M2P) or, for an opened leaf, its particles are fetched with one coalesced
 // load per array and handed round with v_readlane (P2P), the inner loop touching no memory.
 // Compiled with -ffp-contract=off like the rest of the library: the MAC arithmetic is the one the tests restate.
+//
+// On a locally essential tree (cstone_hip_compute_gravity_let, the LET flag of the walk) one more rule applies: a node
+// that fails the MAC, has no children and has an EMPTY particle range is applied as a multipole.  Such a leaf belongs to
+// another rank and is no halo: syncGrav left it without particles because every focus CELL of this rank passes the
+// vector MAC against it (markMacs), and every real target lies in a focus cell, so its multipole is within the MAC's
+// error bound for each target.  The walk only asks to open it because it tests the MAC against the bounding box of 64
+// consecutive targets, and on a non-convex piece of the space-filling curve that box reaches outside the focus.
+// Without the rule the leaf's mass would vanish from the sum.  node, child and the range are wave-uniform already, so
+// the rule costs a scalar branch and no lane mask.
 #include <algorithm>
 
 #include "ctx.hpp"
@@ -120,13 +129,14 @@ __global__ __launch_bounds__(256) void upsweepMultipolesKernel(NodeIdx firstCell
 
 /*! The walk of one target group per wave (see the head of the file).  Outputs are indexed by i - first; lanes without a
  *  target (the tail of a group) take the group's first particle as a stand-in and write nothing. */
-template<class T, class Tm, bool QUAD>
+template<class T, class Tm, bool QUAD, bool LET>
 __global__ __launch_bounds__(GW_BLOCK) void gravityWalkKernel(
     const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ z, const Tm* __restrict__ m, uint32_t first,
     uint32_t last, const uint32_t* __restrict__ groups, uint32_t numGroups, const NodeIdx* __restrict__ childOffsets,
     const NodeIdx* __restrict__ internalToLeaf, const uint32_t* __restrict__ layout, const T* __restrict__ centers,
     const T* __restrict__ mp, T G, T eps2, T* __restrict__ ax, T* __restrict__ ay, T* __restrict__ az,
-    T* __restrict__ phi, uint32_t* __restrict__ p2pCounts, uint32_t* __restrict__ m2pCounts, int* __restrict__ errors)
+    T* __restrict__ phi, uint32_t* __restrict__ p2pCounts, uint32_t* __restrict__ m2pCounts,
+    uint32_t* __restrict__ letCounts, int* __restrict__ errors)
 {
     __shared__ NodeIdx stacks[GW_WAVES][GW_STACK];
     const int lane = int(threadIdx.x & 63u), wave = int(threadIdx.x >> 6);
@@ -151,7 +161,7 @@ __global__ __launch_bounds__(GW_BLOCK) void gravityWalkKernel(
         const T tsx = (hix - lox) * T(0.5), tsy = (hiy - loy) * T(0.5), tsz = (hiz - loz) * T(0.5);
 
         T axi = 0, ayi = 0, azi = 0, phii = 0;
-        uint32_t nP2P = 0, nM2P = 0;
+        uint32_t nP2P = 0, nM2P = 0, nLet = 0;
 
         if (lane == 0) stack[0] = 0;
         int top = 1;
@@ -169,7 +179,29 @@ __global__ __launch_bounds__(GW_BLOCK) void gravityWalkKernel(
             dX += fabs(dX), dY += fabs(dY), dZ += fabs(dZ);
             dX *= T(0.5), dY *= T(0.5), dZ *= T(0.5);
             const T R2      = dX * dX + (dY * dY + dZ * dZ); // right fold, as traverseNeighbors
-            const bool open = uniform(int(R2 < fabs(macSq))) != 0;
+            bool open = uniform(int(R2 < fabs(macSq))) != 0;
+
+            NodeIdx child = 0;
+            uint32_t jb = 0, je = 0;
+            if (open)
+            {
+                child = uniform(childOffsets[node]);
+                if (child == 0)
+                {
+                    const NodeIdx leaf = uniform(internalToLeaf[node]);
+                    jb                 = uint32_t(uniform(int32_t(layout[leaf])));
+                    je                 = uint32_t(uniform(int32_t(layout[leaf + 1])));
+                    if constexpr (LET)
+                    {
+                        // a massive leaf whose particles are not here (see the head of the file): its multipole
+                        if (jb == je)
+                        {
+                            open = false;
+                            ++nLet;
+                        }
+                    }
+                }
+            }
 
             if (!open)
             {
@@ -205,7 +237,6 @@ __global__ __launch_bounds__(GW_BLOCK) void gravityWalkKernel(
                 continue;
             }
 
-            const NodeIdx child = uniform(childOffsets[node]);
             if (child != 0)
             {
                 if (top + 8 > GW_STACK)
@@ -219,9 +250,6 @@ __global__ __launch_bounds__(GW_BLOCK) void gravityWalkKernel(
             }
 
             // P2P with every particle of the opened leaf, d = r_j - r_i, the target itself skipped
-            const NodeIdx leaf = uniform(internalToLeaf[node]);
-            const uint32_t jb  = uint32_t(uniform(int32_t(layout[leaf])));
-            const uint32_t je  = uint32_t(uniform(int32_t(layout[leaf + 1])));
             for (uint32_t base = jb; base < je; base += 64)
             {
                 const int cnt = int(min(64u, je - base));
@@ -256,18 +284,19 @@ __global__ __launch_bounds__(GW_BLOCK) void gravityWalkKernel(
             if (phi) phi[t] = G * phii;
             if (p2pCounts) p2pCounts[t] = nP2P;
             if (m2pCounts) m2pCounts[t] = nM2P;
+            if constexpr (LET)
+            {
+                if (letCounts) letCounts[t] = nLet;
+            }
         }
     }
 }
 
-template<class T, class Tm>
-int upsweepMultipoles(cstone_hip_ctx* ctx, const void* x, const void* y, const void* z, const void* m,
-                      const int32_t* leafToInternal, int numLeaves, const uint32_t* layout, int numLevels,
-                      const int32_t* levelRangeHost, const int32_t* childOffsets, const void* centers, void* multipoles)
+//! the internal nodes of every level, deepest first, from their children
+template<class T>
+int upsweepLevels(cstone_hip_ctx* ctx, int numLevels, const int32_t* levelRangeHost, const int32_t* childOffsets,
+                  const void* centers, void* multipoles)
 {
-    hipLaunchKernelGGL((leafMultipolesKernel<T, Tm>), gridFor(size_t(numLeaves), 256), 256, 0, ctx->stream,
-                       (const T*)x, (const T*)y, (const T*)z, (const Tm*)m, leafToInternal, numLeaves, layout,
-                       (const T*)centers, (T*)multipoles);
     for (int level = numLevels - 1; level >= 0; --level)
     {
         const int first = levelRangeHost[level], last = levelRangeHost[level + 1];
@@ -280,29 +309,85 @@ int upsweepMultipoles(cstone_hip_ctx* ctx, const void* x, const void* y, const v
 }
 
 template<class T, class Tm>
+int upsweepMultipoles(cstone_hip_ctx* ctx, const void* x, const void* y, const void* z, const void* m,
+                      const int32_t* leafToInternal, int numLeaves, const uint32_t* layout, int numLevels,
+                      const int32_t* levelRangeHost, const int32_t* childOffsets, const void* centers, void* multipoles)
+{
+    hipLaunchKernelGGL((leafMultipolesKernel<T, Tm>), gridFor(size_t(numLeaves), 256), 256, 0, ctx->stream,
+                       (const T*)x, (const T*)y, (const T*)z, (const Tm*)m, leafToInternal, numLeaves, layout,
+                       (const T*)centers, (T*)multipoles);
+    return upsweepLevels<T>(ctx, numLevels, levelRangeHost, childOffsets, centers, multipoles);
+}
+
+template<class T, class Tm, bool QUAD, bool LET>
+void launchWalk(cstone_hip_ctx* ctx, const void* x, const void* y, const void* z, const void* m, uint32_t first,
+                uint32_t last, const uint32_t* groups, uint32_t numGroups, const int32_t* childOffsets,
+                const int32_t* internalToLeaf, const uint32_t* layout, const void* centers, const void* multipoles,
+                double G, double eps2, void* ax, void* ay, void* az, void* phi, uint32_t* p2p, uint32_t* m2p,
+                uint32_t* letM2p)
+{
+    hipLaunchKernelGGL((gravityWalkKernel<T, Tm, QUAD, LET>), gridFor(numGroups, GW_WAVES), GW_BLOCK, 0, ctx->stream,
+                       (const T*)x, (const T*)y, (const T*)z, (const Tm*)m, first, last, groups, numGroups, childOffsets,
+                       internalToLeaf, layout, (const T*)centers, (const T*)multipoles, T(G), T(eps2), (T*)ax, (T*)ay,
+                       (T*)az, (T*)phi, p2p, m2p, letM2p, ctx->devScalars + 63);
+}
+
+template<class T, class Tm>
 int launchGravity(cstone_hip_ctx* ctx, const void* x, const void* y, const void* z, const void* m, uint32_t first,
                   uint32_t last, const uint32_t* groups, uint32_t numGroups, const int32_t* childOffsets,
                   const int32_t* internalToLeaf, const uint32_t* layout, const void* centers, const void* multipoles,
-                  int order, double G, double eps2, void* ax, void* ay, void* az, void* phi, uint32_t* p2p,
-                  uint32_t* m2p)
+                  int order, bool let, double G, double eps2, void* ax, void* ay, void* az, void* phi, uint32_t* p2p,
+                  uint32_t* m2p, uint32_t* letM2p)
 {
-    const unsigned grid = gridFor(numGroups, GW_WAVES);
-    int* errors         = ctx->devScalars + 63;
-    if (order == 2)
-        hipLaunchKernelGGL((gravityWalkKernel<T, Tm, true>), grid, GW_BLOCK, 0, ctx->stream, (const T*)x, (const T*)y,
-                           (const T*)z, (const Tm*)m, first, last, groups, numGroups, childOffsets, internalToLeaf,
-                           layout, (const T*)centers, (const T*)multipoles, T(G), T(eps2), (T*)ax, (T*)ay, (T*)az,
-                           (T*)phi, p2p, m2p, errors);
-    else
-        hipLaunchKernelGGL((gravityWalkKernel<T, Tm, false>), grid, GW_BLOCK, 0, ctx->stream, (const T*)x, (const T*)y,
-                           (const T*)z, (const Tm*)m, first, last, groups, numGroups, childOffsets, internalToLeaf,
-                           layout, (const T*)centers, (const T*)multipoles, T(G), T(eps2), (T*)ax, (T*)ay, (T*)az,
-                           (T*)phi, p2p, m2p, errors);
+#define CSTONE_WALK(QUAD, LET)                                                                                         \
+    launchWalk<T, Tm, QUAD, LET>(ctx, x, y, z, m, first, last, groups, numGroups, childOffsets, internalToLeaf, layout, \
+                                 centers, multipoles, G, eps2, ax, ay, az, phi, p2p, m2p, letM2p)
+    if (order == 2) { let ? CSTONE_WALK(true, true) : CSTONE_WALK(true, false); }
+    else { let ? CSTONE_WALK(false, true) : CSTONE_WALK(false, false); }
+#undef CSTONE_WALK
     CS_HIP(ctx, hipGetLastError());
     return CSTONE_OK;
 }
 
+//! the checks and the dispatch behind cstone_hip_compute_gravity and cstone_hip_compute_gravity_let
+int computeGravity(cstone_hip_ctx* ctx, bool let, const char* name, int real_bits, int mass_bits, const void* x,
+                   const void* y, const void* z, const void* m, uint32_t first, uint32_t last, const uint32_t* groups,
+                   uint32_t num_groups, const cstone_box* box_host, const int32_t* child_offsets,
+                   const int32_t* internal_to_leaf, const uint32_t* layout, const void* expansion_centers,
+                   const void* multipoles, int order, double G, double eps2, void* ax, void* ay, void* az, void* phi,
+                   uint32_t* p2p_counts, uint32_t* m2p_counts, uint32_t* let_m2p_counts);
+
 bool badBits(int bits) { return bits != 32 && bits != 64; }
+
+int computeGravity(cstone_hip_ctx* ctx, bool let, const char* name, int real_bits, int mass_bits, const void* x,
+                   const void* y, const void* z, const void* m, uint32_t first, uint32_t last, const uint32_t* groups,
+                   uint32_t num_groups, const cstone_box* box_host, const int32_t* child_offsets,
+                   const int32_t* internal_to_leaf, const uint32_t* layout, const void* expansion_centers,
+                   const void* multipoles, int order, double G, double eps2, void* ax, void* ay, void* az, void* phi,
+                   uint32_t* p2p_counts, uint32_t* m2p_counts, uint32_t* let_m2p_counts)
+{
+    if (!ctx || badBits(real_bits) || badBits(mass_bits) || (order != 0 && order != 2) || !(eps2 >= 0.0) ||
+        last < first || !x || !y || !z || !m || (num_groups && !groups) || !box_host || !child_offsets ||
+        !internal_to_leaf || !layout || !expansion_centers || !multipoles || !ax || !ay || !az)
+        return fail(ctx, CSTONE_E_ARG, "%s: bad argument", name);
+    if (box_host->bc[0] == 1 || box_host->bc[1] == 1 || box_host->bc[2] == 1)
+        return fail(ctx, CSTONE_E_ARG, "%s: periodic boundaries need Ewald summation, which is not provided", name);
+    if (last == first || num_groups == 0) return CSTONE_OK;
+    {
+        StageTimer timer(ctx, CSTONE_STAGE_GRAVITY);
+#define CSTONE_GRAVITY(T, Tm)                                                                                          \
+    launchGravity<T, Tm>(ctx, x, y, z, m, first, last, groups, num_groups, child_offsets, internal_to_leaf, layout,     \
+                         expansion_centers, multipoles, order, let, G, eps2, ax, ay, az, phi, p2p_counts, m2p_counts,   \
+                         let_m2p_counts)
+        int rc;
+        if (real_bits == 64) rc = mass_bits == 64 ? CSTONE_GRAVITY(double, double) : CSTONE_GRAVITY(double, float);
+        else rc = mass_bits == 64 ? CSTONE_GRAVITY(float, double) : CSTONE_GRAVITY(float, float);
+#undef CSTONE_GRAVITY
+        CS_TRY(rc);
+    }
+    // a stack overflow of the walk sets the sticky error word: report it here instead of returning a partial result
+    return cstone_hip_ctx_sync(ctx);
+}
 
 } // namespace
 
@@ -343,26 +428,39 @@ int cstone_hip_compute_gravity(cstone_hip_ctx* ctx, int real_bits, int mass_bits
                                const void* multipoles, int order, double G, double eps2, void* ax, void* ay, void* az,
                                void* phi, uint32_t* p2p_counts, uint32_t* m2p_counts)
 {
-    if (!ctx || badBits(real_bits) || badBits(mass_bits) || (order != 0 && order != 2) || !(eps2 >= 0.0) ||
-        last < first || !x || !y || !z || !m || (num_groups && !groups) || !box_host || !child_offsets ||
-        !internal_to_leaf || !layout || !expansion_centers || !multipoles || !ax || !ay || !az)
-        return fail(ctx, CSTONE_E_ARG, "compute_gravity: bad argument");
-    if (box_host->bc[0] == 1 || box_host->bc[1] == 1 || box_host->bc[2] == 1)
-        return fail(ctx, CSTONE_E_ARG, "compute_gravity: periodic boundaries need Ewald summation, which is not provided");
-    if (last == first || num_groups == 0) return CSTONE_OK;
-    {
-        StageTimer timer(ctx, CSTONE_STAGE_GRAVITY);
-#define CSTONE_GRAVITY(T, Tm)                                                                                          \
-    launchGravity<T, Tm>(ctx, x, y, z, m, first, last, groups, num_groups, child_offsets, internal_to_leaf, layout,     \
-                         expansion_centers, multipoles, order, G, eps2, ax, ay, az, phi, p2p_counts, m2p_counts)
-        int rc;
-        if (real_bits == 64) rc = mass_bits == 64 ? CSTONE_GRAVITY(double, double) : CSTONE_GRAVITY(double, float);
-        else rc = mass_bits == 64 ? CSTONE_GRAVITY(float, double) : CSTONE_GRAVITY(float, float);
-#undef CSTONE_GRAVITY
-        CS_TRY(rc);
-    }
-    // a stack overflow of the walk sets the sticky error word: report it here instead of returning a partial result
-    return cstone_hip_ctx_sync(ctx);
+    return computeGravity(ctx, false, "compute_gravity", real_bits, mass_bits, x, y, z, m, first, last, groups,
+                          num_groups, box_host, child_offsets, internal_to_leaf, layout, expansion_centers, multipoles,
+                          order, G, eps2, ax, ay, az, phi, p2p_counts, m2p_counts, nullptr);
+}
+
+int cstone_hip_compute_gravity_let(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
+                                   const void* z, const void* m, uint32_t first, uint32_t last, const uint32_t* groups,
+                                   uint32_t num_groups, const cstone_box* box_host, const int32_t* child_offsets,
+                                   const int32_t* internal_to_leaf, const uint32_t* layout,
+                                   const void* expansion_centers, const void* multipoles, int order, double G,
+                                   double eps2, void* ax, void* ay, void* az, void* phi, uint32_t* p2p_counts,
+                                   uint32_t* m2p_counts, uint32_t* let_m2p_counts)
+{
+    return computeGravity(ctx, true, "compute_gravity_let", real_bits, mass_bits, x, y, z, m, first, last, groups,
+                          num_groups, box_host, child_offsets, internal_to_leaf, layout, expansion_centers, multipoles,
+                          order, G, eps2, ax, ay, az, phi, p2p_counts, m2p_counts, let_m2p_counts);
+}
+
+int cstone_hip_upsweep_multipoles_nodes(cstone_hip_ctx* ctx, int real_bits, int num_levels,
+                                        const int32_t* level_range_host, const int32_t* child_offsets, int num_nodes,
+                                        const void* expansion_centers, void* multipoles)
+{
+    if (!ctx || badBits(real_bits) || num_levels < 0 || num_nodes < 1 || !level_range_host || !child_offsets ||
+        !expansion_centers || !multipoles)
+        return fail(ctx, CSTONE_E_ARG, "upsweep_multipoles_nodes: bad argument");
+    for (int level = 0; level < num_levels; ++level)
+        if (level_range_host[level] < 0 || level_range_host[level + 1] < level_range_host[level] ||
+            level_range_host[level + 1] > num_nodes)
+            return fail(ctx, CSTONE_E_ARG, "upsweep_multipoles_nodes: level_range_host is not a range of [0, num_nodes)");
+    StageTimer timer(ctx, CSTONE_STAGE_MULTIPOLES);
+    if (real_bits == 64)
+        return upsweepLevels<double>(ctx, num_levels, level_range_host, child_offsets, expansion_centers, multipoles);
+    return upsweepLevels<float>(ctx, num_levels, level_range_host, child_offsets, expansion_centers, multipoles);
 }
 
 } // extern "C"

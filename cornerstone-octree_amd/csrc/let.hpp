@@ -231,6 +231,50 @@ public:
         return cstone_hip_set_mac(ctx_, curve_, kb, rb, prefixes_.p, numNodesOf(L_), centers_.p, 1.0f / theta_, &box_);
     }
 
+    /*! The multipoles (M, Qxx, Qxy, Qxz, Qyy, Qyz, Qzz, 0) of EVERY node of the focus tree about its expansion centre,
+     *  built the way updateCenters builds the centres: my leaves from my particles (x, y, z, m: the assigned particles,
+     *  device), upsweep; the nodes larger than any rank's domain through the global tree, swept up about the global
+     *  nodes' centres that the centre exchange left in gCenters_ (a multipole moves to its parent by a shift, not by a
+     *  sum); the peers' regions from the peers; upsweep.  A multipole that arrives from another rank is about that
+     *  rank's centre of the node, which is the centre this rank holds for it, because the same routes delivered it.  So
+     *  the result is valid for the centres of the last updateGrav / updateExpansionCenters and must follow either.
+     *  Collective.  (Not instantiated by clients of this header that have no gravity entry points.) */
+    int updateMultipoles(const T* x, const T* y, const T* z, const void* m, int massBits, const K* globalLeaves,
+                         const K* globalLeavesHost, int numGlobalLeaves)
+    {
+        const int L = L_, M = numNodesOf(L), I = numInternalOf(L);
+        const int e = int(8 * sizeof(T));
+        haveMultipoles_ = false;
+        LET_TRY(multipoles_.ensure(size_t(M) * e));
+        uint32_t* lay = nullptr;
+        LET_TRY(ownLayout(&lay));
+        LET_TRY(readBack(levelRange_.as<int32_t>(), levelHost_, size_t(maxLevel) + 2));
+        LET_TRY(cstone_hip_upsweep_multipoles(ctx_, rb, massBits, x, y, z, m, lti_.as<int32_t>() + I, L, lay, maxLevel,
+                                              levelHost_, child_.as<int32_t>(), M, centers_.p, multipoles_.p));
+        if (P_ > 1)
+        {
+            const int GL = numGlobalLeaves;
+            if (GL != gCentersLeaves_)
+                return fail(CSTONE_E_INTERNAL, "multipoles: the global tree has %d leaves, the centre exchange saw %d", GL,
+                            gCentersLeaves_);
+            const void* gNodeCenters = gCenters_.as<char>() + size_t(GL + 1) * 4 * sizeof(T);
+            LET_TRY(globalNodeExchange(globalLeaves, globalLeavesHost, GL, e, gMultipoles_, multipoles_.p,
+                                       [&](void* nodeMp)
+                                       {
+                                           return cstone_hip_upsweep_multipoles_nodes(ctx_, rb, maxLevel, gLevelHost_,
+                                                                                      gChild_.as<int32_t>(), numNodesOf(GL),
+                                                                                      gNodeCenters, nodeMp);
+                                       }));
+            LET_TRY(peerNodeExchange(e, multipoles_.p));
+            LET_TRY(cstone_hip_upsweep_multipoles_nodes(ctx_, rb, maxLevel, levelHost_, child_.as<int32_t>(), M,
+                                                        centers_.p, multipoles_.p));
+        }
+        haveMultipoles_ = true;
+        return CSTONE_OK;
+    }
+    //! T[numNodes()][8] of the last updateMultipoles, or null
+    const T* multipoles() const { return haveMultipoles_ ? multipoles_.as<T>() : nullptr; }
+
     //! (centre of mass, MAC radius^2) of every node of the focus tree: Vec4<T>[numNodes()], after updateGrav
     const T* expansionCenters() const { return centers_.as<T>(); }
     const char* macs() const { return macs_.as<char>(); }
@@ -347,7 +391,7 @@ private:
                 &macs_, &centers_, &geoCenters_, &geoSizes_, &opsAll_, &ops_, &scratchKeys_, &scratchKeys2_, &scratchIdx_,
                 &scratchIdx2_, &scratchU64_, &gPrefixes_, &gChild_, &gParents_, &gLevelRange_, &gItl_, &gLti_, &treelets_,
                 &treeletIdx_, &tlFlags_, &tlScan_, &sendBuf_, &recvBuf_, &layout_, &flags_, &radii_, &rangeOffsets_,
-                &rangeScan_, &haloSend_, &haloRecv_, &rowBuf_, &gSeg_, &gCenters_};
+                &rangeScan_, &haloSend_, &haloRecv_, &rowBuf_, &gSeg_, &gCenters_, &multipoles_, &gMultipoles_};
     }
 
     int fail(int code, const char* fmt, ...)
@@ -859,6 +903,7 @@ private:
         *done = true;
         if (oldStart == focusStart && oldEnd == focusEnd) return CSTONE_OK;
         const int L = L_, M = numNodesOf(L), I = numInternalOf(L);
+        haveMultipoles_ = false; // (they are about the centres this call replaces)
         LET_TRY(centers_.ensure(size_t(M) * 4 * sizeof(T)));
         LET_TRY(cstone_hip_geo_mac_spheres(ctx_, curve_, kb, rb, prefixes_.p, M, centers_.p, invTheta, &box));
         LET_TRY(macs_.ensure(size_t(M)));
@@ -1210,16 +1255,10 @@ private:
     //! addMacs (:601-610): a leaf whose node fails the MAC becomes a halo leaf
     int addMacs() { return cstone_hip_add_macs(ctx_, macs_.as<char>(), lti_.as<int32_t>() + numInternalOf(L_), L_, flags_.as<int32_t>()); }
 
-    /*! updateCenters (octree_focus_mpi.hpp:369-449): mass centres of my leaves from the particles, upsweep, the nodes
-     *  that are larger than any rank's domain through the global tree (globalCenterExchange), the peers' regions from
-     *  the peers, upsweep */
-    int updateCenters(const T* x, const T* y, const T* z, const void* m, int massBits, const K* globalLeaves,
-                      const K* globalLeavesHost, int numGlobalLeaves)
+    //! temporary pre-halo layout: offsets of MY leaves among my particles, zero-sized ranges everywhere else
+    int ownLayout(uint32_t** out)
     {
-        const int L = L_, M = numNodesOf(L), I = numInternalOf(L);
-        const int first = assignment_[rank_].start, last = assignment_[rank_].end;
-        LET_TRY(centers_.ensure(size_t(M) * 4 * sizeof(T)));
-        // temporary pre-halo layout: offsets of MY leaves among my particles, zero-sized ranges everywhere else
+        const int L = L_, first = assignment_[rank_].start, last = assignment_[rank_].end;
         LET_TRY(scratchIdx2_.ensure(size_t(L + 2) * 4));
         uint32_t* lay = scratchIdx2_.as<uint32_t>();
         LET_TRY(cstone_hip_memset(ctx_, lay, 0, size_t(first + 1) * 4));
@@ -1232,6 +1271,21 @@ private:
             const uint32_t total = uint32_t(numKeys_);
             LET_TRY(cstone_hip_fill(ctx_, 4, lay + last + 1, size_t(L - last), &total));
         }
+        *out = lay;
+        return CSTONE_OK;
+    }
+
+    /*! updateCenters (octree_focus_mpi.hpp:369-449): mass centres of my leaves from the particles, upsweep, the nodes
+     *  that are larger than any rank's domain through the global tree (globalCenterExchange), the peers' regions from
+     *  the peers, upsweep */
+    int updateCenters(const T* x, const T* y, const T* z, const void* m, int massBits, const K* globalLeaves,
+                      const K* globalLeavesHost, int numGlobalLeaves)
+    {
+        const int L = L_, M = numNodesOf(L), I = numInternalOf(L);
+        haveMultipoles_ = false; // (they are about the centres this call replaces)
+        LET_TRY(centers_.ensure(size_t(M) * 4 * sizeof(T)));
+        uint32_t* lay = nullptr;
+        LET_TRY(ownLayout(&lay));
         LET_TRY(cstone_hip_leaf_source_centers(ctx_, rb, massBits, rb, x, y, z, m, lti_.as<int32_t>() + I, L, lay,
                                                centers_.p));
         LET_TRY(readBack(levelRange_.as<int32_t>(), levelHost_, size_t(maxLevel) + 2));
@@ -1240,30 +1294,38 @@ private:
         {
             LET_TRY(globalCenterExchange(globalLeaves, globalLeavesHost, numGlobalLeaves));
             // the peers' regions from their owners (peerExchange of SourceCenterType, :436-447), like the counts
-            std::vector<uint64_t> sendCounts(P_, 0), recvCounts(P_, 0);
-            uint64_t sendTotal = 0, recvTotal = 0;
-            for (int peer : peers_)
-            {
-                sendCounts[peer] = tlCount_[peer];
-                recvCounts[peer] = uint64_t(assignment_[peer].count());
-                sendTotal += sendCounts[peer];
-                recvTotal += recvCounts[peer];
-            }
-            const int e = int(4 * sizeof(T));
-            LET_TRY(sendBuf_.ensure(std::max<uint64_t>(sendTotal, 1) * e));
-            LET_TRY(recvBuf_.ensure(std::max<uint64_t>(recvTotal, 1) * e));
-            if (sendTotal)
-                LET_TRY(cstone_hip_gather(ctx_, e, treeletIdx_.as<uint32_t>(), size_t(sendTotal), centers_.p, sendBuf_.p));
-            LET_TRY(allToAll(sendBuf_.p, sendCounts, e, recvBuf_.p, recvCounts));
-            uint64_t at = 0;
-            for (int peer : peers_)
-            {
-                if (recvCounts[peer])
-                    LET_TRY(cstone_hip_scatter(ctx_, e, lti_.as<uint32_t>() + I + assignment_[peer].start,
-                                               size_t(recvCounts[peer]), recvBuf_.template as<char>() + at * e, centers_.p));
-                at += recvCounts[peer];
-            }
+            LET_TRY(peerNodeExchange(int(4 * sizeof(T)), centers_.p));
             LET_TRY(cstone_hip_upsweep_centers(ctx_, rb, maxLevel, levelHost_, child_.as<int32_t>(), centers_.p));
+        }
+        return CSTONE_OK;
+    }
+
+    //! values of e bytes per node (centres, multipoles): the leaves of the peers' ranges from their owners' nodes of the
+    //! same key ranges, along the treelet routes of the last tree update
+    int peerNodeExchange(int e, void* nodeValues)
+    {
+        const int I = numInternalOf(L_);
+        std::vector<uint64_t> sendCounts(P_, 0), recvCounts(P_, 0);
+        uint64_t sendTotal = 0, recvTotal = 0;
+        for (int peer : peers_)
+        {
+            sendCounts[peer] = tlCount_[peer];
+            recvCounts[peer] = uint64_t(assignment_[peer].count());
+            sendTotal += sendCounts[peer];
+            recvTotal += recvCounts[peer];
+        }
+        LET_TRY(sendBuf_.ensure(std::max<uint64_t>(sendTotal, 1) * e));
+        LET_TRY(recvBuf_.ensure(std::max<uint64_t>(recvTotal, 1) * e));
+        if (sendTotal)
+            LET_TRY(cstone_hip_gather(ctx_, e, treeletIdx_.as<uint32_t>(), size_t(sendTotal), nodeValues, sendBuf_.p));
+        LET_TRY(allToAll(sendBuf_.p, sendCounts, e, recvBuf_.p, recvCounts));
+        uint64_t at = 0;
+        for (int peer : peers_)
+        {
+            if (recvCounts[peer])
+                LET_TRY(cstone_hip_scatter(ctx_, e, lti_.as<uint32_t>() + I + assignment_[peer].start,
+                                           size_t(recvCounts[peer]), recvBuf_.template as<char>() + at * e, nodeValues));
+            at += recvCounts[peer];
         }
         return CSTONE_OK;
     }
@@ -1274,8 +1336,18 @@ private:
      *  neither I nor a peer own take their centres from the global nodes of the same key range (extractGlobal) */
     int globalCenterExchange(const K* globalLeaves, const K* gl, int GL)
     {
+        gCentersLeaves_ = GL;
+        return globalNodeExchange(globalLeaves, gl, GL, int(4 * sizeof(T)), gCenters_, centers_.p, [&](void* nodeCen)
+                                  { return cstone_hip_upsweep_centers(ctx_, rb, maxLevel, gLevelHost_, gChild_.as<int32_t>(), nodeCen); });
+    }
+
+    //! the global exchange for values of e bytes per node (centres, multipoles); store: [GL + 1] values in leaf order
+    //! followed by the values of the global tree's nodes, which upsweepGlobal completes from its leaves
+    template<class Upsweep>
+    int globalNodeExchange(const K* globalLeaves, const K* gl, int GL, int e, LetBuf& store, void* nodeValues,
+                           Upsweep&& upsweepGlobal)
+    {
         const int L = L_, I = numInternalOf(L);
-        const int e = int(4 * sizeof(T));
         const int GM = numNodesOf(GL), GI = numInternalOf(GL);
         // findNodeAbove(globalLeaves, key) for the assignment of the last tree update (host copy of the global leaves)
         auto above = [&](K key) { return int(std::lower_bound(gl, gl + GL + 1, key) - gl); };
@@ -1293,10 +1365,10 @@ private:
                         gFirst, gLast, displ[rank_], displ[rank_ + 1]);
         // populateGlobal: the focus node of every global leaf of mine
         LET_TRY(gSeg_.ensure(size_t(longest) * e * (size_t(P_) + 1)));
-        LET_TRY(gCenters_.ensure(size_t(std::max(GM, GL) + 1) * e * 2));
+        LET_TRY(store.ensure(size_t(std::max(GM, GL) + 1) * e * 2));
         char* seg     = gSeg_.as<char>();
         char* all     = seg + size_t(longest) * e;
-        char* leafCen = gCenters_.as<char>();                    // [GL] in leaf order
+        char* leafCen = store.template as<char>();               // [GL] in leaf order
         char* nodeCen = leafCen + size_t(GL + 1) * e;            // [GM] in node order
         LET_TRY(cstone_hip_memset(ctx_, seg, 0, size_t(longest) * e));
         if (mine > 0)
@@ -1304,7 +1376,7 @@ private:
             LET_TRY(scratchIdx_.ensure(size_t(mine + 1) * 4));
             LET_TRY(cstone_hip_locate_nodes(ctx_, kb, globalLeaves + gFirst, size_t(mine) + 1, prefixes_.p,
                                             levelRange_.as<int32_t>(), scratchIdx_.as<int32_t>()));
-            LET_TRY(cstone_hip_gather(ctx_, e, scratchIdx_.as<uint32_t>(), size_t(mine), centers_.p, seg));
+            LET_TRY(cstone_hip_gather(ctx_, e, scratchIdx_.as<uint32_t>(), size_t(mine), nodeValues, seg));
         }
         LET_TRY(commCall(comm_.all_gather(comm_.user, seg, all, size_t(longest) * e), "all_gather (global leaf centres)"));
         for (int r = 0; r < P_; ++r)
@@ -1314,7 +1386,7 @@ private:
         // the global tree: leaf quantities to node order, upsweep (the linked octree of the global tree is findPeers')
         LET_TRY(cstone_hip_memset(ctx_, nodeCen, 0, size_t(GM) * e));
         LET_TRY(cstone_hip_scatter(ctx_, e, gLti_.as<uint32_t>() + GI, size_t(GL), leafCen, nodeCen));
-        LET_TRY(cstone_hip_upsweep_centers(ctx_, rb, maxLevel, gLevelHost_, gChild_.as<int32_t>(), nodeCen));
+        LET_TRY(upsweepGlobal(nodeCen));
         // extractGlobal: the leaves outside my range and the peers' ranges, run by run
         int32_t cur = 0;
         auto extractRun = [&](int32_t a, int32_t b) -> int
@@ -1324,7 +1396,7 @@ private:
             LET_TRY(cstone_hip_locate_nodes(ctx_, kb, leaves_.as<K>() + a, size_t(b - a) + 1, gPrefixes_.p,
                                             gLevelRange_.as<int32_t>(), scratchIdx_.as<int32_t>()));
             return cstone_hip_gather_scatter(ctx_, e, scratchIdx_.as<uint32_t>(), lti_.as<uint32_t>() + I + a, size_t(b - a),
-                                             nodeCen, centers_.p);
+                                             nodeCen, nodeValues);
         };
         for (const LetRange& r : assignment_)
         {
@@ -1533,6 +1605,9 @@ private:
     LetBuf opsAll_, ops_, scratchKeys_, scratchKeys2_, scratchIdx_, scratchIdx2_, scratchU64_;
     LetBuf gPrefixes_, gChild_, gParents_, gLevelRange_, gItl_, gLti_; // linked octree of the global tree (peer search)
     LetBuf gSeg_, gCenters_;                  // global centre exchange: my segment + everybody's, leaf and node centres
+    int gCentersLeaves_ = -1;                 // global leaves of the last global centre exchange (gCenters_ is laid out for)
+    LetBuf multipoles_, gMultipoles_;         // updateMultipoles: T[numNodes()][8], and the global exchange's store
+    bool haveMultipoles_ = false;
     int32_t levelHost_[maxLevel + 2]  = {0};  // level ranges of the focus tree / the global tree on the host (upsweeps)
     int32_t gLevelHost_[maxLevel + 2] = {0};
 

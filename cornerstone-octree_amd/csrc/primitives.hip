@@ -322,6 +322,7 @@ int permute(cstone_hip_ctx* ctx, int elemBytes, const uint32_t* map, size_t n, c
         case 16: launchPermute<GATHER, 16>(ctx, map, n, src, dst); break;
         case 24: launchPermute<GATHER, 24>(ctx, map, n, src, dst); break;
         case 32: launchPermute<GATHER, 32>(ctx, map, n, src, dst); break;
+        case 64: launchPermute<GATHER, 64>(ctx, map, n, src, dst); break; // a multipole of 8 doubles
         default: return fail(ctx, CSTONE_E_ARG, "gather/scatter: element size %d unsupported", elemBytes);
     }
     CS_HIP(ctx, hipGetLastError());
@@ -618,6 +619,7 @@ int cstone_hip_gather_scatter(cstone_hip_ctx* ctx, int elem_bytes, const uint32_
         CSTONE_GS_CASE(16);
         CSTONE_GS_CASE(24);
         CSTONE_GS_CASE(32);
+        CSTONE_GS_CASE(64);
         default: return fail(ctx, CSTONE_E_ARG, "gather_scatter: element size %d unsupported", elem_bytes);
     }
 #undef CSTONE_GS_CASE

@@ -59,6 +59,9 @@ EXPORTS = [
     "cstone_hip_domain_mr_set_sort_mode", "cstone_hip_find_neighbors_interleaved",
     # Barnes-Hut gravity (csrc/gravity.hip)
     "cstone_hip_upsweep_multipoles", "cstone_hip_compute_gravity", "cstone_hip_domain_compute_gravity",
+    # ... on a locally essential tree and on several ranks (csrc/let.hpp, FocusLet::updateMultipoles)
+    "cstone_hip_upsweep_multipoles_nodes", "cstone_hip_compute_gravity_let", "cstone_hip_domain_mr_compute_gravity",
+    "cstone_hip_domain_mr_multipoles_get",
 ]
 
 GRAVITY_GROUP_TOL = 2.0  # CSTONE_GRAVITY_GROUP_TOL: tol_factor of the target groups of cstone_hip_domain_compute_gravity
@@ -586,6 +589,28 @@ class Context:
             C.c_int(order), C.c_double(G), C.c_double(eps2), _ptr(ax), _ptr(ay), _ptr(az), _ptr(phi), _ptr(p2p),
             _ptr(m2p)), "compute_gravity")
         return ax, ay, az, phi, p2p, m2p
+
+    def compute_gravity_let(self, x, y, z, m, first, last, groups, box, child_offsets, internal_to_leaf, layout,
+                            expansion_centers, multipoles, order=2, G=1.0, eps2=0.0, potential=True, counts=False):
+        """compute_gravity on a locally essential tree (cstone_hip_compute_gravity_let): an opened leaf WITHOUT particles
+        is applied as a multipole.  Returns (ax, ay, az, phi, p2p_counts, m2p_counts, let_m2p_counts), the last one the
+        number of such leaves per target (they are counted in m2p_counts too)"""
+        torch = _torch()
+        nt = last - first
+
+        def out(dt):
+            return torch.zeros(nt, dtype=dt, device=x.device)
+
+        ax, ay, az = out(x.dtype), out(x.dtype), out(x.dtype)
+        phi = out(x.dtype) if potential else None
+        p2p, m2p, let = (out(torch.int32), out(torch.int32), out(torch.int32)) if counts else (None, None, None)
+        self._chk(self.lib.cstone_hip_compute_gravity_let(
+            self.h, C.c_int(x.element_size() * 8), C.c_int(m.element_size() * 8), _ptr(x), _ptr(y), _ptr(z), _ptr(m),
+            C.c_uint32(first), C.c_uint32(last), _ptr(groups), C.c_uint32(groups.numel() - 1), C.byref(box),
+            _ptr(child_offsets), _ptr(internal_to_leaf), _ptr(layout), _ptr(expansion_centers), _ptr(multipoles),
+            C.c_int(order), C.c_double(G), C.c_double(eps2), _ptr(ax), _ptr(ay), _ptr(az), _ptr(phi), _ptr(p2p),
+            _ptr(m2p), _ptr(let)), "compute_gravity_let")
+        return ax, ay, az, phi, p2p, m2p, let
 
 
 _DEFAULT = None

@@ -308,6 +308,41 @@ class NativeDistributedDomain:
             raise err
         self.ctx._chk(rc, "domain_mr_exchange_halos")
 
+    def gravity(self, x, y, z, m, G=1.0, eps=0.0, order=2, potential=True, exchange_masses=True):
+        """Barnes-Hut gravity on several ranks (cstone_hip_domain_mr_compute_gravity): (ax, ay, az, phi) laid out like the
+        result arrays of the last sync_grav, their assigned range [start, end) filled (phi None unless potential).
+        x, y, z, m: laid out like those arrays and read on the halo ranges too.  The sync fills the halo ranges of the
+        coordinates but not those of the masses, so the masses' halos are exchanged first (in place) unless
+        exchange_masses is False, in which case the caller has done that.  Collective"""
+        torch = _torch()
+        if exchange_masses:
+            self.exchange_halos(m)
+        ax, ay, az = [torch.zeros_like(x) for _ in range(3)]
+        phi = torch.zeros_like(x) if potential else None
+        rc = self.ctx.lib.cstone_hip_domain_mr_compute_gravity(
+            self.h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(z.data_ptr()),
+            C.c_void_p(m.data_ptr()), C.c_int(m.element_size() * 8), C.c_int(order), C.c_double(G),
+            C.c_double(eps * eps), C.c_void_p(ax.data_ptr()), C.c_void_p(ay.data_ptr()), C.c_void_p(az.data_ptr()),
+            C.c_void_p(phi.data_ptr() if phi is not None else 0))
+        if rc != 0 and self.coll.error is not None:
+            err, self.coll.error = self.coll.error, None
+            raise err
+        self.ctx._chk(rc, "domain_mr_compute_gravity")
+        return ax, ay, az, phi
+
+    def multipoles(self):
+        """(num_nodes, 8) multipoles of the focus tree as the last gravity() built them (a tensor that aliases the
+        domain's array), or None"""
+        torch = _torch()
+        ptr, nn = C.c_void_p(), C.c_int32(0)
+        self.ctx._chk(self.ctx.lib.cstone_hip_domain_mr_multipoles_get(self.h, C.byref(ptr), C.byref(nn)),
+                      "domain_mr_multipoles_get")
+        if not ptr.value:
+            return None
+        rdt = torch.float64 if self.rb == 64 else torch.float32
+        return torch.as_tensor(_DevMem(ptr.value, nn.value * 8 * self.rb // 8), device=self.ctx.device).view(rdt).view(
+            nn.value, 8)
+
     def octree(self):
         """Domain::octreeProperties() + layout(): the tree over all local particles (halos included) of the last sync as
         tensors that alias the domain's arrays; the dict is what Context.find_neighbors takes as `octree`"""

@@ -801,6 +801,29 @@ public:
         Context::check(cstone_hip_domain_mr_octree_get(dom_, &o), "MultiRankDomain::expansionCenters");
         return static_cast<const T*>(o.expansion_centers);
     }
+    /*! Barnes-Hut gravity on several ranks (cstone_hip_domain_mr_compute_gravity): accelerations and, if phi is not
+     *  null, potentials of the assigned particles, written to [startIndex(), endIndex()) of arrays laid out like the
+     *  result arrays (nParticlesWithHalos() elements).  x, y, z, m are laid out the same way and read on the halo ranges
+     *  too; the sync does not fill the halo ranges of the masses, so they are exchanged here first (in place) unless
+     *  exchangeMasses is false.  eps: Plummer softening length; order 0: monopoles, 2: + quadrupoles.  Collective. */
+    template<class Tm>
+    void computeGravity(const T* x, const T* y, const T* z, Tm* m, T* ax, T* ay, T* az, T* phi, T G, T eps, int order = 2,
+                        bool exchangeMasses = true)
+    {
+        static_assert(std::is_same_v<Tm, float> || std::is_same_v<Tm, double>);
+        if (exchangeMasses) exchangeHalos(m);
+        Context::check(cstone_hip_domain_mr_compute_gravity(dom_, x, y, z, m, int(sizeof(Tm)) * 8, order, double(G),
+                                                            double(eps) * double(eps), ax, ay, az, phi),
+                       "MultiRankDomain::computeGravity");
+    }
+    //! the multipoles of the focus tree that the last computeGravity built: 8 values of T per node (device), or null
+    const T* multipoles() const
+    {
+        const void* p = nullptr;
+        std::int32_t n = 0;
+        Context::check(cstone_hip_domain_mr_multipoles_get(dom_, &p, &n), "MultiRankDomain::multipoles");
+        return static_cast<const T*>(p);
+    }
     template<class V>
     V* property(int i) const
     {
@@ -1100,14 +1123,26 @@ public:
     /*! Barnes-Hut gravity on the focus tree (cstone_hip_domain_compute_gravity): accelerations and, if phi is not null,
      *  potentials of the endIndex() particles (the vectors are resized to that), from the expansion centres of
      *  updateExpansionCenters after the last sync; x, y, z, m laid out like the result arrays of that sync.  eps: Plummer
-     *  softening length; order 0: monopoles, 2: monopoles + quadrupoles.  Open boundaries, one rank. */
+     *  softening length; order 0: monopoles, 2: monopoles + quadrupoles.  Open boundaries.  On several ranks the
+     *  vectors hold nParticlesWithHalos() elements, [startIndex(), endIndex()) is written and the halo ranges of m are
+     *  exchanged first (MultiRankDomain::computeGravity). */
     template<class Tm>
     void computeGravity(const DeviceVector<T>& x, const DeviceVector<T>& y, const DeviceVector<T>& z,
                         const DeviceVector<Tm>& m, DeviceVector<T>& ax, DeviceVector<T>& ay, DeviceVector<T>& az,
                         DeviceVector<T>* phi, T G, T eps, int order = 2)
     {
         static_assert(std::is_same_v<Tm, float> || std::is_same_v<Tm, double>);
-        if (mr_) throw std::runtime_error("computeGravity: one rank only");
+        if (mr_)
+        {
+            const std::size_t nh = mr_->nParticlesWithHalos();
+            ax.resize(nh);
+            ay.resize(nh);
+            az.resize(nh);
+            if (phi) phi->resize(nh);
+            mr_->computeGravity(x.data(), y.data(), z.data(), const_cast<Tm*>(m.data()), ax.data(), ay.data(), az.data(),
+                                phi ? phi->data() : nullptr, G, eps, order);
+            return;
+        }
         const std::size_t ne = endIndex();
         ax.resize(ne);
         ay.resize(ne);

@@ -879,8 +879,38 @@ extern "C"
      *                 periodic axis).  x, y, z, m: laid out like the last sync's results (what update_expansion_centers
      *                 takes); the target groups (compute_group_splits, group size 64, tol_factor
      *                 CSTONE_GRAVITY_GROUP_TOL) are computed once per sync, the multipoles on every call; end_index values
-     *                 are written to ax, ay, az and phi (nullable).  One rank only: the multipoles of a multi-rank focus
-     *                 tree would need the exchange of FocusLet::updateGrav.
+     *                 are written to ax, ay, az and phi (nullable).  One rank only; several ranks:
+     *                 cstone_hip_domain_mr_compute_gravity below.
+     * upsweep_multipoles_nodes : the internal-node part of upsweep_multipoles alone, for multipoles whose leaf entries
+     *                 are filled already (the leaves of a locally essential tree that other ranks own).
+     * compute_gravity_let : compute_gravity for a locally essential tree, with ONE more rule: a node that is to be
+     *                 opened, has no children and has an EMPTY particle range (layout[leaf] == layout[leaf + 1]) is
+     *                 applied as a multipole instead (M2P) and counted in m2p_counts and in the optional per-target
+     *                 let_m2p_counts (u32, indexed and overwritten like the other counts).  Such a leaf belongs to
+     *                 another rank: syncGrav fetched no particles for it because every focus CELL passes the MAC
+     *                 against it, and every target lies in a focus cell, so the multipole is within the MAC's error
+     *                 bound for each target; the walk asks to open it only because it tests the MAC against the box
+     *                 of 64 consecutive targets, which reaches outside a non-convex focus.  compute_gravity would drop
+     *                 that leaf's mass.  On a tree without such a leaf both calls give the same bits.
+     * domain_mr_compute_gravity : gravity on several ranks -- the multipoles of the WHOLE locally essential tree about
+     *                 its current expansion centres (this rank's leaves from its assigned particles, upsweep, the
+     *                 global exchange and the peer exchange along the routes the centres took, upsweep; csrc/let.hpp,
+     *                 FocusLet::updateMultipoles), then compute_gravity_let for the assigned particles.  COLLECTIVE:
+     *                 every rank calls it.  x, y, z, m: laid out like the result arrays of the last sync
+     *                 (num_particles_with_halos elements) and read ON THE HALO RANGES TOO.  The sync fills the halo
+     *                 ranges of x, y, z but NOT those of the masses (view.props), so the call sequence is
+     *                 _sync_grav -> _exchange_halos(m) -> _compute_gravity, as with the reference's Domain.  The
+     *                 multipoles are valid for the expansion centres of the last _sync_grav or
+     *                 _update_expansion_centers and are recomputed on every call.  ax, ay, az, phi (nullable): laid out
+     *                 like the result arrays, only [start_index, end_index) is written.  The target groups
+     *                 (compute_group_splits over the assigned range, 64, CSTONE_GRAVITY_GROUP_TOL) are computed once
+     *                 per sync.  CSTONE_E_ARG, decided before any collective and therefore on every rank alike: no
+     *                 expansion centres for the current tree, a periodic axis, halo mode CSTONE_MR_HALOS_OWNER_SIDE,
+     *                 a bad argument.
+     * domain_mr_multipoles_get : device pointer to the T[num_nodes][8] multipoles of the focus tree that the last
+     *                 domain_mr_compute_gravity built (NULL before the first), and the number of nodes; the tree itself
+     *                 and its expansion centres come from cstone_hip_domain_mr_octree_get (which, in halo mode
+     *                 CSTONE_MR_HALOS_LET, describes the focus tree).  Valid until the next sync.
      * ------------------------------------------------------------------------------------------- */
 #define CSTONE_GRAVITY_GROUP_TOL 2.0f
     int cstone_hip_upsweep_multipoles(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
@@ -897,6 +927,20 @@ extern "C"
     int cstone_hip_domain_compute_gravity(cstone_hip_domain* dom, const void* x, const void* y, const void* z,
                                           const void* m, int mass_bits, int order, double G, double eps2, void* ax,
                                           void* ay, void* az, void* phi);
+    int cstone_hip_upsweep_multipoles_nodes(cstone_hip_ctx* ctx, int real_bits, int num_levels,
+                                            const int32_t* level_range_host, const int32_t* child_offsets,
+                                            int num_nodes, const void* expansion_centers, void* multipoles);
+    int cstone_hip_compute_gravity_let(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
+                                       const void* z, const void* m, uint32_t first, uint32_t last,
+                                       const uint32_t* groups, uint32_t num_groups, const cstone_box* box_host,
+                                       const int32_t* child_offsets, const int32_t* internal_to_leaf,
+                                       const uint32_t* layout, const void* expansion_centers, const void* multipoles,
+                                       int order, double G, double eps2, void* ax, void* ay, void* az, void* phi,
+                                       uint32_t* p2p_counts, uint32_t* m2p_counts, uint32_t* let_m2p_counts);
+    int cstone_hip_domain_mr_compute_gravity(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z,
+                                             const void* m, int mass_bits, int order, double G, double eps2, void* ax,
+                                             void* ay, void* az, void* phi);
+    int cstone_hip_domain_mr_multipoles_get(cstone_hip_domain_mr* dom, const void** multipoles, int32_t* num_nodes);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,13 @@ FLOP per interaction, as the kernel writes them (-ffp-contract=off: no FMA; sqrt
   P2P  21: d 3, r^2 + eps^2 6, sqrt 1, 1/r 1, m/r 1, m/r^3 2, a 6, phi 1
   M2P  54: d 3, r^2 + eps^2 6, sqrt 1, 1/r 1, 1/r^2 1, M/r^3 2, Q d 15, d.Q.d 5, 1/r^5 2, the d coefficient 4, a 9, phi 5
 
-    python tools/gravity_bench.py [--sizes 1e6 1e7] [--clouds plummer uniform] [--reals 64 32] [--reps 5]
+With --mr the same cloud also goes through the multi-rank route on a world of one rank (NativeDistributedDomain over
+gloo: sync_grav, then cstone_hip_domain_mr_compute_gravity): mr_multipoles_ms is the multipole update of the locally
+essential tree (with its exchanges, which a single rank skips) and mr_walk_ms the LET walk, both from the library's
+stage timers, mr_call_ms the whole call between device events.  The single-rank figures of the same process stand
+beside them in the same line.
+
+    python tools/gravity_bench.py [--sizes 1e6 1e7] [--clouds plummer uniform] [--reals 64 32] [--reps 5] [--mr]
 """
 import argparse
 import json
@@ -30,6 +36,7 @@ def main():
     p.add_argument("--theta", type=float, default=0.5)
     p.add_argument("--reps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--mr", action="store_true", help="also time the multi-rank route on a world of one rank")
     a = p.parse_args()
 
     import numpy as np
@@ -40,6 +47,14 @@ def main():
     from cstone_amd.domain import Domain
 
     ctx = cstone_amd.Context(0)
+    if a.mr:
+        import torch.distributed as dist
+
+        from cstone_amd.distributed import NativeDistributedDomain
+
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", "29830")
+        dist.init_process_group("gloo", rank=0, world_size=1)
     for n in [int(s) for s in a.sizes]:
         for cloud in a.clouds:
             for rb in a.reals:
@@ -90,8 +105,26 @@ def main():
                 p2p_mean, m2p_mean = p2p.double().mean().item(), m2p.double().mean().item()
                 inter = (p2p_mean + m2p_mean) * ne
                 flop = (p2p_mean * P2P_FLOP + m2p_mean * M2P_FLOP) * ne
+                mr = {}
+                if a.mr:
+                    x0, y0, z0, h0, _ = make_cloud(cloud, n, n, "cuda", dt, 7)
+                    m0 = torch.full((n,), 1.0 / n, dtype=dt, device="cuda")
+                    mdom = NativeDistributedDomain(ctx, cstone_amd.HILBERT, 64, rb, 4096, 64, lim, theta=a.theta)
+                    r = mdom.sync_grav(x0, y0, z0, h0, m0)
+                    call = lambda: mdom.gravity(r["x"], r["y"], r["z"], r["m"], exchange_masses=False)  # noqa: E731
+                    call_ms, _ = timed(call)
+                    ctx.profile_enable(True)
+                    ctx.profile_reset()
+                    for _ in range(a.reps):
+                        call()
+                    ctx.sync()
+                    (mp_ms, mp_cnt), (wk_ms, wk_cnt) = ctx.profile_get("multipoles"), ctx.profile_get("gravity")
+                    ctx.profile_enable(False)
+                    mr = dict(mr_leaves=int(mdom.view().num_focus_leaves), mr_call_ms=round(call_ms, 3),
+                              mr_multipoles_ms=round(mp_ms / a.reps, 4), mr_walk_ms=round(wk_ms / max(wk_cnt, 1), 3))
+                    del mdom, r, x0, y0, z0, h0, m0
                 print(json.dumps(dict(
-                    n=n, cloud=cloud, real_bits=rb, theta=a.theta, leaves=L, groups=int(groups.numel() - 1),
+                    n=n, cloud=cloud, real_bits=rb, theta=a.theta, leaves=L, groups=int(groups.numel() - 1), **mr,
                     upsweep_ms=round(up_ms, 4), walk_ms=round(walk_ms, 3), walk_ms_min=round(walk_min, 3),
                     p2p_per_target=round(p2p_mean, 1), m2p_per_target=round(m2p_mean, 1),
                     interactions_per_s=float(f"{inter / (walk_ms * 1e-3):.4g}"),
