@@ -387,6 +387,7 @@ extern "C"
 int cstone_hip_upload(cstone_hip_ctx* ctx, void* dst, const void* src, size_t bytes)
 {
     if (!ctx) return CSTONE_E_ARG;
+    if (bytes && (!dst || !src)) return fail(ctx, CSTONE_E_ARG, "upload: bad argument");
     if (bytes == 0) return CSTONE_OK;
     constexpr size_t stageBytes = size_t(1) << 20;
     if (!ctx->uploadStage)

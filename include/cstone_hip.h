@@ -447,10 +447,17 @@ extern "C"
      * partition_keys : with scan = exclusive scan of flags: keys with flag 1 go to set_out[scan[i]], the others to
      *                 unset_out[i - scan[i]] (either output may be NULL): pruneTreelets / the rejected keys (:118-171)
      * zero_ops_at_keys : node_ops[findNodeAbove(leaves, num_keys_in_leaves, keys[i])] = 0 (exchangeRejectedKeys, :186-190);
-     *                 leaves has num_leaves + 1 keys, all of them are searched
+     *                 leaves has num_leaves + 1 keys, all of them are searched, node_ops has num_leaves + 1 entries.  A key
+     *                 strictly inside a leaf zeroes the entry of the NEXT boundary.  The keys are rejected treelet keys of
+     *                 this rank's own range, so keys[i] <= leaves[num_leaves]; a larger key has no boundary above it and
+     *                 is ignored (the reference would write behind nodeOps)
      * locate_nodes  : idx[i] = locateNode(keys[i], keys[i+1], prefixes, level_range) for i < num_keys - 1
      *                 (indexTreelets, :266-287; R/tree/octree.hpp:216-241): the node with exactly that key range, or
-     *                 num_nodes if there is none
+     *                 num_nodes if there is none.  Like the reference, the range enters only through p = the number of
+     *                 leading zero bits of keys[i+1] - keys[i] - 1 (behind the unused bits): the node looked up is the one
+     *                 of level p / 3 whose prefix is the first p bits of keys[i] -- so a range of 5..8 smallest cells finds
+     *                 the level maxLevel - 1 node that holds keys[i], and a range whose p is no multiple of three finds
+     *                 nothing.  keys[i+1] <= keys[i] (the reference's arithmetic is undefined there) gives num_nodes
      * node_layout   : computeNodeLayout (R/domain/layout.hpp:150-165): layout[num_leaves + 1] = exclusive scan of
      *                 (first <= i < last || flags[i]) ? counts[i] : 0
      * halo_requests : extractMarkedElements for every peer at once (R/domain/layout.hpp:104-139, as called by
@@ -462,7 +469,9 @@ extern "C"
      *                 R/halos/halos.hpp:59-95).  pairs_out needs room for 2 * (flagged leaves) keys
      * ranges_from_keys : the serving side of exchangeRequestKeys (:98-108): range r = [layout[findNodeAbove(leaves,
      *                 pairs[2r])], layout[findNodeAbove(leaves, pairs[2r+1])]) -> range_offsets[r] = its start,
-     *                 range_scan[num_pairs + 1] = exclusive scan of the lengths (what gather_ranges takes)
+     *                 range_scan[num_pairs + 1] = exclusive scan of the lengths (what gather_ranges takes); all
+     *                 num_leaves + 1 keys of leaves are searched, a key that is no leaf key rounds up to the next one;
+     *                 pairs[2r] <= pairs[2r+1] <= leaves[num_leaves]; range_scan[0] = 0 is written for num_pairs = 0 too
      * ------------------------------------------------------------------------------------------- */
     int cstone_hip_raise(cstone_hip_ctx* ctx, int code, const char* message);
     /* upload : a SMALL host array to the device without synchronising the stream: the bytes are copied to a pinned

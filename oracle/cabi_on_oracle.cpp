@@ -639,7 +639,11 @@ int cstone_hip_zero_ops_at_keys(cstone_hip_ctx*, int key_bits, const void* leave
                        using K = decltype(k);
                        auto* l = (const K*)leaves;
                        for (size_t i = 0; i < num_keys; ++i)
-                           node_ops[std::lower_bound(l, l + num_leaves + 1, ((const K*)keys)[i]) - l] = 0;
+                       {
+                           // (a key above leaves[num_leaves] has no node above it: ignored, as on the device)
+                           auto at = std::lower_bound(l, l + num_leaves + 1, ((const K*)keys)[i]) - l;
+                           if (at < num_leaves + 1) node_ops[at] = 0;
+                       }
                    });
 }
 int cstone_hip_locate_nodes(cstone_hip_ctx*, int key_bits, const void* keys, size_t num_keys, const void* prefixes,
@@ -651,7 +655,9 @@ int cstone_hip_locate_nodes(cstone_hip_ctx*, int key_bits, const void* keys, siz
                        using K = decltype(k);
                        auto* q = (const K*)keys;
                        for (size_t i = 0; i + 1 < num_keys; ++i)
-                           idx[i] = locateNode<K>(q[i], q[i + 1], (const K*)prefixes, level_range);
+                           // (an empty or reversed range is no node; the reference's arithmetic is undefined for it)
+                           idx[i] = q[i + 1] > q[i] ? locateNode<K>(q[i], q[i + 1], (const K*)prefixes, level_range)
+                                                    : level_range[maxLevel<K>() + 1];
                    });
 }
 int cstone_hip_node_layout(cstone_hip_ctx*, const uint32_t* counts, const int32_t* flags, int first, int last,
