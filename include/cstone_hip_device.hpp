@@ -276,8 +276,9 @@ __device__ __forceinline__ uint32_t traverseNeighbors(bool valid, uint32_t i, co
                 --top;
                 node = uniform(sNode[top]);
                 mask = sMask[top];
-                mask = (uint64_t(__builtin_amdgcn_readfirstlane(uint32_t(mask >> 32))) << 32) |
-                       __builtin_amdgcn_readfirstlane(uint32_t(mask));
+                // readfirstlane returns int: without the casts a set bit 31 would sign-extend into lanes 32..63
+                mask = (uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(mask >> 32)))) << 32) |
+                       uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(mask))));
             } while (node != 0);
         }
     }
