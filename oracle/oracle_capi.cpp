@@ -287,7 +287,9 @@ int cstone_oracle_find_neighbors(int real_bits, const void* x, const void* y, co
 }
 
 /* ---- independent (brute-force) checkers for the owner-side halo discovery building blocks of the HIP library
- *      (cstone_hip_halo_boxes / cstone_hip_find_overlaps); they restate R/traversal/boxoverlap.hpp:42-182 only ---- */
+ *      (cstone_hip_halo_boxes / cstone_hip_find_overlaps); they restate R/traversal/boxoverlap.hpp:42-182 only.
+ *      find_overlaps keeps the rank bit of the C ABI (flags[l] |= 1 << (record[7] & 31)), so the CPU backend of
+ *      tests/py_domain.py and the kernels share one contract ---- */
 int cstone_oracle_halo_boxes(int curve, int key_bits, int real_bits, const void* leaves, const float* radii,
                              const double* lim, const int* bc, int first, int last, int* boxes)
 {
@@ -329,13 +331,19 @@ int cstone_oracle_find_overlaps(int curve, int key_bits, const void* leaves, con
                        {
                            unsigned level = levelOfSpan<K>(lv[l + 1] - lv[l]);
                            IBox nb        = nodeIBox<K>(Curve(curve), lv[l], level);
-                           for (int j = 0; j < num_boxes && !flags[l]; ++j)
+                           // the contract of cstone_hip_find_overlaps: every record ORs the bit of its exporting rank,
+                           // 1 << (record[7] & 31); record[7] = 0 (what halo_boxes writes) gives plain 0/1 flags
+                           unsigned word = unsigned(flags[l]);
+                           for (int j = 0; j < num_boxes; ++j)
                            {
                                const int* rec = boxes + size_t(j) * 8;
                                if (!rec[6]) continue;
+                               unsigned mark = 1u << (unsigned(rec[7]) & 31u);
+                               if (word & mark) continue;
                                IBox tb{{rec[0], rec[2], rec[4]}, {rec[1], rec[3], rec[5]}};
-                               if (boxesOverlap<K>(nb, tb)) flags[l] = 1;
+                               if (boxesOverlap<K>(nb, tb)) word |= mark;
                            }
+                           flags[l] = int(word);
                        }
                    });
 }
