@@ -156,483 +156,40 @@ public:
     int sync(void** keysPP, void** xPP, void** yPP, void** zPP, void** hPP, size_t n, void** scratchAll, int numScratch,
              void** props, const int* propBytes, int numProps) override
     {
-        void** scratchPP = scratchAll; // the first scratch buffer: the one the single-scratch rotation works with
         if (n == 0) return fail(ctx_, CSTONE_E_ARG, "domain_sync: no particles");
         if (!firstCall_ && n != bufSize_)
             return fail(ctx_, CSTONE_E_ARG, "Domain sync: input array sizes are inconsistent (%zu != %u)", n, bufSize_);
-        K* keys = static_cast<K*>(*keysPP);
-        const int kb = 8 * sizeof(K), rb = 8 * sizeof(T);
-        // the level ranges of the linked octree the last sync (re)built travelled to a pinned block behind its last
-        // kernels; that sync ended with a synchronisation of the stream, so they are here now
-        if (levelsPending_)
-        {
-            CS_HIP(ctx_, hipStreamSynchronize(ctx_->stream)); // (idle unless the last sync failed half way)
-            levelRangeHost_.assign(pinnedLevels_, pinnedLevels_ + maxLevel<K>() + 2);
-            int deepest = 0;
-            for (int l = 0; l <= int(maxLevel<K>()); ++l)
-                if (levelRangeHost_[l + 1] > levelRangeHost_[l]) deepest = l;
-            if (deepest > deepestBound_)
-                return fail(ctx_, CSTONE_E_INTERNAL, "domain_sync: the focus tree has level %d, the bound was %d", deepest,
-                            deepestBound_);
-            deepestBound_  = deepest;
-            levelsPending_ = false;
-        }
-
+        SyncState s{xPP, yPP, zPP, hPP, static_cast<K*>(*keysPP), n, scratchAll, numScratch, props, propBytes, numProps};
+        CS_TRY(takeLevelRanges());
         // ---- GlobalAssignment::assign (assignment.hpp:57-103): box, keys, sort, one global-tree step
-        // The box of a sync follows from the extents of x, y, z (makeGlobalBox + limitBoxShrinking).  After the first call
-        // it rarely changes, so the keys are computed SPECULATIVELY with the box of the previous sync while the same
-        // pass over x, y, z measures the extents; the box rule is evaluated afterwards and only a box that really
-        // changed costs a second encode + sort.  Saves the separate 2.4 GB pass over the coordinates per sync at 1e8.
-        auto boxFromExtents = [&](const double* lim, cstone_box& box)
-        {
-            if (firstCall_) { std::copy(lim, lim + 6, box.lim); }
-            else
-            {
-                // limitBoxShrinking (sfc/box.hpp:415-431), evaluated in T like the reference
-                const T shrink = T(0.05);
-                for (int d = 0; d < 3; ++d)
-                {
-                    T lo = T(box.lim[2 * d]), hi = T(box.lim[2 * d + 1]);
-                    T len = hi - lo;
-                    T a = lo + shrink * len, b = hi - shrink * len;
-                    box.lim[2 * d]     = std::min(T(lim[2 * d]), a);
-                    box.lim[2 * d + 1] = std::max(T(lim[2 * d + 1]), b);
-                }
-            }
-        };
-        const bool anyOpen = box_.bc[0] != 1 || box_.bc[1] != 1 || box_.bc[2] != 1;
-        // (adaptive: a sync whose speculation failed -- the outermost particles of an open box move -- makes the following
-        //  syncs measure first, until one of them finds the box unchanged again)
-        bool speculate     = anyOpen && !firstCall_ && !measureFirst_ && maySpeculate();
-        bool boxMoved      = false; // measured first and found a new box: every key changes, nothing to re-sort from
-        if (anyOpen && !speculate)
-        {
-            const cstone_box before = box_;
-            double lim[6];
-            // extents of the open dimensions in one launch and one read-back (MinMaxGpu x3 in the reference)
-            const void* open[3];
-            int dims[3], numOpen = 0;
-            void* coords[3] = {*xPP, *yPP, *zPP};
-            for (int d = 0; d < 3; ++d)
-            {
-                if (box_.bc[d] == 1) { lim[2 * d] = box_.lim[2 * d], lim[2 * d + 1] = box_.lim[2 * d + 1]; }
-                else { open[numOpen] = coords[d], dims[numOpen++] = d; }
-            }
-            double ext[6];
-            CS_TRY(minMaxCoordinates(ctx_, rb, open, numOpen, n, ext));
-            for (int i = 0; i < numOpen; ++i)
-                lim[2 * dims[i]] = ext[2 * i], lim[2 * dims[i] + 1] = ext[2 * i + 1];
-            boxFromExtents(lim, box_);
-            for (int k = 0; k < 6; ++k)
-                boxMoved = boxMoved || box_.lim[k] != before.lim[k];
-            if (!firstCall_) measureFirst_ = boxMoved;
-        }
-        // computeSfcKeys + setMapFromCodes (assignment.hpp:81-86) in one call: the sort's digits are counted while the keys
-        // are still in the encode kernel's registers, its first pass produces the positions instead of reading an iota
-        CS_TRY(order_.ensure(ctx_, n * sizeof(uint32_t)));
-        CS_TRY(orderAlt_.ensure(ctx_, n * sizeof(uint32_t)));
-        CS_TRY(keysAlt_.ensure(ctx_, n * sizeof(K)));
-        size_t tb = cstone_hip_sort_pairs_temp_bytes(kb, n);
-        CS_TRY(sortTmp_.ensure(ctx_, tb));
-        // Which digits need the radix passes: two particles whose keys agree in the digits above the deepest leaf level
-        // (+1) of the previous focus tree sit in the same leaf cell, i.e. such runs hold at most a bucket of particles
-        // and are ordered by a fix-up pass instead (sort.hip, fixupRunsKernel).  If a run turns out longer (the
-        // particles have clustered since), the flag read back below triggers a regular sort of the rest.
-        int startPass = 0;
-        if (!firstCall_ && !levelRangeHost_.empty() && !allDigits())
-        {
-            int lmax = 0;
-            for (int l = 0; l <= int(maxLevel<K>()); ++l)
-                if (levelRangeHost_[l + 1] > levelRangeHost_[l]) lmax = l;
-            // one level below the deepest leaves a run holds about bucket / 8 particles; larger buckets get more margin
-            // (the fix-up handles runs of up to 192)
-            int margin  = 1 + (bucketFocus_ > 128) + (bucketFocus_ > 1024);
-            int lowBits = 3 * int(maxLevel<K>()) - 3 * (lmax + margin);
-            startPass   = std::max(0, lowBits / 8) & ~1;
-        }
-        T* extentsDev  = reinterpret_cast<T*>(ctx_->devScalars + 16);
-        T* extentsHost = reinterpret_cast<T*>(ctx_->hostScalars + 16);
-        auto encodeAndSort = [&](bool measure, bool* measured)
-        {
-            CS_TRY(sfcKeysAndOrderingHint(ctx_, curve_, kb, rb, *xPP, *yPP, *zPP, keys, order_.as<uint32_t>(), n, box_,
-                                          keysAlt_.p, orderAlt_.as<uint32_t>(), sortTmp_.p, tb, startPass,
-                                          ctx_->devScalars + 3, true, measure ? extentsDev : nullptr, measured));
-            if (startPass == 0) CS_HIP(ctx_, hipMemsetAsync(ctx_->devScalars + 3, 0, sizeof(int), ctx_->stream));
-            return CSTONE_OK;
-        };
-        // the box the extents of this sync ask for (makeGlobalBox + limitBoxShrinking); true: it differs from box_
-        auto nextBox = [&](const double* ext, cstone_box& next)
-        {
-            double lim[6];
-            for (int d = 0; d < 3; ++d)
-            {
-                const bool pbc = box_.bc[d] == 1;
-                lim[2 * d]     = pbc ? box_.lim[2 * d] : ext[2 * d];
-                lim[2 * d + 1] = pbc ? box_.lim[2 * d + 1] : ext[2 * d + 1];
-            }
-            next = box_;
-            boxFromExtents(lim, next);
-            bool changed = false;
-            for (int k = 0; k < 6; ++k)
-                changed = changed || next.lim[k] != box_.lim[k];
-            return changed;
-        };
-
-        // ---- the incremental re-sort (resort.hpp): particles that are still inside the leaf their position belonged to
-        //      at the previous sync are ordered leaf by leaf, the others are binned into their new leaves.  Same result
-        //      as the sort of all keys; a box that changed, too many movers or an overfull leaf take the regular path.
-        const int tileLeaves = LeafResort<K>::leavesPerTile(bucketFocus_);
-        bool sorted          = false;
-        uint32_t resortMarkers = 0; // particles with the remove marker, as the re-sort counted them
-        const bool tryResort = !firstCall_ && tileLeaves > 0 && layoutLeaves_ == fLeaves_ && fLeaves_ > 0 &&
-                               resortBackoff_ == 0 && !boxMoved && mayResort();
-        if (resortBackoff_ > 0) --resortBackoff_;
-        // The field-carrying leaf pass (resort.hpp, sortLeavesFields; CSTONE_FUSED_LEAF_PASS=1 and four scratch arrays): x,
-        // y, z, h move with the keys in ONE pass over the particle arrays instead of the leaf pass and the gathers of h and
-        // of x, y, z.  Measured at 1e8 particles, every particle drifting: 2.14 ms against 0.66 + 0.37 + 0.91 ms for the
-        // three passes it replaces (it saves 8 of their 92 bytes per particle, and the ordering network -- bound by
-        // instruction issue -- and the data movement do not overlap inside one wave the way separate kernels on two streams
-        // do): kept selectable, not the default.
-        const bool fusedLeafPass        = std::getenv("CSTONE_FUSED_LEAF_PASS") != nullptr; // (read per sync: tests switch it)
-        const bool carryFields          = numScratch >= 4 && fusedLeafPass;
-        bool fieldsMoved                = false; // x, y, z, h are in their new order already (and radii follow from hmax)
+        CS_TRY(measureBoxFirst(s));
+        CS_TRY(reserveSortBuffers(s));
         // The gather of x, y, z has no consumer inside a sync: with three or more scratch arrays it runs on the context's
         // second stream, next to the tree updates (chains of small, latency-bound kernels with two read-backs in between)
         // and the gather of h, and is joined before the call returns.
-        const bool noOverlap = std::getenv("CSTONE_NO_GATHER_OVERLAP") != nullptr; // tuning / tests
-        bool xyzForked = false, xyzJoined = false;
-        ctx_->auxBusy  = false; // (a sync that failed behind its fork may have left it set)
-        auto forkXyzGather = [&](size_t count) -> int
-        {
-            if (fieldsMoved || numScratch < 3 || noOverlap || xyzForked || count == 0) return CSTONE_OK;
-            CS_TRY(ensureAuxStream(ctx_));
-            CS_HIP(ctx_, hipEventRecord(ctx_->evFork, ctx_->stream));
-            CS_HIP(ctx_, hipStreamWaitEvent(ctx_->aux, ctx_->evFork, 0));
-            const void* src[3] = {*xPP, *yPP, *zPP};
-            void* dst[3]       = {scratchAll[0], scratchAll[1], scratchAll[2]};
-            int rc;
-            {
-                StreamScope scope(ctx_, ctx_->aux);
-                rc = cstone_hip_gather_multi(ctx_, sizeof(T), order_.as<uint32_t>(), count, src, dst, 3);
-            }
-            CS_TRY(rc);
-            CS_HIP(ctx_, hipEventRecord(ctx_->evJoin, ctx_->aux));
-            ctx_->auxBusy = true;
-            std::swap(*xPP, scratchAll[0]);
-            std::swap(*yPP, scratchAll[1]);
-            std::swap(*zPP, scratchAll[2]);
-            xyzForked = true;
-            return CSTONE_OK;
-        };
-        auto joinXyzGather = [&]() -> int
-        {
-            if (xyzForked && !xyzJoined) CS_HIP(ctx_, hipStreamWaitEvent(ctx_->stream, ctx_->evJoin, 0));
-            xyzJoined     = true;
-            ctx_->auxBusy = false;
-            return CSTONE_OK;
-        };
-        if (tryResort)
-        {
-            CS_TRY(resort_.prepare(ctx_, fTree_.as<K>(), layout_.as<uint32_t>(), fLeaves_, n, keysAlt_.as<K>(), true,
-                                   carryFields ? rb : 0));
-            const ResortArgs<K> ra = resort_.args();
-            bool done              = false;
-            CS_TRY(computeKeysResort(ctx_, curve_, kb, rb, *xPP, *yPP, *zPP, keys, n, box_, &ra,
-                                     speculate ? extentsDev : nullptr, &done));
-            if (done)
-            {
-                CS_TRY(resort_.binMovers(ctx_, tileLeaves));
-                // one read-back: the extents (slots 16..27) and what the re-sort found (28..31)
-                CS_TRY(copyToPinned(ctx_, ctx_->hostScalars + 16, ctx_->devScalars + 16, 16 * sizeof(int)));
-                CS_HIP(ctx_, hipStreamSynchronize(ctx_->stream));
-                bool boxChanged = false;
-                cstone_box next = box_;
-                if (speculate)
-                {
-                    double ext[6];
-                    for (int k = 0; k < 6; ++k)
-                        ext[k] = double(extentsHost[k]);
-                    boxChanged = nextBox(ext, next);
-                }
-                const uint32_t markers = uint32_t(ctx_->hostScalars[RESORT_SCALARS]);
-                resortMarkers          = markers;
-                const int flags        = ctx_->hostScalars[RESORT_SCALARS + 1];
-                const uint32_t J       = uint32_t(ctx_->hostScalars[RESORT_SCALARS + 2]);
-                const uint32_t movers  = uint32_t(ctx_->hostScalars[RESORT_SCALARS + 3]);
-                if (!boxChanged && (flags & 7) == 0 && movers <= n / 8)
-                {
-                    if (carryFields)
-                    {
-                        ResortFields rf{rb, {*xPP, *yPP, *zPP, *hPP}, {scratchAll[0], scratchAll[1], scratchAll[2], scratchAll[3]}};
-                        CS_TRY(resort_.sortLeavesFields(ctx_, keysAlt_.as<K>(), keys, order_.as<uint32_t>(), rf, movers,
-                                                        markers, J, tileLeaves));
-                        std::swap(*xPP, scratchAll[0]);
-                        std::swap(*yPP, scratchAll[1]);
-                        std::swap(*zPP, scratchAll[2]);
-                        std::swap(*hPP, scratchAll[3]);
-                        fieldsMoved = true;
-                    }
-                    else
-                    {
-                        CS_TRY(resort_.sortLeaves(ctx_, keysAlt_.as<K>(), keys, order_.as<uint32_t>(), movers, markers, J,
-                                                  tileLeaves, (flags & 8) != 0));
-                        CS_TRY(forkXyzGather(n - markers)); // (the ordering is final: x, y, z follow on the second stream)
-                    }
-                    CS_HIP(ctx_, hipMemsetAsync(ctx_->devScalars + 3, 0, sizeof(int), ctx_->stream));
-                    sorted      = true;
-                    lastMovers_ = movers;
-                    ++resorts_;
-                }
-                else
-                {
-                    // the caller's key array has not been touched: the regular path starts from scratch, with the box
-                    // this sync needs (the extents are known by now)
-                    if (boxChanged)
-                    {
-                        box_ = next;
-                        ++boxRedos_;
-                        measureFirst_ = true;
-                    }
-                    else
-                    {
-                        resortBackoff_ = 4;
-                        ++resortFallbacks_;
-                    }
-                    speculate = false;
-                }
-            }
-        }
-
-        resortedThisSync_ = sorted;
-        bool measured     = false;
-        if (!sorted) CS_TRY(encodeAndSort(speculate, &measured));
-        if (!sorted && speculate)
-        {
-            double lim[6];
-            if (measured)
-            {
-                CS_TRY(copyToPinned(ctx_, extentsHost, extentsDev, 6 * sizeof(T)));
-                CS_HIP(ctx_, hipStreamSynchronize(ctx_->stream));
-                for (int k = 0; k < 6; ++k)
-                    lim[k] = double(extentsHost[k]);
-            }
-            else
-            {
-                // unaligned arrays: the plain encode ran, measure the extents the regular way
-                const void* all[3] = {*xPP, *yPP, *zPP};
-                CS_TRY(minMaxCoordinates(ctx_, rb, all, 3, n, lim));
-            }
-            cstone_box next = box_;
-            if (nextBox(lim, next))
-            {
-                // the particles have left the box (or shrunk away from it by more than 5 %): keys and order again
-                box_ = next;
-                ++boxRedos_;
-                measureFirst_ = true;
-                // the key array is sorted by now: put every entry back to its particle first (the remove markers of the
-                // caller must meet their own particles again), then encode with the new box
-                CS_TRY(cstone_hip_scatter(ctx_, sizeof(K), order_.as<uint32_t>(), n, keys, keysAlt_.p));
-                CS_HIP(ctx_, hipMemcpyAsync(keys, keysAlt_.p, n * sizeof(K), hipMemcpyDeviceToDevice, ctx_->stream));
-                CS_TRY(encodeAndSort(false, nullptr));
-            }
-        }
-
-        if (firstCall_)
-        {
-            // spanning tree of one rank = the root; counts = bucket - 1 (assignment.hpp:48-53)
-            CS_TRY(ensureTree(gTree_, gCounts_, gCap_, 4096));
-            hipLaunchKernelGGL(initTreeKernel<K>, 1, 1, 0, ctx_->stream, gTree_.as<K>(), gCounts_.as<uint32_t>(),
-                               bucket_ - 1);
-            gLeaves_ = 1;
-        }
-        // A sync that was re-sorted knows its number of valid particles already, and the host holds the (small) global tree
-        // and its counts from the last sync: the update step of the global tree is then made on the HOST
-        // (globalTreeStepHost), the device only counts, and the counts travel back with the read-back of the focus-tree
-        // update -- one stream synchronisation and a handful of launches fewer than cstone_hip_update_octree.
-        uint32_t numAssigned = 0;
-        int converged        = 0;
-        const bool hostStep  = sorted && !firstCall_ && hostGlobalStep_ && int(gLeavesHost_.size()) == gLeaves_ + 1 &&
-                              int(gCountsHost_.size()) == gLeaves_;
-        if (hostStep)
-        {
-            numAssigned = uint32_t(n) - resortMarkers;
-            if (numAssigned == 0) return fail(ctx_, CSTONE_E_ARG, "domain_sync: all particles removed");
-            std::vector<K> fresh;
-            const bool same = globalTreeStepHost<K>(gLeavesHost_, gCountsHost_, bucket_, fresh);
-            if (!same)
-            {
-                const int leaves = int(fresh.size()) - 1;
-                CS_TRY(ensureTree(gTree_, gCounts_, gCap_, leaves + 1));
-                gLeavesHost_.swap(fresh);
-                CS_TRY(cstone_hip_upload(ctx_, gTree_.p, gLeavesHost_.data(), gLeavesHost_.size() * sizeof(K)));
-                gLeaves_ = leaves;
-            }
-            converged = same;
-            CS_TRY(cstone_hip_compute_node_counts(ctx_, kb, gTree_.p, gCounts_.as<uint32_t>(), gLeaves_, keys, n,
-                                                  0xFFFFFFFFu));
-            CS_TRY(queueGlobalReadBack(false));
-        }
-        else
-        {
-        // particles flagged with the remove marker sort behind the end of the curve and leave the domain: their number
-        // is on its way to the host while the global tree is updated (whose own read-back completes the stream)
-        hipLaunchKernelGGL(countValidKernel<K>, 1, 1, 0, ctx_->stream, keys, n, ctx_->devScalars + 2);
-        CS_TRY(copyToPinned(ctx_, ctx_->hostScalars + 2, ctx_->devScalars + 2, 2 * sizeof(int)));
-        CS_TRY(updateGlobal(keys, n, &converged));
-        if (firstCall_)
-        {
-            // `while (!updateOctreeGlobal(...));` (assignment.hpp:95-98): at least one more step, whatever the first said
-            int guard = 0;
-            do
-            {
-                CS_TRY(updateGlobal(keys, n, &converged));
-                if (++guard > 64) return fail(ctx_, CSTONE_E_INTERNAL, "global tree does not converge");
-            } while (!converged);
-        }
-        // the copy was queued ahead of the update's own read-back (update_octree synchronises for the new leaf count)
-        numAssigned = uint32_t(ctx_->hostScalars[2]);
-        if (numAssigned == 0) return fail(ctx_, CSTONE_E_ARG, "domain_sync: all particles removed");
-        if (ctx_->hostScalars[3] != 0)
-        {
-            // a run of equal high digits was too long for the fix-up: sort the rest the regular way.  (The global tree
-            // above is not affected: its leaf boundaries cannot fall inside such a run.)
-            CS_TRY(cstone_hip_sort_pairs(ctx_, kb, keys, order_.as<uint32_t>(), n, keysAlt_.p, orderAlt_.as<uint32_t>(),
-                                         sortTmp_.p, tb));
-            ++fullSortFallbacks_;
-        }
-        // (tree and counts for the host's copy: they arrive behind the next synchronisation of the stream)
-        CS_TRY(queueGlobalReadBack(true));
-        }
-        CS_TRY(forkXyzGather(numAssigned)); // (radix path: the ordering is final from here on)
-
+        s.noOverlap   = std::getenv("CSTONE_NO_GATHER_OVERLAP") != nullptr; // tuning / tests
+        ctx_->auxBusy = false; // (a sync that failed behind its fork may have left it set)
+        CS_TRY(tryResort(s));
+        resortedThisSync_ = s.sorted;
+        CS_TRY(encodeSortCheckBox(s));
+        CS_TRY(stepGlobalTree(s));
+        CS_TRY(forkXyzGather(s, s.numAssigned)); // (radix path: the ordering is final from here on)
         // ---- GlobalAssignment::distribute on one rank: nothing to exchange; the second sort (assignment.hpp:156) of an
         //      already sorted range is the identity and is skipped.
         // ---- h goes into SFC order for the halo radii (domain.hpp:213-215): gathered further down, in the pass that
         //      takes the maximum per leaf
-
-        // ---- focus tree (octree_focus_mpi.hpp:535-553 on first call, then :225-227)
-        if (firstCall_)
-        {
-            CS_TRY(ensureTree(fTree_, fLeafCounts_, fCap_, 4096));
-            hipLaunchKernelGGL(initTreeKernel<K>, 1, 1, 0, ctx_->stream, fTree_.as<K>(), fLeafCounts_.as<uint32_t>(),
-                               bucketFocus_ + 1);
-            fLeaves_ = 1;
-            CS_TRY(buildFocusOctree());
-            // counts_ of the single root node = bucketFocus + 1 (octree_focus_mpi.hpp:75)
-            CS_TRY(fCounts_.ensure(ctx_, sizeof(uint32_t)));
-            CS_HIP(ctx_, hipMemcpyAsync(fCounts_.p, fLeafCounts_.p, sizeof(uint32_t), hipMemcpyDeviceToDevice,
-                                        ctx_->stream));
-            int conv = 0, guard = 0;
-            while (!conv)
-            {
-                CS_TRY(updateFocus(keys, numAssigned, &conv));
-                if (++guard > 64) return fail(ctx_, CSTONE_E_INTERNAL, "focus tree does not converge");
-            }
-        }
-        int conv = 0;
-        CS_TRY(updateFocus(keys, numAssigned, &conv));
-        takeGlobalReadBack(); // (updateFocus has synchronised the stream: the global counts are here)
-
-        // ---- Halos::discover + computeLayout (halos.hpp:128-222) for the assignment [0, L)
-        const NodeIdx L = fLeaves_;
-        CS_TRY(layout_.ensure(ctx_, size_t(L + 1) * sizeof(uint32_t)));
-        CS_TRY(radii_.ensure(ctx_, size_t(L) * sizeof(float)));
-        CS_TRY(flags_.ensure(ctx_, size_t(L) * sizeof(int)));
-        CS_HIP(ctx_, hipMemsetAsync(layout_.p, 0, sizeof(uint32_t), ctx_->stream));
-        CS_TRY(cstone_hip_inclusive_scan_u32(ctx_, fLeafCounts_.as<uint32_t>(), layout_.as<uint32_t>() + 1, size_t(L)));
-        layoutLeaves_ = L;
-        // gatherArrays(h) + segmentMax + scale in one pass over h (every leaf is assigned on one rank: the leaves' particles
-        // are all the assigned particles)
-        static const bool splitGather = std::getenv("CSTONE_SPLIT_H_GATHER") != nullptr; // tuning: the two-pass form
-        if (fieldsMoved)
-        {
-            // h is in SFC order already; the radii follow from the maxima the leaf pass folded per OLD leaf
-            CS_TRY(resort_.radiiOfLeaves(ctx_, L, layout_.as<uint32_t>(), *hPP, rb, haloSearchExt_, radii_.as<float>()));
-        }
-        else
-        {
-            // where h goes: the first scratch array -- unless x, y, z are still on their way there on the second stream; a
-            // fourth scratch array then takes h (no waiting), with three the gather of h waits for them
-            void** hDst = scratchPP;
-            if (xyzForked && numScratch >= 4) { hDst = &scratchAll[3]; }
-            else { CS_TRY(joinXyzGather()); }
-            if (splitGather)
-            {
-                CS_TRY(cstone_hip_gather(ctx_, sizeof(T), order_.as<uint32_t>(), numAssigned, *hPP, *hDst));
-                std::swap(*hPP, *hDst);
-                CS_TRY(cstone_hip_halo_radii(ctx_, rb, *hPP, layout_.as<uint32_t>(), 0, L, L, haloSearchExt_,
-                                             radii_.as<float>()));
-            }
-            else
-            {
-                CS_TRY(gatherWithHaloRadii(ctx_, rb, *hPP, order_.as<uint32_t>(), *hDst, layout_.as<uint32_t>(), L,
-                                           haloSearchExt_, radii_.as<float>()));
-                std::swap(*hPP, *hDst);
-            }
-        }
-        CS_HIP(ctx_, hipMemsetAsync(flags_.p, 0, size_t(L) * sizeof(int), ctx_->stream));
-        CS_TRY(cstone_hip_find_halos(ctx_, curve_, kb, rb, fPrefixes_.p, fChild_.as<int32_t>(), fItl_.as<int32_t>(),
-                                     fTree_.p, radii_.as<float>(), &box_, 0, L, flags_.as<int32_t>()));
-        // one rank: every leaf is assigned, no halo leaves: layout = exclusive scan of the leaf counts (layout.hpp:150-165),
-        // which is the inclusive scan written above shifted by one.
-
-        // ---- updateLayout (domain.hpp:542-604): keys already sit at offset 0; gather the unordered arrays
-        CS_TRY(joinXyzGather()); // (the property gathers below go through the buffers x, y, z were read from)
-        if (fieldsMoved || xyzForked) {} // (x, y, z went with the leaf pass, or on the second stream)
-        else if (numScratch >= 3)
-        {
-            // three free buffers (the caller's scratch tuple, R/domain/domain.hpp:196-206 has three as well): x, y, z go
-            // to their new order in ONE pass that reads the ordering once
-            const void* src[3] = {*xPP, *yPP, *zPP};
-            void* dst[3]       = {scratchAll[0], scratchAll[1], scratchAll[2]};
-            CS_TRY(cstone_hip_gather_multi(ctx_, sizeof(T), order_.as<uint32_t>(), numAssigned, src, dst, 3));
-            std::swap(*xPP, scratchAll[0]);
-            std::swap(*yPP, scratchAll[1]);
-            std::swap(*zPP, scratchAll[2]);
-        }
-        else
-        {
-            void** arrays[3] = {xPP, yPP, zPP};
-            for (auto a : arrays)
-            {
-                CS_TRY(cstone_hip_gather(ctx_, sizeof(T), order_.as<uint32_t>(), numAssigned, *a, *scratchPP));
-                std::swap(*a, *scratchPP);
-            }
-        }
-        for (int p = 0; p < numProps; ++p)
-        {
-            if (propBytes[p] > int(sizeof(T)))
-                return fail(ctx_, CSTONE_E_ARG, "domain_sync: property %d is wider than the scratch element", p);
-            CS_TRY(cstone_hip_gather(ctx_, propBytes[p], order_.as<uint32_t>(), numAssigned, props[p], *scratchPP));
-            std::swap(props[p], *scratchPP);
-        }
-
-        startIndex_ = 0;
-        endIndex_   = numAssigned;
-        lastN_      = n;
-        haveExpansion_ = false; // (the tree and the particles' order may have changed)
-        bufSize_    = numAssigned;
-        ++syncs_;
-        firstCall_  = false;
-        // the sticky device-side error word (look-back spin bail-out of the sort, traversal stack overflow ...): a sync
-        // that tripped one of those checks must not report success (tests: CSTONE_FORCE_DEVICE_ERROR raises it)
-#ifdef CSTONE_TEST_HOOKS
-        if (std::getenv("CSTONE_FORCE_DEVICE_ERROR")) CS_HIP(ctx_, hipMemsetAsync(ctx_->devScalars + 63, 1, 1, ctx_->stream));
-#endif
-        return cstone_hip_ctx_sync(ctx_);
+        CS_TRY(updateFocusTree(s));
+        gHost_.takeReadBack(); // (updateFocus has synchronised the stream: the global counts are here)
+        CS_TRY(layoutAndHalos(s));
+        CS_TRY(gatherFields(s));
+        return finishSync(s);
     }
 
     void setHaloFactor(float factor) override { haloSearchExt_ = factor; }
     void setSortMode(int mode) override { sortMode_ = mode; }
     void setSpeculativeBox(bool on) override { speculativeBox_ = on; }
-    // what the client chose (cstone_hip_domain_set_sort_mode / _set_speculative_box); the environment variables of the
-    // experiments override it
-    bool mayResort() const
-    {
-        return sortMode_ == CSTONE_SORT_INCREMENTAL && std::getenv("CSTONE_NO_RESORT") == nullptr &&
-               std::getenv("CSTONE_FULL_SORT") == nullptr;
-    }
-    bool allDigits() const { return sortMode_ == CSTONE_SORT_ALL_DIGITS || std::getenv("CSTONE_FULL_SORT") != nullptr; }
+    // what the client chose (cstone_hip_domain_set_speculative_box); the environment variable of the experiments overrides
+    // it.  Read at every sync (the multi-rank path reads it once, in its constructor)
     bool maySpeculate() const { return speculativeBox_ && std::getenv("CSTONE_NO_SPECULATIVE_BOX") == nullptr; }
 
     int view(cstone_hip_domain_view* v) override
@@ -702,7 +259,6 @@ public:
                                             "not provided");
         if ((massBits != 32 && massBits != 64) || !x || !y || !z || !m || !ax || !ay || !az)
             return fail(ctx_, CSTONE_E_ARG, "domain_compute_gravity: bad argument");
-        const int kb = 8 * sizeof(K), rb = 8 * sizeof(T);
         const NodeIdx L = fLeaves_, I = (L - 1) / 7, M = L + I;
         if (groupsSync_ != syncs_)
         {
@@ -755,58 +311,444 @@ private:
     bool measureFirst_ = false; // the last box was not the one before it: measure the extents before encoding
     int sortMode_        = CSTONE_SORT_INCREMENTAL;
     bool speculativeBox_ = true;
-    int ensureTree(DevBuf& tree, DevBuf& counts, int& cap, int need)
+    static constexpr int kb = 8 * sizeof(K), rb = 8 * sizeof(T);
+
+    //! What the stages of one sync share: the caller's arrays (they change places with the scratch arrays as the fields
+    //! move) and what the stages before have decided.  Made by sync() on its stack.
+    struct SyncState
     {
-        if (need <= cap) return CSTONE_OK;
-        int newCap = std::max(need, int(cap * 1.5));
-        CS_TRY(tree.ensure(ctx_, size_t(newCap + 1) * sizeof(K), true));
-        CS_TRY(counts.ensure(ctx_, size_t(newCap) * sizeof(uint32_t), true));
-        cap = newCap;
+        void **xPP, **yPP, **zPP, **hPP;
+        K* keys;
+        size_t n;
+        void** scratch; // [0]: the buffer the single-scratch rotation works with
+        int numScratch;
+        void** props;
+        const int* propBytes;
+        int numProps;
+        bool speculate      = false; // the keys are computed with the box of the previous sync, the same pass measures
+        bool boxMoved       = false; // measured first and found a new box: every key changes, nothing to re-sort from
+        int startPass       = 0;     // low digit passes the radix sort leaves to the fix-up
+        size_t sortTmpBytes = 0;
+        bool sorted         = false; // the re-sort has put keys and order_ into their final order
+        uint32_t resortMarkers = 0;  // particles with the remove marker, as the re-sort counted them
+        bool fieldsMoved    = false; // x, y, z, h are in their new order already (and radii follow from hmax)
+        bool noOverlap      = false; // CSTONE_NO_GATHER_OVERLAP
+        bool xyzForked = false, xyzJoined = false; // the gather of x, y, z on the second stream
+        uint32_t numAssigned = 0;    // particles without the remove marker
+    };
+
+    T* extentsDev() const { return reinterpret_cast<T*>(ctx_->devScalars + 16); }
+    T* extentsHost() const { return reinterpret_cast<T*>(ctx_->hostScalars + 16); }
+
+    //! the level ranges of the linked octree the last sync (re)built travelled to a pinned block behind its last
+    //! kernels; that sync ended with a synchronisation of the stream, so they are here now
+    int takeLevelRanges()
+    {
+        if (!levelsPending_) return CSTONE_OK;
+        CS_HIP(ctx_, hipStreamSynchronize(ctx_->stream)); // (idle unless the last sync failed half way)
+        levelRangeHost_.assign(pinnedLevels_, pinnedLevels_ + maxLevel<K>() + 2);
+        const int deepest = deepestLevel<K>(levelRangeHost_);
+        if (deepest > deepestBound_)
+            return fail(ctx_, CSTONE_E_INTERNAL, "domain_sync: the focus tree has level %d, the bound was %d", deepest,
+                        deepestBound_);
+        deepestBound_  = deepest;
+        levelsPending_ = false;
         return CSTONE_OK;
     }
 
-    //! global counts (and, when the device made it, the leaf array) on their way to the pinned block; not waited for
-    int queueGlobalReadBack(bool withLeaves)
+    /*! The box of a sync follows from the extents of x, y, z (makeGlobalBox + limitBoxShrinking).  After the first call
+     *  it rarely changes, so the keys are computed SPECULATIVELY with the box of the previous sync while the same pass
+     *  over x, y, z measures the extents; the box rule is evaluated afterwards and only a box that really changed costs a
+     *  second encode + sort.  Saves the separate 2.4 GB pass over the coordinates per sync at 1e8.
+     *  Decides s.speculate; a sync that does not speculate measures here and sets box_, s.boxMoved and measureFirst_. */
+    int measureBoxFirst(SyncState& s)
     {
-        CS_TRY(pin_.reserve(ctx_, size_t(gLeaves_) * 4 + size_t(gLeaves_ + 1) * sizeof(K) + 256));
-        pinCounts_ = static_cast<uint32_t*>(pin_.take(size_t(gLeaves_) * 4));
-        CS_TRY(copyToPinned(ctx_, pinCounts_, gCounts_.p, size_t(gLeaves_) * 4));
-        pinLeaves_ = nullptr;
-        if (withLeaves)
+        const bool anyOpen = box_.bc[0] != 1 || box_.bc[1] != 1 || box_.bc[2] != 1;
+        // (adaptive: a sync whose speculation failed -- the outermost particles of an open box move -- makes the following
+        //  syncs measure first, until one of them finds the box unchanged again)
+        s.speculate = anyOpen && !firstCall_ && !measureFirst_ && maySpeculate();
+        if (!anyOpen || s.speculate) return CSTONE_OK;
+        // extents of the open dimensions in one launch and one read-back (MinMaxGpu x3 in the reference)
+        const void* open[3];
+        int dims[3], numOpen = 0;
+        void* coords[3] = {*s.xPP, *s.yPP, *s.zPP};
+        for (int d = 0; d < 3; ++d)
+            if (box_.bc[d] != 1) open[numOpen] = coords[d], dims[numOpen++] = d;
+        double ext[6], lim[6] = {};
+        CS_TRY(minMaxCoordinates(ctx_, rb, open, numOpen, s.n, ext));
+        for (int i = 0; i < numOpen; ++i)
+            lim[2 * dims[i]] = ext[2 * i], lim[2 * dims[i] + 1] = ext[2 * i + 1];
+        const cstone_box before = box_;
+        box_                    = limitBoxShrinking<T>(before, lim, firstCall_);
+        s.boxMoved              = !sameLimits(box_, before);
+        if (!firstCall_) measureFirst_ = s.boxMoved;
+        return CSTONE_OK;
+    }
+
+    //! buffers of the sort, and which digits need the radix passes (partialSortStartPass); a run that turns out longer
+    //! than the fix-up takes (the particles have clustered since) raises the flag stepGlobalTree reads back
+    int reserveSortBuffers(SyncState& s)
+    {
+        CS_TRY(order_.ensure(ctx_, s.n * sizeof(uint32_t)));
+        CS_TRY(orderAlt_.ensure(ctx_, s.n * sizeof(uint32_t)));
+        CS_TRY(keysAlt_.ensure(ctx_, s.n * sizeof(K)));
+        s.sortTmpBytes = cstone_hip_sort_pairs_temp_bytes(kb, s.n);
+        CS_TRY(sortTmp_.ensure(ctx_, s.sortTmpBytes));
+        // (the deepest level: of the tree the last sync left behind, exact; the multi-rank path takes the same value
+        //  from its own pinned block)
+        if (!firstCall_ && !levelRangeHost_.empty() && !allDigits(sortMode_))
+            s.startPass = partialSortStartPass<K>(deepestLevel<K>(levelRangeHost_), bucketFocus_);
+        return CSTONE_OK;
+    }
+
+    //! computeSfcKeys + setMapFromCodes (assignment.hpp:81-86) in one call: the sort's digits are counted while the keys
+    //! are still in the encode kernel's registers, its first pass produces the positions instead of reading an iota
+    int encodeAndSort(SyncState& s, bool measure, bool* measured)
+    {
+        CS_TRY(sfcKeysAndOrderingHint(ctx_, curve_, kb, rb, *s.xPP, *s.yPP, *s.zPP, s.keys, order_.as<uint32_t>(), s.n,
+                                      box_, keysAlt_.p, orderAlt_.as<uint32_t>(), sortTmp_.p, s.sortTmpBytes, s.startPass,
+                                      ctx_->devScalars + 3, true, measure ? extentsDev() : nullptr, measured));
+        if (s.startPass == 0) CS_HIP(ctx_, hipMemsetAsync(ctx_->devScalars + 3, 0, sizeof(int), ctx_->stream));
+        return CSTONE_OK;
+    }
+
+    //! x, y, z change places with the first three scratch arrays (and h with the fourth)
+    void swapFieldsWithScratch(SyncState& s, bool withH)
+    {
+        std::swap(*s.xPP, s.scratch[0]);
+        std::swap(*s.yPP, s.scratch[1]);
+        std::swap(*s.zPP, s.scratch[2]);
+        if (withH) std::swap(*s.hPP, s.scratch[3]);
+    }
+
+    //! the gather of x, y, z for the first `count` entries of order_ starts on the second stream (once per sync, and only
+    //! with three scratch arrays); the caller's pointers name the new arrays from here on
+    int forkXyzGather(SyncState& s, size_t count)
+    {
+        if (s.fieldsMoved || s.numScratch < 3 || s.noOverlap || s.xyzForked || count == 0) return CSTONE_OK;
+        CS_TRY(ensureAuxStream(ctx_));
+        CS_HIP(ctx_, hipEventRecord(ctx_->evFork, ctx_->stream));
+        CS_HIP(ctx_, hipStreamWaitEvent(ctx_->aux, ctx_->evFork, 0));
+        const void* src[3] = {*s.xPP, *s.yPP, *s.zPP};
+        void* dst[3]       = {s.scratch[0], s.scratch[1], s.scratch[2]};
+        int rc;
         {
-            pinLeaves_ = static_cast<K*>(pin_.take(size_t(gLeaves_ + 1) * sizeof(K)));
-            CS_TRY(copyToPinned(ctx_, pinLeaves_, gTree_.p, size_t(gLeaves_ + 1) * sizeof(K)));
+            StreamScope scope(ctx_, ctx_->aux);
+            rc = cstone_hip_gather_multi(ctx_, sizeof(T), order_.as<uint32_t>(), count, src, dst, 3);
         }
-        pinLeafCount_ = gLeaves_;
+        CS_TRY(rc);
+        CS_HIP(ctx_, hipEventRecord(ctx_->evJoin, ctx_->aux));
+        ctx_->auxBusy = true;
+        swapFieldsWithScratch(s, false);
+        s.xyzForked = true;
         return CSTONE_OK;
     }
-    void takeGlobalReadBack()
+    //! the main stream waits for that gather (once)
+    int joinXyzGather(SyncState& s)
     {
-        if (!pinCounts_) return;
-        gCountsHost_.assign(pinCounts_, pinCounts_ + pinLeafCount_);
-        if (pinLeaves_) gLeavesHost_.assign(pinLeaves_, pinLeaves_ + pinLeafCount_ + 1);
-        pinCounts_ = nullptr, pinLeaves_ = nullptr;
+        if (s.xyzForked && !s.xyzJoined) CS_HIP(ctx_, hipStreamWaitEvent(ctx_->stream, ctx_->evJoin, 0));
+        s.xyzJoined   = true;
+        ctx_->auxBusy = false;
+        return CSTONE_OK;
     }
 
-    //! updateOctreeGlobal on one rank (tree/update_mpi.hpp:71-94): rebalance with the previous counts, then recount
-    int updateGlobal(const K* keys, size_t n, int* converged)
+    /*! The incremental re-sort (resort.hpp): particles that are still inside the leaf their position belonged to at the
+     *  previous sync are ordered leaf by leaf, the others are binned into their new leaves.  Same result as the sort of
+     *  all keys; a box that changed, too many movers or an overfull leaf take the regular path.
+     *  Result: s.sorted (keys and order_ are final; x, y, z are then on their way or, s.fieldsMoved, in place),
+     *  s.resortMarkers, and s.speculate -- switched off when the attempt has read the extents back and failed, with
+     *  box_ being the box this sync needs from then on.  One read-back. */
+    int tryResort(SyncState& s)
     {
-        while (true)
+        const int tileLeaves = LeafResort<K>::leavesPerTile(bucketFocus_);
+        const bool attempt   = !firstCall_ && tileLeaves > 0 && layoutLeaves_ == fLeaves_ && fLeaves_ > 0 &&
+                             resortBackoff_ == 0 && !s.boxMoved && mayResort(sortMode_);
+        if (resortBackoff_ > 0) --resortBackoff_;
+        // The field-carrying leaf pass (resort.hpp, sortLeavesFields; CSTONE_FUSED_LEAF_PASS=1 and four scratch arrays): x,
+        // y, z, h move with the keys in ONE pass over the particle arrays instead of the leaf pass and the gathers of h and
+        // of x, y, z.  Measured at 1e8 particles, every particle drifting: 2.14 ms against 0.66 + 0.37 + 0.91 ms for the
+        // three passes it replaces (it saves 8 of their 92 bytes per particle, and the ordering network -- bound by
+        // instruction issue -- and the data movement do not overlap inside one wave the way separate kernels on two streams
+        // do): kept selectable, not the default.
+        const bool fusedLeafPass = std::getenv("CSTONE_FUSED_LEAF_PASS") != nullptr; // (read per sync: tests switch it)
+        const bool carryFields   = s.numScratch >= 4 && fusedLeafPass;
+        if (!attempt) return CSTONE_OK;
+        CS_TRY(resort_.prepare(ctx_, fTree_.as<K>(), layout_.as<uint32_t>(), fLeaves_, s.n, keysAlt_.as<K>(), true,
+                               carryFields ? rb : 0));
+        const ResortArgs<K> ra = resort_.args();
+        bool done              = false;
+        CS_TRY(computeKeysResort(ctx_, curve_, kb, rb, *s.xPP, *s.yPP, *s.zPP, s.keys, s.n, box_, &ra,
+                                 s.speculate ? extentsDev() : nullptr, &done));
+        if (!done) return CSTONE_OK;
+        CS_TRY(resort_.binMovers(ctx_, tileLeaves));
+        // one read-back: the extents (slots 16..27) and what the re-sort found (28..31)
+        CS_TRY(copyToPinned(ctx_, ctx_->hostScalars + 16, ctx_->devScalars + 16, 16 * sizeof(int)));
+        CS_HIP(ctx_, hipStreamSynchronize(ctx_->stream));
+        cstone_box next = box_;
+        if (s.speculate)
         {
-            int leaves = gLeaves_;
-            int rc = cstone_hip_update_octree(ctx_, 8 * sizeof(K), keys, n, bucket_, gTree_.p, gCounts_.as<uint32_t>(),
-                                              &leaves, gCap_, 0xFFFFFFFFu, converged);
-            if (rc == CSTONE_E_CAPACITY)
+            double ext[6];
+            for (int k = 0; k < 6; ++k)
+                ext[k] = double(extentsHost()[k]);
+            next = limitBoxShrinking<T>(box_, ext, firstCall_);
+        }
+        const bool boxChanged = !sameLimits(next, box_);
+        const int* found      = ctx_->hostScalars + RESORT_SCALARS;
+        const uint32_t markers = uint32_t(found[0]), J = uint32_t(found[2]), movers = uint32_t(found[3]);
+        const int flags        = found[1];
+        s.resortMarkers        = markers;
+        if (!boxChanged && resortAccepted(flags, movers, s.n))
+        {
+            if (carryFields)
             {
-                CS_TRY(ensureTree(gTree_, gCounts_, gCap_, leaves + 1));
-                continue;
+                ResortFields rf{rb, {*s.xPP, *s.yPP, *s.zPP, *s.hPP}, {s.scratch[0], s.scratch[1], s.scratch[2], s.scratch[3]}};
+                CS_TRY(resort_.sortLeavesFields(ctx_, keysAlt_.as<K>(), s.keys, order_.as<uint32_t>(), rf, movers, markers,
+                                                J, tileLeaves));
+                swapFieldsWithScratch(s, true);
+                s.fieldsMoved = true;
             }
-            CS_TRY(rc);
-            gLeaves_ = leaves;
+            else
+            {
+                CS_TRY(resort_.sortLeaves(ctx_, keysAlt_.as<K>(), s.keys, order_.as<uint32_t>(), movers, markers, J,
+                                          tileLeaves, (flags & RESORT_LARGE_QUIET_TILES) != 0));
+                CS_TRY(forkXyzGather(s, s.n - markers)); // (the ordering is final: x, y, z follow on the second stream)
+            }
+            CS_HIP(ctx_, hipMemsetAsync(ctx_->devScalars + 3, 0, sizeof(int), ctx_->stream));
+            s.sorted    = true;
+            lastMovers_ = movers;
+            ++resorts_;
             return CSTONE_OK;
         }
+        // the caller's key array has not been touched: the regular path starts from scratch, with the box this sync
+        // needs (the extents are known by now)
+        if (boxChanged) { adoptChangedBox(next); }
+        else
+        {
+            resortBackoff_ = RESORT_BACKOFF_SYNCS;
+            ++resortFallbacks_; // (the multi-rank path backs off alike and keeps no such count)
+        }
+        s.speculate = false;
+        return CSTONE_OK;
     }
 
+    //! the speculation failed: `next` is the box of this sync, and the following syncs measure first
+    void adoptChangedBox(const cstone_box& next)
+    {
+        box_ = next;
+        ++boxRedos_;
+        measureFirst_ = true;
+    }
+
+    //! the regular path of a sync that was not re-sorted: encode + radix sort, then the check of a speculated box -- a
+    //! box that changed costs a second encode + sort
+    int encodeSortCheckBox(SyncState& s)
+    {
+        if (s.sorted) return CSTONE_OK;
+        bool measured = false;
+        CS_TRY(encodeAndSort(s, s.speculate, &measured));
+        if (!s.speculate) return CSTONE_OK;
+        double lim[6];
+        if (measured)
+        {
+            CS_TRY(copyToPinned(ctx_, extentsHost(), extentsDev(), 6 * sizeof(T)));
+            CS_HIP(ctx_, hipStreamSynchronize(ctx_->stream));
+            for (int k = 0; k < 6; ++k)
+                lim[k] = double(extentsHost()[k]);
+        }
+        else
+        {
+            // unaligned arrays: the plain encode ran, measure the extents the regular way
+            const void* all[3] = {*s.xPP, *s.yPP, *s.zPP};
+            CS_TRY(minMaxCoordinates(ctx_, rb, all, 3, s.n, lim));
+        }
+        const cstone_box next = limitBoxShrinking<T>(box_, lim, firstCall_);
+        if (sameLimits(next, box_)) return CSTONE_OK;
+        // the particles have left the box (or shrunk away from it by more than 5 %): keys and order again
+        adoptChangedBox(next);
+        // the key array is sorted by now: put every entry back to its particle first (the remove markers of the
+        // caller must meet their own particles again), then encode with the new box
+        CS_TRY(cstone_hip_scatter(ctx_, sizeof(K), order_.as<uint32_t>(), s.n, s.keys, keysAlt_.p));
+        CS_HIP(ctx_, hipMemcpyAsync(s.keys, keysAlt_.p, s.n * sizeof(K), hipMemcpyDeviceToDevice, ctx_->stream));
+        return encodeAndSort(s, false, nullptr);
+    }
+
+    //! one update step of the global tree (on the first call: until it converges) and s.numAssigned
+    int stepGlobalTree(SyncState& s)
+    {
+        if (firstCall_)
+        {
+            // spanning tree of one rank = the root; counts = bucket - 1 (assignment.hpp:48-53)
+            CS_TRY(ensureTree<K>(ctx_, gTree_, gCounts_, gCap_, 4096));
+            hipLaunchKernelGGL(initTreeKernel<K>, 1, 1, 0, ctx_->stream, gTree_.as<K>(), gCounts_.as<uint32_t>(),
+                               bucket_ - 1);
+            gLeaves_ = 1;
+        }
+        // A sync that was re-sorted knows its number of valid particles already, and the host holds the (small) global tree
+        // and its counts from the last sync: the update step of the global tree is then made on the HOST
+        // (globalTreeStepHost), the device only counts, and the counts travel back with the read-back of the focus-tree
+        // update -- one stream synchronisation and a handful of launches fewer than cstone_hip_update_octree.
+        if (s.sorted && !firstCall_ && hostGlobalStep_ && gHost_.matches(gLeaves_))
+        {
+            s.numAssigned = uint32_t(s.n) - s.resortMarkers;
+            if (s.numAssigned == 0) return fail(ctx_, CSTONE_E_ARG, "domain_sync: all particles removed");
+            bool same;
+            CS_TRY(gHost_.stepOnHost(ctx_, bucket_, gTree_, gCounts_, gCap_, gLeaves_, &same));
+            CS_TRY(cstone_hip_compute_node_counts(ctx_, kb, gTree_.p, gCounts_.as<uint32_t>(), gLeaves_, s.keys, s.n,
+                                                  0xFFFFFFFFu));
+            return gHost_.queueReadBack(ctx_, gTree_, gCounts_, gLeaves_, false, 256);
+        }
+        // particles flagged with the remove marker sort behind the end of the curve and leave the domain: their number
+        // is on its way to the host while the global tree is updated (whose own read-back completes the stream)
+        hipLaunchKernelGGL(countValidKernel<K>, 1, 1, 0, ctx_->stream, s.keys, s.n, ctx_->devScalars + 2);
+        CS_TRY(copyToPinned(ctx_, ctx_->hostScalars + 2, ctx_->devScalars + 2, 2 * sizeof(int)));
+        // updateOctreeGlobal on one rank (tree/update_mpi.hpp:71-94): rebalance with the previous counts, then recount
+        int converged = 0;
+        CS_TRY(updateOctreeGrowing<K>(ctx_, s.keys, s.n, bucket_, gTree_, gCounts_, gCap_, gLeaves_, &converged));
+        if (firstCall_)
+        {
+            // `while (!updateOctreeGlobal(...));` (assignment.hpp:95-98): at least one more step, whatever the first said
+            int guard = 0;
+            do
+            {
+                CS_TRY(updateOctreeGrowing<K>(ctx_, s.keys, s.n, bucket_, gTree_, gCounts_, gCap_, gLeaves_, &converged));
+                if (++guard > 64) return fail(ctx_, CSTONE_E_INTERNAL, "global tree does not converge");
+            } while (!converged);
+        }
+        // the copy was queued ahead of the update's own read-back (update_octree synchronises for the new leaf count)
+        s.numAssigned = uint32_t(ctx_->hostScalars[2]);
+        if (s.numAssigned == 0) return fail(ctx_, CSTONE_E_ARG, "domain_sync: all particles removed");
+        if (ctx_->hostScalars[3] != 0)
+        {
+            // a run of equal high digits was too long for the fix-up: sort the rest the regular way.  (The global tree
+            // above is not affected: its leaf boundaries cannot fall inside such a run.)
+            CS_TRY(cstone_hip_sort_pairs(ctx_, kb, s.keys, order_.as<uint32_t>(), s.n, keysAlt_.p, orderAlt_.as<uint32_t>(),
+                                         sortTmp_.p, s.sortTmpBytes));
+            ++fullSortFallbacks_;
+        }
+        // (tree and counts for the host's copy: they arrive behind the next synchronisation of the stream)
+        return gHost_.queueReadBack(ctx_, gTree_, gCounts_, gLeaves_, true, 256);
+    }
+
+    //! focus tree (octree_focus_mpi.hpp:535-553 on first call, then :225-227)
+    int updateFocusTree(SyncState& s)
+    {
+        int conv = 0;
+        if (firstCall_)
+        {
+            CS_TRY(ensureTree<K>(ctx_, fTree_, fLeafCounts_, fCap_, 4096));
+            hipLaunchKernelGGL(initTreeKernel<K>, 1, 1, 0, ctx_->stream, fTree_.as<K>(), fLeafCounts_.as<uint32_t>(),
+                               bucketFocus_ + 1);
+            fLeaves_ = 1;
+            CS_TRY(buildFocusOctree());
+            // counts_ of the single root node = bucketFocus + 1 (octree_focus_mpi.hpp:75)
+            CS_TRY(fCounts_.ensure(ctx_, sizeof(uint32_t)));
+            CS_HIP(ctx_, hipMemcpyAsync(fCounts_.p, fLeafCounts_.p, sizeof(uint32_t), hipMemcpyDeviceToDevice,
+                                        ctx_->stream));
+            int guard = 0;
+            while (!conv)
+            {
+                CS_TRY(updateFocus(s.keys, s.numAssigned, &conv));
+                if (++guard > 64) return fail(ctx_, CSTONE_E_INTERNAL, "focus tree does not converge");
+            }
+        }
+        return updateFocus(s.keys, s.numAssigned, &conv);
+    }
+
+    //! Halos::discover + computeLayout (halos.hpp:128-222) for the assignment [0, L); h goes into SFC order on the way
+    int layoutAndHalos(SyncState& s)
+    {
+        const NodeIdx L = fLeaves_;
+        CS_TRY(layout_.ensure(ctx_, size_t(L + 1) * sizeof(uint32_t)));
+        CS_TRY(radii_.ensure(ctx_, size_t(L) * sizeof(float)));
+        CS_TRY(flags_.ensure(ctx_, size_t(L) * sizeof(int)));
+        CS_HIP(ctx_, hipMemsetAsync(layout_.p, 0, sizeof(uint32_t), ctx_->stream));
+        CS_TRY(cstone_hip_inclusive_scan_u32(ctx_, fLeafCounts_.as<uint32_t>(), layout_.as<uint32_t>() + 1, size_t(L)));
+        layoutLeaves_ = L;
+        // gatherArrays(h) + segmentMax + scale in one pass over h (every leaf is assigned on one rank: the leaves' particles
+        // are all the assigned particles)
+        static const bool splitGather = std::getenv("CSTONE_SPLIT_H_GATHER") != nullptr; // tuning: the two-pass form
+        if (s.fieldsMoved)
+        {
+            // h is in SFC order already; the radii follow from the maxima the leaf pass folded per OLD leaf
+            CS_TRY(resort_.radiiOfLeaves(ctx_, L, layout_.as<uint32_t>(), *s.hPP, rb, haloSearchExt_, radii_.as<float>()));
+        }
+        else
+        {
+            // where h goes: the first scratch array -- unless x, y, z are still on their way there on the second stream; a
+            // fourth scratch array then takes h (no waiting), with three the gather of h waits for them
+            void** hDst = s.scratch;
+            if (s.xyzForked && s.numScratch >= 4) { hDst = &s.scratch[3]; }
+            else { CS_TRY(joinXyzGather(s)); }
+            if (splitGather)
+            {
+                CS_TRY(cstone_hip_gather(ctx_, sizeof(T), order_.as<uint32_t>(), s.numAssigned, *s.hPP, *hDst));
+                std::swap(*s.hPP, *hDst);
+                CS_TRY(cstone_hip_halo_radii(ctx_, rb, *s.hPP, layout_.as<uint32_t>(), 0, L, L, haloSearchExt_,
+                                             radii_.as<float>()));
+            }
+            else
+            {
+                CS_TRY(gatherWithHaloRadii(ctx_, rb, *s.hPP, order_.as<uint32_t>(), *hDst, layout_.as<uint32_t>(), L,
+                                           haloSearchExt_, radii_.as<float>()));
+                std::swap(*s.hPP, *hDst);
+            }
+        }
+        CS_HIP(ctx_, hipMemsetAsync(flags_.p, 0, size_t(L) * sizeof(int), ctx_->stream));
+        // one rank: every leaf is assigned, no halo leaves: layout = exclusive scan of the leaf counts (layout.hpp:150-165),
+        // which is the inclusive scan written above shifted by one.
+        return cstone_hip_find_halos(ctx_, curve_, kb, rb, fPrefixes_.p, fChild_.as<int32_t>(), fItl_.as<int32_t>(),
+                                     fTree_.p, radii_.as<float>(), &box_, 0, L, flags_.as<int32_t>());
+    }
+
+    //! updateLayout (domain.hpp:542-604): keys already sit at offset 0; gather the unordered arrays
+    int gatherFields(SyncState& s)
+    {
+        CS_TRY(joinXyzGather(s)); // (the property gathers below go through the buffers x, y, z were read from)
+        if (s.fieldsMoved || s.xyzForked) {} // (x, y, z went with the leaf pass, or on the second stream)
+        else if (s.numScratch >= 3)
+        {
+            // three free buffers (the caller's scratch tuple, R/domain/domain.hpp:196-206 has three as well): x, y, z go
+            // to their new order in ONE pass that reads the ordering once
+            const void* src[3] = {*s.xPP, *s.yPP, *s.zPP};
+            void* dst[3]       = {s.scratch[0], s.scratch[1], s.scratch[2]};
+            CS_TRY(cstone_hip_gather_multi(ctx_, sizeof(T), order_.as<uint32_t>(), s.numAssigned, src, dst, 3));
+            swapFieldsWithScratch(s, false);
+        }
+        else
+        {
+            void** arrays[3] = {s.xPP, s.yPP, s.zPP};
+            for (auto a : arrays)
+            {
+                CS_TRY(cstone_hip_gather(ctx_, sizeof(T), order_.as<uint32_t>(), s.numAssigned, *a, *s.scratch));
+                std::swap(*a, *s.scratch);
+            }
+        }
+        for (int p = 0; p < s.numProps; ++p)
+        {
+            if (s.propBytes[p] > int(sizeof(T)))
+                return fail(ctx_, CSTONE_E_ARG, "domain_sync: property %d is wider than the scratch element", p);
+            CS_TRY(cstone_hip_gather(ctx_, s.propBytes[p], order_.as<uint32_t>(), s.numAssigned, s.props[p], *s.scratch));
+            std::swap(s.props[p], *s.scratch);
+        }
+        return CSTONE_OK;
+    }
+
+    //! bookkeeping of a completed sync, and the sticky device-side error word (look-back spin bail-out of the sort,
+    //! traversal stack overflow ...): a sync that tripped one of those checks must not report success
+    int finishSync(const SyncState& s)
+    {
+        startIndex_ = 0;
+        endIndex_   = s.numAssigned;
+        lastN_      = s.n;
+        haveExpansion_ = false; // (the tree and the particles' order may have changed)
+        bufSize_    = s.numAssigned;
+        ++syncs_;
+        firstCall_  = false;
+#ifdef CSTONE_TEST_HOOKS // (tests: CSTONE_FORCE_DEVICE_ERROR raises the error word)
+        if (std::getenv("CSTONE_FORCE_DEVICE_ERROR")) CS_HIP(ctx_, hipMemsetAsync(ctx_->devScalars + 63, 1, 1, ctx_->stream));
+#endif
+        return cstone_hip_ctx_sync(ctx_);
+    }
     int buildFocusOctree()
     {
         const NodeIdx L = fLeaves_, M = L + (L - 1) / 7;
@@ -898,9 +840,7 @@ private:
                                               fChild_.as<int32_t>(), fCounts_.as<uint32_t>(), deepestBound_));
         // updateGeoCenters: the geometry of the nodes follows from the tree and the box alone -- nothing to do for an
         // unchanged tree inside an unchanged box (the reference recomputes it in every sync, octree_focus_mpi.hpp:259-273)
-        bool sameBox = centersNodes_ == newM;
-        for (int k = 0; k < 6; ++k)
-            sameBox = sameBox && centersBox_.lim[k] == box_.lim[k];
+        const bool sameBox = centersNodes_ == newM && sameLimits(centersBox_, box_);
         if (!(*converged && sameBox))
         {
             CS_TRY(fCenters_.ensure(ctx_, size_t(newM) * 3 * sizeof(T)));
@@ -928,12 +868,7 @@ private:
     bool resortedThisSync_ = false;
     DevBuf gTree_, gCounts_;
     int gCap_ = 0, gLeaves_ = 0;
-    std::vector<K> gLeavesHost_;        // host copies of the global tree and its counts (the host makes its update step)
-    std::vector<uint32_t> gCountsHost_;
-    PinnedBlock pin_;
-    uint32_t* pinCounts_ = nullptr;
-    K* pinLeaves_        = nullptr;
-    int pinLeafCount_    = 0;
+    GlobalTreeHost<K> gHost_; // host copies of the global tree and its counts (the host makes its update step)
     bool hostGlobalStep_ = std::getenv("CSTONE_DEVICE_GLOBAL_STEP") == nullptr; // (tests: the device-side step)
     DevBuf fTree_, fLeafCounts_, fCounts_, newTree_;
     int fCap_ = 0, fLeaves_ = 0;

@@ -395,12 +395,6 @@ public:
     void setHaloFactor(float f) override { haloExt_ = f; }
     void setSortMode(int mode) override { sortMode_ = mode; }
     void contextGone(bool gone) override { ctxGone_ = gone; }
-    bool mayResort() const
-    {
-        return sortMode_ == CSTONE_SORT_INCREMENTAL && std::getenv("CSTONE_NO_RESORT") == nullptr &&
-               std::getenv("CSTONE_FULL_SORT") == nullptr;
-    }
-    bool allDigits() const { return sortMode_ == CSTONE_SORT_ALL_DIGITS || std::getenv("CSTONE_FULL_SORT") != nullptr; }
 
     //! before the first sync: how halos are found (CSTONE_MR_HALOS_LET: the reference's way, CSTONE_MR_HALOS_OWNER_SIDE)
     int setHaloMode(int mode) override
@@ -553,7 +547,7 @@ public:
         const size_t si = view_.start_index;
         int rc = let_->updateExpansionCenters(static_cast<const T*>(x) + si, static_cast<const T*>(y) + si,
                                               static_cast<const T*>(z) + si, static_cast<const char*>(m) + si * size_t(massBits / 8),
-                                              massBits, gTree_.as<K>(), gLeavesHost_.data(), gLeaves_);
+                                              massBits, gTree_.as<K>(), gHost_.leaves.data(), gLeaves_);
         haveExpansionCenters_ = rc == CSTONE_OK;
         return rc;
     }
@@ -596,7 +590,7 @@ public:
         }
         CS_TRY(t.updateMultipoles(static_cast<const T*>(x) + si, static_cast<const T*>(y) + si,
                                   static_cast<const T*>(z) + si, static_cast<const char*>(m) + si * mb, massBits,
-                                  gTree_.as<K>(), gLeavesHost_.data(), gLeaves_));
+                                  gTree_.as<K>(), gHost_.leaves.data(), gLeaves_));
         if (ei == si) return CSTONE_OK;
         const size_t off = size_t(si) * sizeof(T);
         return cstone_hip_compute_gravity_let(
@@ -711,9 +705,7 @@ public:
         //      sync finds the box unchanged (an open box whose outermost particles move changes every time).
         //      The box all-reduce stays the first collective of the sync on every rank either way.
         const bool anyOpen = !(box_.bc[0] == 1 && box_.bc[1] == 1 && box_.bc[2] == 1);
-        bool boxSame       = true;
-        for (int k = 0; k < 6; ++k)
-            boxSame = boxSame && box_.lim[k] == layoutBox_.lim[k];
+        const bool boxSame = sameLimits(box_, layoutBox_);
         const int tileLeavesSpec = LeafResort<K>::leavesPerTile(bucketFocus_);
         // What the re-sort of THIS sync starts from: the leaves of my range and their layout as the last COMPLETED sync
         // left them.  The members are invalidated here and set again only at the end of the tree update below: a sync
@@ -725,15 +717,13 @@ public:
         resortTree_ = nullptr, resortLeaves_ = 0, layoutParticles_ = 0;
         bool speculate = anyOpen && !firstCall_ && !measureFirst_ && !pending_ && boxSame && n >= resortMinParticles() &&
                          n == layoutParticles && tileLeavesSpec > 0 && resortLeaves > 0 && resortBackoff_ == 0 &&
-                         mayResort() && speculativeBox_;
+                         mayResort(sortMode_) && speculativeBox_; // (CSTONE_NO_SPECULATIVE_BOX: read once, in the
+                                                                   //  constructor; the single-rank path reads it per sync)
         if (!speculate)
         {
             const cstone_box before = box_;
             CS_TRY(updateBox(x, y, z, n));
-            bool moved = false;
-            for (int k = 0; k < 6; ++k)
-                moved = moved || box_.lim[k] != before.lim[k];
-            if (!firstCall_ && anyOpen) measureFirst_ = moved;
+            if (!firstCall_ && anyOpen) measureFirst_ = !sameLimits(box_, before);
         }
         tick("1 box");
 
@@ -753,9 +743,7 @@ public:
         // the syncs that re-sort
         if (levelRangePending_)
         {
-            prevMaxLeafLevel_ = 0;
-            for (int l = 0; l <= int(maxLevel<K>()); ++l)
-                if (hostLevelRange_[l + 1] > hostLevelRange_[l]) prevMaxLeafLevel_ = l;
+            prevMaxLeafLevel_  = deepestLevel<K>(hostLevelRange_);
             levelRangePending_ = false;
         }
         // ---- the incremental re-sort (resort.hpp), as in the single-rank domain: the input arrays are the assigned block
@@ -764,12 +752,10 @@ public:
         bool resorted         = false;
         bool boxChecked       = false;
         const int tileLeaves  = LeafResort<K>::leavesPerTile(bucketFocus_);
-        bool sameBox          = true;
-        for (int k = 0; k < 6; ++k)
-            sameBox = sameBox && box_.lim[k] == layoutBox_.lim[k];
+        const bool sameBox    = sameLimits(box_, layoutBox_); // (box_ may be a freshly measured one by now)
         const size_t resortMin = resortMinParticles();
         const bool tryResort = !firstCall_ && n >= resortMin && n == layoutParticles && tileLeaves > 0 && sameBox && resortLeaves > 0 &&
-                               resortBackoff_ == 0 && !pending_ && mayResort();
+                               resortBackoff_ == 0 && !pending_ && mayResort(sortMode_);
         if (resortBackoff_ > 0) --resortBackoff_;
         if (tryResort)
         {
@@ -802,8 +788,7 @@ public:
                 }
                 cstone_box next;
                 CS_TRY(reduceBox(dev, &next, foundHere, foundHere ? counters : nullptr));
-                for (int k = 0; k < 6; ++k)
-                    boxHolds = boxHolds && next.lim[k] == box_.lim[k];
+                boxHolds = sameLimits(next, box_);
                 if (!boxHolds)
                 {
                     box_          = next;
@@ -818,15 +803,15 @@ public:
                 if (foundHere) { std::copy(counters, counters + 4, found); }
                 else { CS_TRY(toHost(found, ctx_->devScalars + RESORT_SCALARS, sizeof found)); }
                 const uint32_t markers = uint32_t(found[0]), J = uint32_t(found[2]), movers = uint32_t(found[3]);
-                if ((found[1] & 7) == 0 && movers <= n / 8)
+                if (resortAccepted(found[1], movers, n))
                 {
                     CS_TRY(resort_.sortLeaves(ctx_, keysAlt_.as<K>(), keys_.as<K>(), order_.as<uint32_t>(), movers, markers,
-                                              J, tileLeaves, (found[1] & 8) != 0));
+                                              J, tileLeaves, (found[1] & RESORT_LARGE_QUIET_TILES) != 0));
                     resorted    = true;
                     lastMovers_ = movers;
                     ++resorts_;
                 }
-                else { resortBackoff_ = 4; }
+                else { resortBackoff_ = RESORT_BACKOFF_SYNCS; } // (not counted here, unlike the single-rank path)
             }
         }
         if (speculate && !boxChecked)
@@ -839,9 +824,9 @@ public:
             // radix passes only over the digits above the leaf level (+1) of the previous tree, runs of equal high digits
             // are finished by a fix-up pass; a run that is too long raises a flag and the regular sort completes the job
             int startPass = 0;
-            if (!firstCall_ && prevMaxLeafLevel_ >= 0 && !allDigits())
-                startPass = std::max(0, (3 * int(maxLevel<K>()) -
-                                         3 * (prevMaxLeafLevel_ + 1 + (bucketFocus_ > 128) + (bucketFocus_ > 1024))) / 8) & ~1;
+            // (the deepest level: as the last read of the pinned block left it; the single-rank path keeps the whole array)
+            if (!firstCall_ && prevMaxLeafLevel_ >= 0 && !allDigits(sortMode_))
+                startPass = partialSortStartPass<K>(prevMaxLeafLevel_, bucketFocus_);
             int* tooLong = reinterpret_cast<int*>(scal_.as<char>() + 128);
             CS_TRY(sfcKeysAndOrderingHint(ctx_, curve_, kb, rb, x, y, z, keys_.p, order_.as<uint32_t>(), n, box_,
                                           keysAlt_.p, orderAlt_.as<uint32_t>(), sortTmp_.p, sortTmp_.bytes, startPass,
@@ -856,7 +841,8 @@ public:
 
         tick("2 encode+sort");
         CS_TRY(updateGlobalTree(n));
-        CS_TRY(queueGlobalTreeReadBack());
+        // (counts, and the leaf array when the device made it; room behind them for the cut points and the count matrix)
+        CS_TRY(gHost_.queueReadBack(ctx_, gTree_, gCounts_, gLeaves_, !gLeavesOnHost_, size_t(P_ + 1) * (P_ + 2) * 8 + 1024));
 
         // ---- C3 (first half): send ranges on the sorted keys and the counts of everybody.  The assignment follows from
         //      the global counts that are on their way to the host; it rarely changes from one sync to the next (a
@@ -885,8 +871,8 @@ public:
             CS_HIP(ctx_, hipGetLastError());
             if (!pinRows)
             {
-                pinRows = static_cast<uint64_t*>(pin_.take(rows.size() * 8));
-                pinCut  = static_cast<uint64_t*>(pin_.take(size_t(P_ + 1) * 8));
+                pinRows = static_cast<uint64_t*>(gHost_.pin.take(rows.size() * 8));
+                pinCut  = static_cast<uint64_t*>(gHost_.pin.take(size_t(P_ + 1) * 8));
             }
             if (P_ > 1)
             {
@@ -905,7 +891,7 @@ public:
         const bool speculateCuts = !firstCall_ && int(assignment_.size()) == P_ + 1 && speculateCuts_;
         if (speculateCuts) CS_TRY(queueCuts(assignment_));
         CS_HIP(ctx_, hipStreamSynchronize(ctx_->stream)); // global counts (+ leaves), the sort's flag, cut points, matrix
-        takeGlobalTreeReadBack();
+        gHost_.takeReadBack();
         if (speculateCuts) takeCuts();
         if (partialSort && ctx_->hostScalars[3] != 0)
             CS_TRY(cstone_hip_sort_pairs(ctx_, kb, keys_.p, order_.as<uint32_t>(), n, keysAlt_.p, orderAlt_.as<uint32_t>(),
@@ -1128,7 +1114,7 @@ public:
             if (grav)
             {
                 const char* mSorted = o.props[numProps - 1].as<char>() + M * size_t(massBits / 8);
-                rc = let_->updateGrav(box_, keysM, size_t(nm), assignment_.data(), gTree_.as<K>(), gLeavesHost_.data(),
+                rc = let_->updateGrav(box_, keysM, size_t(nm), assignment_.data(), gTree_.as<K>(), gHost_.leaves.data(),
                                       gCounts_.as<uint32_t>(), gLeaves_, o.x.as<T>() + M, o.y.as<T>() + M, o.z.as<T>() + M,
                                       mSorted, massBits, o.h.as<T>() + M, haloExt_, &centerDriftTol_,
                                       pending_ ? rank_ + 1 : 0, gTreeSame_);
@@ -1621,36 +1607,23 @@ private:
         CS_TRY(toHost(ext, dev, counters ? sizeof ext : 7 * sizeof(double)));
         if (counters) std::memcpy(counters, ext + 7, 4 * sizeof(int));
         if (ext[6] < 0) return agreed(int(-ext[6]) - 1);
-        *next = box_;
-        double fit[6];
+        double fit[6]; // (lo, -hi) -> {min, max}; limitBoxShrinking keeps the limits of the periodic axes
         for (int d = 0; d < 3; ++d)
-        {
             fit[2 * d] = ext[2 * d], fit[2 * d + 1] = -ext[2 * d + 1];
-            if (box_.bc[d] == 1) fit[2 * d] = box_.lim[2 * d], fit[2 * d + 1] = box_.lim[2 * d + 1];
-        }
-        if (firstCall_) { std::copy(fit, fit + 6, next->lim); }
-        else
-        {
-            // limitBoxShrinking (R/sfc/box.hpp:415-431), evaluated in T like the reference
-            const T shrink = T(0.05);
-            for (int d = 0; d < 3; ++d)
-            {
-                T lo = T(box_.lim[2 * d]), hi = T(box_.lim[2 * d + 1]);
-                T len                = hi - lo;
-                next->lim[2 * d]     = std::min(T(fit[2 * d]), T(lo + shrink * len));
-                next->lim[2 * d + 1] = std::max(T(fit[2 * d + 1]), T(hi - shrink * len));
-            }
-        }
+        *next = limitBoxShrinking<T>(box_, fit, firstCall_);
         return CSTONE_OK;
     }
 
-    int ensureTree(DevBuf& tree, DevBuf& counts, int& cap, int need)
+    //! the counts of the global tree summed over the ranks, and no smaller than this rank's own (maxWithLocalKernel)
+    int allReduceGlobalCounts()
     {
-        if (need <= cap) return CSTONE_OK;
-        int newCap = std::max(need, int(cap * 1.5));
-        CS_TRY(tree.ensure(ctx_, size_t(newCap + 1) * sizeof(K), true));
-        CS_TRY(counts.ensure(ctx_, size_t(newCap) * sizeof(uint32_t), true));
-        cap = newCap;
+        if (P_ == 1) return CSTONE_OK;
+        CS_TRY(gLocalCounts_.ensure(ctx_, size_t(gLeaves_) * sizeof(uint32_t)));
+        CS_HIP(ctx_, hipMemcpyAsync(gLocalCounts_.p, gCounts_.p, size_t(gLeaves_) * sizeof(uint32_t),
+                                    hipMemcpyDeviceToDevice, ctx_->stream));
+        CS_TRY(callComm(comm_.all_reduce(comm_.user, gCounts_.p, size_t(gLeaves_), 1, 0), "all_reduce (counts)"));
+        hipLaunchKernelGGL(maxWithLocalKernel, gridFor(size_t(gLeaves_), 256), 256, 0, ctx_->stream,
+                           gCounts_.as<uint32_t>(), gLocalCounts_.as<uint32_t>(), gLeaves_);
         return CSTONE_OK;
     }
 
@@ -1661,40 +1634,22 @@ private:
         {
             std::vector<K> init = initialGlobalTree<K>(P_);
             int leaves          = int(init.size()) - 1;
-            CS_TRY(ensureTree(gTree_, gCounts_, gCap_, std::max(4096, 2 * leaves)));
+            CS_TRY(ensureTree<K>(ctx_, gTree_, gCounts_, gCap_, std::max(4096, 2 * leaves)));
             std::vector<uint32_t> c0(leaves, bucket_ - 1);
             CS_HIP(ctx_, hipMemcpy(gTree_.p, init.data(), init.size() * sizeof(K), hipMemcpyHostToDevice));
             CS_HIP(ctx_, hipMemcpy(gCounts_.p, c0.data(), c0.size() * 4, hipMemcpyHostToDevice));
             gLeaves_ = leaves;
         }
-        if (!firstCall_ && hostGlobalStep_ && int(gLeavesHost_.size()) == gLeaves_ + 1 && int(gCountsHost_.size()) == gLeaves_)
+        if (!firstCall_ && hostGlobalStep_ && gHost_.matches(gLeaves_))
         {
             // later calls take exactly ONE update step (assignment.hpp:92-98).  The tree is small and replicated and the
             // host holds its leaves and the all-reduced counts of the last sync (assign() read them): the decision and the
             // new leaf array are made here; the device counts this rank's keys, the counts are reduced, and assign() reads
             // them back together with everything else the sync needs at that point -- no read-back in between
-            std::vector<K> fresh;
-            const bool same = globalTreeStepHost<K>(gLeavesHost_, gCountsHost_, bucket_, fresh);
-            if (!same)
-            {
-                const int leaves = int(fresh.size()) - 1;
-                CS_TRY(ensureTree(gTree_, gCounts_, gCap_, leaves + 1));
-                gLeavesHost_.swap(fresh);
-                CS_TRY(cstone_hip_upload(ctx_, gTree_.p, gLeavesHost_.data(), gLeavesHost_.size() * sizeof(K)));
-                gLeaves_ = leaves;
-            }
-            gTreeSame_ = same;
+            CS_TRY(gHost_.stepOnHost(ctx_, bucket_, gTree_, gCounts_, gCap_, gLeaves_, &gTreeSame_));
             CS_TRY(cstone_hip_compute_node_counts(ctx_, kb, gTree_.p, gCounts_.as<uint32_t>(), gLeaves_, keys_.p, n,
                                                   0xFFFFFFFFu));
-            if (P_ > 1)
-            {
-                CS_TRY(gLocalCounts_.ensure(ctx_, size_t(gLeaves_) * sizeof(uint32_t)));
-                CS_HIP(ctx_, hipMemcpyAsync(gLocalCounts_.p, gCounts_.p, size_t(gLeaves_) * sizeof(uint32_t),
-                                            hipMemcpyDeviceToDevice, ctx_->stream));
-                CS_TRY(callComm(comm_.all_reduce(comm_.user, gCounts_.p, size_t(gLeaves_), 1, 0), "all_reduce (counts)"));
-                hipLaunchKernelGGL(maxWithLocalKernel, gridFor(size_t(gLeaves_), 256), 256, 0, ctx_->stream,
-                                   gCounts_.as<uint32_t>(), gLocalCounts_.as<uint32_t>(), gLeaves_);
-            }
+            CS_TRY(allReduceGlobalCounts());
             gLeavesOnHost_ = true;
             return CSTONE_OK;
         }
@@ -1702,26 +1657,10 @@ private:
         int steps = 0;
         while (true)
         {
-            int leaves = gLeaves_, conv = 0;
-            int rc = cstone_hip_update_octree(ctx_, kb, keys_.p, n, bucket_, gTree_.p, gCounts_.as<uint32_t>(), &leaves,
-                                              gCap_, 0xFFFFFFFFu, &conv);
-            if (rc == CSTONE_E_CAPACITY)
-            {
-                CS_TRY(ensureTree(gTree_, gCounts_, gCap_, leaves + 1));
-                continue;
-            }
-            CS_TRY(rc);
-            gLeaves_ = leaves;
+            int conv = 0;
+            CS_TRY(updateOctreeGrowing<K>(ctx_, keys_.p, n, bucket_, gTree_, gCounts_, gCap_, gLeaves_, &conv));
             gTreeSame_ = steps == 0 && !firstCall_ && conv != 0; // the one step of a later sync kept every leaf
-            if (P_ > 1)
-            {
-                CS_TRY(gLocalCounts_.ensure(ctx_, size_t(leaves) * sizeof(uint32_t)));
-                CS_HIP(ctx_, hipMemcpyAsync(gLocalCounts_.p, gCounts_.p, size_t(leaves) * sizeof(uint32_t),
-                                            hipMemcpyDeviceToDevice, ctx_->stream));
-                CS_TRY(callComm(comm_.all_reduce(comm_.user, gCounts_.p, size_t(leaves), 1, 0), "all_reduce (counts)"));
-                hipLaunchKernelGGL(maxWithLocalKernel, gridFor(size_t(leaves), 256), 256, 0, ctx_->stream,
-                                   gCounts_.as<uint32_t>(), gLocalCounts_.as<uint32_t>(), leaves);
-            }
+            CS_TRY(allReduceGlobalCounts());
             ++steps;
             // later calls: exactly one step; first call: one step, then `while (!update)` (assignment.hpp:92-98)
             if (!firstCall_ || (steps >= 2 && conv)) break;
@@ -1730,32 +1669,11 @@ private:
         return CSTONE_OK;
     }
 
-    //! the read-back of the global counts (and of the leaf array, when the device made it): queued into the pinned
-    //! block, not waited for; takeGlobalTreeReadBack() behind the synchronisation
-    int queueGlobalTreeReadBack()
-    {
-        CS_TRY(pin_.reserve(ctx_, size_t(gLeaves_) * 4 + size_t(gLeaves_ + 1) * sizeof(K) + size_t(P_ + 1) * (P_ + 2) * 8 + 1024));
-        pinCounts_ = static_cast<uint32_t*>(pin_.take(size_t(gLeaves_) * 4));
-        CS_TRY(copyToPinned(ctx_, pinCounts_, gCounts_.p, size_t(gLeaves_) * 4));
-        pinLeaves_ = nullptr;
-        if (!gLeavesOnHost_)
-        {
-            pinLeaves_ = static_cast<K*>(pin_.take(size_t(gLeaves_ + 1) * sizeof(K)));
-            CS_TRY(copyToPinned(ctx_, pinLeaves_, gTree_.p, size_t(gLeaves_ + 1) * sizeof(K)));
-        }
-        return CSTONE_OK;
-    }
-    void takeGlobalTreeReadBack()
-    {
-        gCountsHost_.assign(pinCounts_, pinCounts_ + gLeaves_);
-        if (pinLeaves_) gLeavesHost_.assign(pinLeaves_, pinLeaves_ + gLeaves_ + 1);
-    }
-
     //! makeSfcAssignment + limitBoundaryShifts from the host copies of the global tree (after the read-back completed)
     int assign()
     {
-        const std::vector<uint32_t>& counts = gCountsHost_;
-        const std::vector<K>& leaves        = gLeavesHost_;
+        const std::vector<uint32_t>& counts = gHost_.counts;
+        const std::vector<K>& leaves        = gHost_.leaves;
         std::vector<int> bins = uniformBinsHost(counts, P_);
         std::vector<K> fresh(P_ + 1);
         for (int r = 0; r <= P_; ++r)
@@ -1775,39 +1693,13 @@ private:
     {
         if (fLeaves_ == 0)
         {
-            int cap = std::max<int>(4096, int(4 * nm / std::max(1u, bucketFocus_)) + 4096);
-            while (true)
-            {
-                CS_TRY(ensureTree(fTree_, fCounts_, fCap_, cap));
-                int leaves = 0, iters = 0;
-                int rc = cstone_hip_compute_octree(ctx_, kb, keysM, nm, bucketFocus_, fTree_.p, fCounts_.as<uint32_t>(),
-                                                   &leaves, fCap_, 0xFFFFFFFFu, &iters);
-                if (rc == CSTONE_E_CAPACITY)
-                {
-                    cap = leaves + 1;
-                    continue;
-                }
-                CS_TRY(rc);
-                fLeaves_   = leaves;
-                treeSteps_ = 0;
-                return CSTONE_OK;
-            }
+            const int cap = std::max<int>(4096, int(4 * nm / std::max(1u, bucketFocus_)) + 4096);
+            treeSteps_    = 0;
+            return computeOctreeGrowing<K>(ctx_, keysM, nm, bucketFocus_, fTree_, fCounts_, fCap_, cap, fLeaves_);
         }
         ++treeSteps_;
-        while (true)
-        {
-            int leaves = fLeaves_, conv = 0;
-            int rc = cstone_hip_update_octree(ctx_, kb, keysM, nm, bucketFocus_, fTree_.p, fCounts_.as<uint32_t>(),
-                                              &leaves, fCap_, 0xFFFFFFFFu, &conv);
-            if (rc == CSTONE_E_CAPACITY)
-            {
-                CS_TRY(ensureTree(fTree_, fCounts_, fCap_, leaves + 1));
-                continue;
-            }
-            CS_TRY(rc);
-            fLeaves_ = leaves;
-            return CSTONE_OK;
-        }
+        int conv = 0;
+        return updateOctreeGrowing<K>(ctx_, keysM, nm, bucketFocus_, fTree_, fCounts_, fCap_, fLeaves_, &conv);
     }
 
     /*! The rank's SFC range must start and end on leaf boundaries of its own tree (the job of enforceKeys in the
@@ -1892,7 +1784,7 @@ private:
         *last  = b[1] >= end ? newL : newIndexOf(b[1], int(q[3]), q[4] == b[1]);
         if (!cuts.empty())
         {
-            CS_TRY(ensureTree(fTree_, fCounts_, fCap_, newL));
+            CS_TRY(ensureTree<K>(ctx_, fTree_, fCounts_, fCap_, newL));
             CS_TRY(fTmp_.ensure(ctx_, size_t(newL + 1) * sizeof(K)));
             K* t        = fTmp_.as<K>();
             const K* ft = fTree_.as<K>();
@@ -1946,41 +1838,15 @@ private:
         const size_t n   = view_.num_particles_with_halos;
         if (nsLeaves_ == 0)
         {
-            int cap = std::max<int>(4096, int(4 * n / std::max(1u, bucketFocus_)) + 4096);
-            while (true)
-            {
-                CS_TRY(ensureTree(nsTree_, nsCounts_, nsCap_, cap));
-                int leaves = 0, iters = 0;
-                int rc = cstone_hip_compute_octree(ctx_, kb, keysAll, n, bucketFocus_, nsTree_.p,
-                                                   nsCounts_.as<uint32_t>(), &leaves, nsCap_, 0xFFFFFFFFu, &iters);
-                if (rc == CSTONE_E_CAPACITY)
-                {
-                    cap = leaves + 1;
-                    continue;
-                }
-                CS_TRY(rc);
-                nsLeaves_ = leaves;
-                break;
-            }
+            const int cap = std::max<int>(4096, int(4 * n / std::max(1u, bucketFocus_)) + 4096);
+            CS_TRY(computeOctreeGrowing<K>(ctx_, keysAll, n, bucketFocus_, nsTree_, nsCounts_, nsCap_, cap, nsLeaves_));
         }
         else
         {
             // the particles moved a little since the last request: a few update steps (each one level of splits or
             // merges, R/tree/csarray.hpp:430-448); the search stays correct if the last one still changed something
-            for (int it = 0, conv = 0; it < 4 && !conv;)
-            {
-                int leaves = nsLeaves_;
-                int rc = cstone_hip_update_octree(ctx_, kb, keysAll, n, bucketFocus_, nsTree_.p, nsCounts_.as<uint32_t>(),
-                                                  &leaves, nsCap_, 0xFFFFFFFFu, &conv);
-                if (rc == CSTONE_E_CAPACITY)
-                {
-                    CS_TRY(ensureTree(nsTree_, nsCounts_, nsCap_, leaves + 1));
-                    continue;
-                }
-                CS_TRY(rc);
-                nsLeaves_ = leaves;
-                ++it;
-            }
+            for (int it = 0, conv = 0; it < 4 && !conv; ++it)
+                CS_TRY(updateOctreeGrowing<K>(ctx_, keysAll, n, bucketFocus_, nsTree_, nsCounts_, nsCap_, nsLeaves_, &conv));
         }
         const NodeIdx L = nsLeaves_, M = L + (L - 1) / 7;
         CS_TRY(nsLayout_.ensure(ctx_, size_t(L + 1) * sizeof(uint32_t)));
@@ -2036,12 +1902,9 @@ private:
     DevBuf gTree_, gCounts_, gLocalCounts_;
     int gCap_ = 0, gLeaves_ = 0;
     bool gTreeSame_ = false; // the global leaf array is that of the previous sync
-    std::vector<K> gLeavesHost_;        // host copies of the global tree and its all-reduced counts (assign())
-    std::vector<uint32_t> gCountsHost_;
-    bool gLeavesOnHost_  = false;       // gLeavesHost_ is what gTree_ holds (the host made this sync's update step)
-    PinnedBlock pin_;                   // where the read-backs of a sync arrive
-    uint32_t* pinCounts_ = nullptr;
-    K* pinLeaves_        = nullptr;
+    GlobalTreeHost<K> gHost_;           // host copies of the global tree and its all-reduced counts (assign()), and the
+                                        // pinned block where the read-backs of a sync arrive
+    bool gLeavesOnHost_  = false;       // gHost_.leaves is what gTree_ holds (the host made this sync's update step)
     bool hostGlobalStep_ = std::getenv("CSTONE_MR_DEVICE_GLOBAL_STEP") == nullptr; // (tests: the device-side step)
     bool speculateCuts_  = std::getenv("CSTONE_MR_NO_SPECULATIVE_CUTS") == nullptr;  // (tests: always ask after assign())
     int cutRedos_        = 0; // syncs whose assignment changed: cut points asked for twice
