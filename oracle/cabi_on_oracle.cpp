@@ -225,6 +225,73 @@ int cstone_hip_compute_node_counts(cstone_hip_ctx*, int key_bits, const void* tr
                        nodeCounts<K>((const K*)tree, counts, num_nodes, (const K*)keys, n, max_count);
                    });
 }
+//! the guess only shortens the search (cstone_hip.h): the restatement searches the whole array and never reads it
+int cstone_hip_compute_node_counts_guided(cstone_hip_ctx* ctx, int key_bits, const void* tree, uint32_t* counts,
+                                          int num_nodes, const void* keys, size_t n, uint32_t max_count, const uint32_t*)
+{
+    return cstone_hip_compute_node_counts(ctx, key_bits, tree, counts, num_nodes, keys, n, max_count);
+}
+int cstone_hip_update_octree(cstone_hip_ctx*, int key_bits, const void* keys, size_t n, uint32_t bucket_size, void* tree,
+                             uint32_t* counts, int* num_leaves_host, int cap_leaves, uint32_t max_count,
+                             int* converged_host)
+{
+    if (*num_leaves_host < 1 || *num_leaves_host > cap_leaves) return CSTONE_E_ARG;
+    int rc = CSTONE_OK;
+    int st = withKey(key_bits,
+                     [&](auto k)
+                     {
+                         using K = decltype(k);
+                         std::vector<K> t((K*)tree, (K*)tree + *num_leaves_host + 1);
+                         std::vector<unsigned> c(counts, counts + *num_leaves_host);
+                         bool converged  = updateOctree<K>((const K*)keys, n, bucket_size, t, c, max_count);
+                         *num_leaves_host = int(c.size());
+                         if (int(c.size()) > cap_leaves)
+                         {
+                             rc = CSTONE_E_CAPACITY; // (needed leaf count reported, buffers as they were)
+                             return;
+                         }
+                         *converged_host = converged;
+                         std::copy(t.begin(), t.end(), (K*)tree);
+                         std::copy(c.begin(), c.end(), counts);
+                     });
+    return st ? st : rc;
+}
+int cstone_hip_compute_octree(cstone_hip_ctx* ctx, int key_bits, const void* keys, size_t n, uint32_t bucket_size,
+                              void* tree, uint32_t* counts, int* num_leaves_host, int cap_leaves, uint32_t max_count,
+                              int* iterations_host)
+{
+    if (cap_leaves < 1) return CSTONE_E_ARG;
+    int st = withKey(key_bits,
+                     [&](auto k)
+                     {
+                         using K       = decltype(k);
+                         ((K*)tree)[0] = 0, ((K*)tree)[1] = endKey<K>();
+                     });
+    if (st) return st;
+    counts[0]        = uint32_t(n); // (seeded with n whatever max_count is, R/tree/csarray.hpp:460)
+    *num_leaves_host = 1;
+    int converged = 0, iters = 0;
+    while (!converged)
+    {
+        int rc = cstone_hip_update_octree(ctx, key_bits, keys, n, bucket_size, tree, counts, num_leaves_host, cap_leaves,
+                                          max_count, &converged);
+        if (rc) return rc;
+        if (++iters > 64) return CSTONE_E_INTERNAL;
+    }
+    if (iterations_host) *iterations_host = iters;
+    return CSTONE_OK;
+}
+int cstone_hip_scan_u32_to_u64(cstone_hip_ctx*, const uint32_t* in, uint64_t* out, size_t n, uint64_t init, int inclusive)
+{
+    if (n && static_cast<const void*>(in) == static_cast<const void*>(out)) return CSTONE_E_ARG;
+    uint64_t run = init;
+    for (size_t i = 0; i < n; ++i)
+    {
+        out[i] = inclusive ? run + in[i] : run;
+        run += in[i];
+    }
+    return CSTONE_OK;
+}
 int cstone_hip_compute_node_ops(cstone_hip_ctx*, int key_bits, const void* tree, int num_nodes, const uint32_t* counts,
                                 uint32_t bucket_size, int32_t* node_ops, int* new_num_nodes_host, int* converged_host)
 {
