@@ -130,8 +130,8 @@ struct DomainBase
     virtual void setSpeculativeBox(bool on)              = 0;
     virtual int reapplySync(const void* in, size_t n, int elemBytes, void* out) = 0;
     virtual int updateExpansionCenters(const void* x, const void* y, const void* z, const void* m, int massBits) = 0;
-    virtual int computeGravity(const void* x, const void* y, const void* z, const void* m, int massBits, int order,
-                               double G, double eps2, void* ax, void* ay, void* az, void* phi) = 0;
+    virtual int computeGravity(const void* x, const void* y, const void* z, const void* m, const void* h, int massBits,
+                               int order, double G, double eps2, void* ax, void* ay, void* az, void* phi) = 0;
     virtual void stats(cstone_hip_domain_stats* out)     = 0;
 };
 
@@ -246,9 +246,9 @@ public:
 
     /*! Barnes-Hut gravity on the focus tree (csrc/gravity.hip): the multipoles about the current expansion centres, then
      *  the group walk over the end_index particles.  The target groups follow from the sync's tree and are kept until
-     *  the next sync. */
-    int computeGravity(const void* x, const void* y, const void* z, const void* m, int massBits, int order, double G,
-                       double eps2, void* ax, void* ay, void* az, void* phi) override
+     *  the next sync.  h: per-particle softening lengths laid out like x, or null. */
+    int computeGravity(const void* x, const void* y, const void* z, const void* m, const void* h, int massBits,
+                       int order, double G, double eps2, void* ax, void* ay, void* az, void* phi) override
     {
         if (!haveExpansion_)
             return fail(ctx_, CSTONE_E_ARG,
@@ -276,10 +276,10 @@ public:
         CS_TRY(cstone_hip_upsweep_multipoles(ctx_, rb, massBits, x, y, z, m, fLti_.as<int32_t>() + I, L,
                                              layout_.as<uint32_t>(), int(maxLevel<K>()), levels, fChild_.as<int32_t>(),
                                              M, fExpansion_.p, fMultipoles_.p));
-        return cstone_hip_compute_gravity(ctx_, rb, massBits, x, y, z, m, 0, endIndex_, groups_.as<uint32_t>(),
-                                          numGroups_, &box_, fChild_.as<int32_t>(), fItl_.as<int32_t>(),
-                                          layout_.as<uint32_t>(), fExpansion_.p, fMultipoles_.p, order, G, eps2, ax,
-                                          ay, az, phi, nullptr, nullptr);
+        return cstone_hip_compute_gravity_h(ctx_, rb, massBits, x, y, z, m, h, 0, endIndex_, groups_.as<uint32_t>(),
+                                            numGroups_, &box_, fChild_.as<int32_t>(), fItl_.as<int32_t>(),
+                                            layout_.as<uint32_t>(), fExpansion_.p, fMultipoles_.p, order, G, eps2, ax,
+                                            ay, az, phi, nullptr, nullptr);
     }
 
     /*! Domain::reapplySync (R/domain/domain.hpp:334-378) without an exchange: the kept particles in SFC order */
@@ -996,7 +996,15 @@ int cstone_hip_domain_compute_gravity(cstone_hip_domain* dom, const void* x, con
                                       void* az, void* phi)
 {
     if (!dom) return CSTONE_E_ARG;
-    return dom->impl->computeGravity(x, y, z, m, mass_bits, order, G, eps2, ax, ay, az, phi);
+    return dom->impl->computeGravity(x, y, z, m, nullptr, mass_bits, order, G, eps2, ax, ay, az, phi);
+}
+
+int cstone_hip_domain_compute_gravity_h(cstone_hip_domain* dom, const void* x, const void* y, const void* z,
+                                        const void* m, const void* h, int mass_bits, int order, double G, double eps2,
+                                        void* ax, void* ay, void* az, void* phi)
+{
+    if (!dom) return CSTONE_E_ARG;
+    return dom->impl->computeGravity(x, y, z, m, h, mass_bits, order, G, eps2, ax, ay, az, phi);
 }
 
 int cstone_hip_domain_view_get(cstone_hip_domain* dom, cstone_hip_domain_view* out)

@@ -359,8 +359,8 @@ struct MrBase
                      const int* propBytes, int numProps, const void* keysIn, const void* mass = nullptr,
                      int massBits = 0) = 0;
     virtual int updateExpansionCenters(const void* x, const void* y, const void* z, const void* m, int massBits) = 0;
-    virtual int computeGravity(const void* x, const void* y, const void* z, const void* m, int massBits, int order,
-                               double G, double eps2, void* ax, void* ay, void* az, void* phi) = 0;
+    virtual int computeGravity(const void* x, const void* y, const void* z, const void* m, const void* h, int massBits,
+                               int order, double G, double eps2, void* ax, void* ay, void* az, void* phi) = 0;
     virtual int multipoles(const void** out, int32_t* numNodes)                           = 0;
     virtual int view(cstone_hip_domain_mr_view* out)                                     = 0;
     virtual void setHaloFactor(float f)                                                  = 0;
@@ -555,10 +555,11 @@ public:
     /*! Barnes-Hut gravity on the locally essential tree (csrc/gravity.hip): the multipoles of every node of the focus
      *  tree about the current expansion centres (FocusLet::updateMultipoles, with its exchanges), then the LET walk over
      *  the assigned particles.  x, y, z, m are laid out like the result arrays and read on the halo ranges too; the
-     *  caller has exchanged the halos of m.  Whatever makes the call fail on its arguments is decided before the first
+     *  caller has exchanged the halos of m.  h (nullable): per-particle softening lengths laid out like x and read on the
+     *  halo ranges too; the sync's h has them filled (sync: x, y, z and h travel in one halo message).  Whatever makes the call fail on its arguments is decided before the first
      *  collective, from state that is the same on every rank, so nobody is left waiting. */
-    int computeGravity(const void* x, const void* y, const void* z, const void* m, int massBits, int order, double G,
-                       double eps2, void* ax, void* ay, void* az, void* phi) override
+    int computeGravity(const void* x, const void* y, const void* z, const void* m, const void* h, int massBits,
+                       int order, double G, double eps2, void* ax, void* ay, void* az, void* phi) override
     {
         if (!useLet_)
             return fail(ctx_, CSTONE_E_ARG, "domain_mr_compute_gravity: needs the locally essential tree "
@@ -593,8 +594,8 @@ public:
                                   gTree_.as<K>(), gHost_.leaves.data(), gLeaves_));
         if (ei == si) return CSTONE_OK;
         const size_t off = size_t(si) * sizeof(T);
-        return cstone_hip_compute_gravity_let(
-            ctx_, rb, massBits, x, y, z, m, si, ei, gravGroups_.as<uint32_t>(), gravNumGroups_, &box_, t.childOffsets(),
+        return cstone_hip_compute_gravity_let_h(
+            ctx_, rb, massBits, x, y, z, m, h, si, ei, gravGroups_.as<uint32_t>(), gravNumGroups_, &box_, t.childOffsets(),
             t.internalToLeaf(), t.layout(), t.expansionCenters(), t.multipoles(), order, G, eps2,
             static_cast<char*>(ax) + off, static_cast<char*>(ay) + off, static_cast<char*>(az) + off,
             phi ? static_cast<char*>(phi) + off : nullptr, nullptr, nullptr, nullptr);
@@ -2053,7 +2054,15 @@ int cstone_hip_domain_mr_compute_gravity(cstone_hip_domain_mr* dom, const void* 
                                          void* ay, void* az, void* phi)
 {
     if (!dom) return CSTONE_E_ARG;
-    return dom->impl->computeGravity(x, y, z, m, mass_bits, order, G, eps2, ax, ay, az, phi);
+    return dom->impl->computeGravity(x, y, z, m, nullptr, mass_bits, order, G, eps2, ax, ay, az, phi);
+}
+
+int cstone_hip_domain_mr_compute_gravity_h(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z,
+                                           const void* m, const void* h, int mass_bits, int order, double G,
+                                           double eps2, void* ax, void* ay, void* az, void* phi)
+{
+    if (!dom) return CSTONE_E_ARG;
+    return dom->impl->computeGravity(x, y, z, m, h, mass_bits, order, G, eps2, ax, ay, az, phi);
 }
 
 int cstone_hip_domain_mr_multipoles_get(cstone_hip_domain_mr* dom, const void** multipoles, int32_t* num_nodes)

@@ -22,6 +22,14 @@
 // consecutive targets, and on a non-convex piece of the space-filling curve that box reaches outside the focus.
 // Without the rule the leaf's mass would vanish from the sum.  node, child and the range are wave-uniform already, so
 // the rule costs a scalar branch and no lane mask.
+//
+// Per-particle softening (the SOFT flag of the walk and of the direct sum, cstone_hip_compute_gravity_h): with
+// H = h_i + h_j a pair closer than H (r2 = |d|^2 + eps2 < H^2) interacts like a point with a homogeneous sphere of radius
+// H, force linear in d and phi = -G m (3 H^2 - r2) / (2 H^3), both continuous at r2 = H^2.  One sqrt and one division per
+// pair as before; h == 0 everywhere gives the Plummer rule's bits.  M2P keeps eps2 only.
+//
+// Direct sum (cstone_hip_direct_gravity): one wave per 64 targets, the sources streamed through the same P2P tile, cut
+// into segments over gridDim.y whose partial sums a second kernel adds in segment order (no atomics).
 #include <algorithm>
 
 #include "ctx.hpp"
@@ -127,16 +135,58 @@ __global__ __launch_bounds__(256) void upsweepMultipolesKernel(NodeIdx firstCell
     out[0] = M, out[1] = qxx, out[2] = qxy, out[3] = qxz, out[4] = qyy, out[5] = qyz, out[6] = qzz, out[7] = T(0);
 }
 
+/*! P2P of one tile: the cnt <= 64 sources that the lanes hold in (xl, yl, zl, ml[, hl]), source k being particle
+ *  base + k, on the lane's target i; d = r_j - r_i, the target itself skipped.  The inner loop of the walk and of the
+ *  direct sum: it touches no memory.  SOFT: the rule of the head of the file with H = hi + h_j */
+template<bool SOFT, class T>
+__device__ __forceinline__ void p2pTile(T xl, T yl, T zl, T ml, T hl, int cnt, uint32_t base, uint32_t i, T xi, T yi,
+                                        T zi, T hi, T eps2, T& axi, T& ayi, T& azi, T& phii)
+{
+    for (int k = 0; k < cnt; ++k)
+    {
+        const T dx = readLane(xl, k) - xi, dy = readLane(yl, k) - yi, dz = readLane(zl, k) - zi;
+        const T mj = readLane(ml, k);
+        const T r2 = dx * dx + dy * dy + dz * dz + eps2;
+        if constexpr (SOFT)
+        {
+            const T H      = hi + readLane(hl, k);
+            const T H2     = H * H;
+            const bool in  = r2 < H2;
+            T rinv         = T(1) / sqrt(in ? H2 : r2);
+            rinv           = (base + uint32_t(k) == i) ? T(0) : rinv;
+            const T mr     = mj * rinv;
+            const T mr3    = mr * rinv * rinv; // (the Plummer branch's order: h == 0 gives its bits)
+            const T w      = in ? T(1.5) - T(0.5) * r2 * (rinv * rinv) : T(1);
+            axi += mr3 * dx;
+            ayi += mr3 * dy;
+            azi += mr3 * dz;
+            phii -= mr * w;
+        }
+        else
+        {
+            T rinv      = T(1) / sqrt(r2);
+            rinv        = (base + uint32_t(k) == i) ? T(0) : rinv;
+            const T mr  = mj * rinv;
+            const T mr3 = mr * rinv * rinv;
+            axi += mr3 * dx;
+            ayi += mr3 * dy;
+            azi += mr3 * dz;
+            phii -= mr;
+        }
+    }
+}
+
 /*! The walk of one target group per wave (see the head of the file).  Outputs are indexed by i - first; lanes without a
- *  target (the tail of a group) take the group's first particle as a stand-in and write nothing. */
-template<class T, class Tm, bool QUAD, bool LET>
+ *  target (the tail of a group) take the group's first particle as a stand-in and write nothing.  SOFT: h, indexed like
+ *  x (by particle, not by i - first), softens the P2P pairs; without it h is not read. */
+template<class T, class Tm, bool QUAD, bool LET, bool SOFT>
 __global__ __launch_bounds__(GW_BLOCK) void gravityWalkKernel(
     const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ z, const Tm* __restrict__ m, uint32_t first,
     uint32_t last, const uint32_t* __restrict__ groups, uint32_t numGroups, const NodeIdx* __restrict__ childOffsets,
     const NodeIdx* __restrict__ internalToLeaf, const uint32_t* __restrict__ layout, const T* __restrict__ centers,
     const T* __restrict__ mp, T G, T eps2, T* __restrict__ ax, T* __restrict__ ay, T* __restrict__ az,
     T* __restrict__ phi, uint32_t* __restrict__ p2pCounts, uint32_t* __restrict__ m2pCounts,
-    uint32_t* __restrict__ letCounts, int* __restrict__ errors)
+    uint32_t* __restrict__ letCounts, int* __restrict__ errors, const T* __restrict__ h)
 {
     __shared__ NodeIdx stacks[GW_WAVES][GW_STACK];
     const int lane = int(threadIdx.x & 63u), wave = int(threadIdx.x >> 6);
@@ -153,6 +203,8 @@ __global__ __launch_bounds__(GW_BLOCK) void gravityWalkKernel(
         const bool valid    = chunk + lane < cend;
         const uint32_t i    = valid ? chunk + lane : chunk;
         const T xi = x[i], yi = y[i], zi = z[i];
+        T hi = T(0);
+        if constexpr (SOFT) hi = h[i];
 
         // the box of the targets: centre (lo + hi) / 2, half-size (hi - lo) / 2 (identical in every lane)
         const T lox = waveMin(xi), loy = waveMin(yi), loz = waveMin(zi);
@@ -253,26 +305,14 @@ __global__ __launch_bounds__(GW_BLOCK) void gravityWalkKernel(
             for (uint32_t base = jb; base < je; base += 64)
             {
                 const int cnt = int(min(64u, je - base));
-                T xl = T(0), yl = T(0), zl = T(0), ml = T(0);
+                T xl = T(0), yl = T(0), zl = T(0), ml = T(0), hl = T(0);
                 if (lane < cnt)
                 {
                     xl = x[base + lane], yl = y[base + lane], zl = z[base + lane];
                     ml = T(m[base + lane]);
+                    if constexpr (SOFT) hl = h[base + lane];
                 }
-                for (int k = 0; k < cnt; ++k)
-                {
-                    const T dx = readLane(xl, k) - xi, dy = readLane(yl, k) - yi, dz = readLane(zl, k) - zi;
-                    const T mj = readLane(ml, k);
-                    const T r2 = dx * dx + dy * dy + dz * dz + eps2;
-                    T rinv     = T(1) / sqrt(r2);
-                    rinv       = (base + uint32_t(k) == i) ? T(0) : rinv;
-                    const T mr  = mj * rinv;
-                    const T mr3 = mr * rinv * rinv;
-                    axi += mr3 * dx;
-                    ayi += mr3 * dy;
-                    azi += mr3 * dz;
-                    phii -= mr;
-                }
+                p2pTile<SOFT>(xl, yl, zl, ml, hl, cnt, base, i, xi, yi, zi, hi, eps2, axi, ayi, azi, phii);
             }
             nP2P += (je - jb) - ((i >= jb && i < je) ? 1u : 0u);
         }
@@ -290,6 +330,83 @@ __global__ __launch_bounds__(GW_BLOCK) void gravityWalkKernel(
             }
         }
     }
+}
+
+constexpr int DG_BLOCK = 256;
+constexpr int DG_WAVES = DG_BLOCK / 64;
+
+//! flag[0] = 1 if any of the target indices is not a particle
+__global__ __launch_bounds__(256) void checkTargetsKernel(const uint32_t* __restrict__ targets, uint32_t numTargets,
+                                                          uint32_t n, int* __restrict__ flag)
+{
+    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+    if (k < numTargets && targets[k] >= n) *flag = 1;
+}
+
+/*! The direct sum: one wave per 64 targets (target position t: particle targets[t], or first + t without a list), one
+ *  per lane; lanes behind the last target take the wave's first target as a stand-in and write nothing.  blockIdx.y
+ *  is the segment of the sources: the ceil(n / 64) source tiles are cut into gridDim.y contiguous runs, and the wave
+ *  streams the tiles of its run through p2pTile.  partial[(segment * numTargets + t) * 4 ..] = (ax, ay, az, phi) without G */
+template<class T, class Tm, bool SOFT>
+__global__ __launch_bounds__(DG_BLOCK) void directGravityKernel(const T* __restrict__ x, const T* __restrict__ y,
+                                                                const T* __restrict__ z, const Tm* __restrict__ m,
+                                                                const T* __restrict__ h, uint32_t n, uint32_t first,
+                                                                const uint32_t* __restrict__ targets,
+                                                                uint32_t numTargets, T eps2, T* __restrict__ partial)
+{
+    const int lane = int(threadIdx.x & 63u), wave = int(threadIdx.x >> 6);
+    const uint32_t t0 = (blockIdx.x * DG_WAVES + wave) * 64u;
+    if (t0 >= numTargets) return;
+    const bool valid = t0 + lane < numTargets;
+    const uint32_t t = valid ? t0 + lane : t0;
+    const uint32_t i = targets ? targets[t] : first + t;
+    const T xi = x[i], yi = y[i], zi = z[i];
+    T hi = T(0);
+    if constexpr (SOFT) hi = h[i];
+
+    const uint32_t seg = blockIdx.y, numSegments = gridDim.y;
+    const uint32_t tiles = (n + 63u) / 64u; // (n <= 2^32 - 64: checked by the caller)
+    const uint32_t tb = uint32_t(uint64_t(tiles) * seg / numSegments);
+    const uint32_t te = uint32_t(uint64_t(tiles) * (seg + 1) / numSegments);
+
+    T axi = 0, ayi = 0, azi = 0, phii = 0;
+    for (uint32_t tile = tb; tile < te; ++tile)
+    {
+        const uint32_t base = tile * 64u;
+        const int cnt       = int(min(64u, n - base));
+        T xl = T(0), yl = T(0), zl = T(0), ml = T(0), hl = T(0);
+        if (lane < cnt)
+        {
+            xl = x[base + lane], yl = y[base + lane], zl = z[base + lane];
+            ml = T(m[base + lane]);
+            if constexpr (SOFT) hl = h[base + lane];
+        }
+        p2pTile<SOFT>(xl, yl, zl, ml, hl, cnt, base, i, xi, yi, zi, hi, eps2, axi, ayi, azi, phii);
+    }
+    if (valid)
+    {
+        T* out = partial + (size_t(seg) * numTargets + t) * 4;
+        out[0] = axi, out[1] = ayi, out[2] = azi, out[3] = phii;
+    }
+}
+
+//! the partial sums of the segments added in segment order, times G
+template<class T>
+__global__ __launch_bounds__(256) void directGravityReduceKernel(const T* __restrict__ partial, uint32_t numTargets,
+                                                                 uint32_t numSegments, T G, T* __restrict__ ax,
+                                                                 T* __restrict__ ay, T* __restrict__ az,
+                                                                 T* __restrict__ phi)
+{
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= numTargets) return;
+    T a = 0, b = 0, c = 0, p = 0;
+    for (uint32_t s = 0; s < numSegments; ++s)
+    {
+        const T* in = partial + (size_t(s) * numTargets + t) * 4;
+        a += in[0], b += in[1], c += in[2], p += in[3];
+    }
+    ax[t] = G * a, ay[t] = G * b, az[t] = G * c;
+    if (phi) phi[t] = G * p;
 }
 
 //! the internal nodes of every level, deepest first, from their children
@@ -319,31 +436,37 @@ int upsweepMultipoles(cstone_hip_ctx* ctx, const void* x, const void* y, const v
     return upsweepLevels<T>(ctx, numLevels, levelRangeHost, childOffsets, centers, multipoles);
 }
 
-template<class T, class Tm, bool QUAD, bool LET>
-void launchWalk(cstone_hip_ctx* ctx, const void* x, const void* y, const void* z, const void* m, uint32_t first,
+template<class T, class Tm, bool QUAD, bool LET, bool SOFT>
+void launchWalk(cstone_hip_ctx* ctx, const void* x, const void* y, const void* z, const void* m, const void* h,
+                uint32_t first,
                 uint32_t last, const uint32_t* groups, uint32_t numGroups, const int32_t* childOffsets,
                 const int32_t* internalToLeaf, const uint32_t* layout, const void* centers, const void* multipoles,
                 double G, double eps2, void* ax, void* ay, void* az, void* phi, uint32_t* p2p, uint32_t* m2p,
                 uint32_t* letM2p)
 {
-    hipLaunchKernelGGL((gravityWalkKernel<T, Tm, QUAD, LET>), gridFor(numGroups, GW_WAVES), GW_BLOCK, 0, ctx->stream,
+    hipLaunchKernelGGL((gravityWalkKernel<T, Tm, QUAD, LET, SOFT>), gridFor(numGroups, GW_WAVES), GW_BLOCK, 0, ctx->stream,
                        (const T*)x, (const T*)y, (const T*)z, (const Tm*)m, first, last, groups, numGroups, childOffsets,
                        internalToLeaf, layout, (const T*)centers, (const T*)multipoles, T(G), T(eps2), (T*)ax, (T*)ay,
-                       (T*)az, (T*)phi, p2p, m2p, letM2p, ctx->devScalars + 63);
+                       (T*)az, (T*)phi, p2p, m2p, letM2p, ctx->devScalars + 63, (const T*)h);
 }
 
 template<class T, class Tm>
-int launchGravity(cstone_hip_ctx* ctx, const void* x, const void* y, const void* z, const void* m, uint32_t first,
-                  uint32_t last, const uint32_t* groups, uint32_t numGroups, const int32_t* childOffsets,
+int launchGravity(cstone_hip_ctx* ctx, const void* x, const void* y, const void* z, const void* m, const void* h,
+                  uint32_t first, uint32_t last, const uint32_t* groups, uint32_t numGroups, const int32_t* childOffsets,
                   const int32_t* internalToLeaf, const uint32_t* layout, const void* centers, const void* multipoles,
                   int order, bool let, double G, double eps2, void* ax, void* ay, void* az, void* phi, uint32_t* p2p,
                   uint32_t* m2p, uint32_t* letM2p)
 {
-#define CSTONE_WALK(QUAD, LET)                                                                                         \
-    launchWalk<T, Tm, QUAD, LET>(ctx, x, y, z, m, first, last, groups, numGroups, childOffsets, internalToLeaf, layout, \
-                                 centers, multipoles, G, eps2, ax, ay, az, phi, p2p, m2p, letM2p)
-    if (order == 2) { let ? CSTONE_WALK(true, true) : CSTONE_WALK(true, false); }
-    else { let ? CSTONE_WALK(false, true) : CSTONE_WALK(false, false); }
+#define CSTONE_WALK(QUAD, LET, SOFT)                                                                                   \
+    launchWalk<T, Tm, QUAD, LET, SOFT>(ctx, x, y, z, m, h, first, last, groups, numGroups, childOffsets, internalToLeaf, \
+                                       layout, centers, multipoles, G, eps2, ax, ay, az, phi, p2p, m2p, letM2p)
+    if (h)
+    {
+        if (order == 2) { let ? CSTONE_WALK(true, true, true) : CSTONE_WALK(true, false, true); }
+        else { let ? CSTONE_WALK(false, true, true) : CSTONE_WALK(false, false, true); }
+    }
+    else if (order == 2) { let ? CSTONE_WALK(true, true, false) : CSTONE_WALK(true, false, false); }
+    else { let ? CSTONE_WALK(false, true, false) : CSTONE_WALK(false, false, false); }
 #undef CSTONE_WALK
     CS_HIP(ctx, hipGetLastError());
     return CSTONE_OK;
@@ -351,8 +474,8 @@ int launchGravity(cstone_hip_ctx* ctx, const void* x, const void* y, const void*
 
 //! the checks and the dispatch behind cstone_hip_compute_gravity and cstone_hip_compute_gravity_let
 int computeGravity(cstone_hip_ctx* ctx, bool let, const char* name, int real_bits, int mass_bits, const void* x,
-                   const void* y, const void* z, const void* m, uint32_t first, uint32_t last, const uint32_t* groups,
-                   uint32_t num_groups, const cstone_box* box_host, const int32_t* child_offsets,
+                   const void* y, const void* z, const void* m, const void* h, uint32_t first, uint32_t last,
+                   const uint32_t* groups, uint32_t num_groups, const cstone_box* box_host, const int32_t* child_offsets,
                    const int32_t* internal_to_leaf, const uint32_t* layout, const void* expansion_centers,
                    const void* multipoles, int order, double G, double eps2, void* ax, void* ay, void* az, void* phi,
                    uint32_t* p2p_counts, uint32_t* m2p_counts, uint32_t* let_m2p_counts);
@@ -360,8 +483,8 @@ int computeGravity(cstone_hip_ctx* ctx, bool let, const char* name, int real_bit
 bool badBits(int bits) { return bits != 32 && bits != 64; }
 
 int computeGravity(cstone_hip_ctx* ctx, bool let, const char* name, int real_bits, int mass_bits, const void* x,
-                   const void* y, const void* z, const void* m, uint32_t first, uint32_t last, const uint32_t* groups,
-                   uint32_t num_groups, const cstone_box* box_host, const int32_t* child_offsets,
+                   const void* y, const void* z, const void* m, const void* h, uint32_t first, uint32_t last,
+                   const uint32_t* groups, uint32_t num_groups, const cstone_box* box_host, const int32_t* child_offsets,
                    const int32_t* internal_to_leaf, const uint32_t* layout, const void* expansion_centers,
                    const void* multipoles, int order, double G, double eps2, void* ax, void* ay, void* az, void* phi,
                    uint32_t* p2p_counts, uint32_t* m2p_counts, uint32_t* let_m2p_counts)
@@ -376,7 +499,7 @@ int computeGravity(cstone_hip_ctx* ctx, bool let, const char* name, int real_bit
     {
         StageTimer timer(ctx, CSTONE_STAGE_GRAVITY);
 #define CSTONE_GRAVITY(T, Tm)                                                                                          \
-    launchGravity<T, Tm>(ctx, x, y, z, m, first, last, groups, num_groups, child_offsets, internal_to_leaf, layout,     \
+    launchGravity<T, Tm>(ctx, x, y, z, m, h, first, last, groups, num_groups, child_offsets, internal_to_leaf, layout,     \
                          expansion_centers, multipoles, order, let, G, eps2, ax, ay, az, phi, p2p_counts, m2p_counts,   \
                          let_m2p_counts)
         int rc;
@@ -387,6 +510,34 @@ int computeGravity(cstone_hip_ctx* ctx, bool let, const char* name, int real_bit
     }
     // a stack overflow of the walk sets the sticky error word: report it here instead of returning a partial result
     return cstone_hip_ctx_sync(ctx);
+}
+
+//! how many segments cstone_hip_direct_gravity cuts the sources into when the caller leaves it open (see the header)
+uint32_t directSegments(uint32_t numTargets, uint32_t n)
+{
+    const uint32_t tiles  = (n + 63u) / 64u;
+    const uint32_t blocks = (numTargets + DG_BLOCK - 1) / DG_BLOCK;
+    const uint32_t fill   = (1024u + blocks - 1) / blocks; // 1024 blocks of 4 waves: 16 waves on each of 256 CUs
+    return std::max(1u, std::min(fill, tiles / 8u));       // at least 8 tiles (512 sources) per segment
+}
+
+template<class T, class Tm>
+int launchDirect(cstone_hip_ctx* ctx, const void* x, const void* y, const void* z, const void* m, const void* h,
+                 uint32_t n, uint32_t first, const uint32_t* targets, uint32_t numTargets, uint32_t numSegments,
+                 double G, double eps2, void* partial, void* ax, void* ay, void* az, void* phi)
+{
+    const dim3 grid(gridFor(numTargets, DG_BLOCK), numSegments);
+    if (h)
+        hipLaunchKernelGGL((directGravityKernel<T, Tm, true>), grid, DG_BLOCK, 0, ctx->stream, (const T*)x, (const T*)y,
+                           (const T*)z, (const Tm*)m, (const T*)h, n, first, targets, numTargets, T(eps2), (T*)partial);
+    else
+        hipLaunchKernelGGL((directGravityKernel<T, Tm, false>), grid, DG_BLOCK, 0, ctx->stream, (const T*)x,
+                           (const T*)y, (const T*)z, (const Tm*)m, (const T*)nullptr, n, first, targets, numTargets,
+                           T(eps2), (T*)partial);
+    hipLaunchKernelGGL(directGravityReduceKernel<T>, gridFor(numTargets, 256), 256, 0, ctx->stream, (const T*)partial,
+                       numTargets, numSegments, T(G), (T*)ax, (T*)ay, (T*)az, (T*)phi);
+    CS_HIP(ctx, hipGetLastError());
+    return CSTONE_OK;
 }
 
 } // namespace
@@ -421,6 +572,18 @@ int cstone_hip_upsweep_multipoles(cstone_hip_ctx* ctx, int real_bits, int mass_b
 #undef CSTONE_UPSWEEP
 }
 
+int cstone_hip_compute_gravity_h(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
+                                 const void* z, const void* m, const void* h, uint32_t first, uint32_t last,
+                                 const uint32_t* groups, uint32_t num_groups, const cstone_box* box_host,
+                                 const int32_t* child_offsets, const int32_t* internal_to_leaf, const uint32_t* layout,
+                                 const void* expansion_centers, const void* multipoles, int order, double G, double eps2,
+                                 void* ax, void* ay, void* az, void* phi, uint32_t* p2p_counts, uint32_t* m2p_counts)
+{
+    return computeGravity(ctx, false, "compute_gravity", real_bits, mass_bits, x, y, z, m, h, first, last, groups,
+                          num_groups, box_host, child_offsets, internal_to_leaf, layout, expansion_centers, multipoles,
+                          order, G, eps2, ax, ay, az, phi, p2p_counts, m2p_counts, nullptr);
+}
+
 int cstone_hip_compute_gravity(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
                                const void* z, const void* m, uint32_t first, uint32_t last, const uint32_t* groups,
                                uint32_t num_groups, const cstone_box* box_host, const int32_t* child_offsets,
@@ -428,9 +591,22 @@ int cstone_hip_compute_gravity(cstone_hip_ctx* ctx, int real_bits, int mass_bits
                                const void* multipoles, int order, double G, double eps2, void* ax, void* ay, void* az,
                                void* phi, uint32_t* p2p_counts, uint32_t* m2p_counts)
 {
-    return computeGravity(ctx, false, "compute_gravity", real_bits, mass_bits, x, y, z, m, first, last, groups,
+    return cstone_hip_compute_gravity_h(ctx, real_bits, mass_bits, x, y, z, m, nullptr, first, last, groups, num_groups,
+                                        box_host, child_offsets, internal_to_leaf, layout, expansion_centers, multipoles,
+                                        order, G, eps2, ax, ay, az, phi, p2p_counts, m2p_counts);
+}
+
+int cstone_hip_compute_gravity_let_h(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
+                                     const void* z, const void* m, const void* h, uint32_t first, uint32_t last,
+                                     const uint32_t* groups, uint32_t num_groups, const cstone_box* box_host,
+                                     const int32_t* child_offsets, const int32_t* internal_to_leaf,
+                                     const uint32_t* layout, const void* expansion_centers, const void* multipoles,
+                                     int order, double G, double eps2, void* ax, void* ay, void* az, void* phi,
+                                     uint32_t* p2p_counts, uint32_t* m2p_counts, uint32_t* let_m2p_counts)
+{
+    return computeGravity(ctx, true, "compute_gravity_let", real_bits, mass_bits, x, y, z, m, h, first, last, groups,
                           num_groups, box_host, child_offsets, internal_to_leaf, layout, expansion_centers, multipoles,
-                          order, G, eps2, ax, ay, az, phi, p2p_counts, m2p_counts, nullptr);
+                          order, G, eps2, ax, ay, az, phi, p2p_counts, m2p_counts, let_m2p_counts);
 }
 
 int cstone_hip_compute_gravity_let(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
@@ -441,9 +617,57 @@ int cstone_hip_compute_gravity_let(cstone_hip_ctx* ctx, int real_bits, int mass_
                                    double eps2, void* ax, void* ay, void* az, void* phi, uint32_t* p2p_counts,
                                    uint32_t* m2p_counts, uint32_t* let_m2p_counts)
 {
-    return computeGravity(ctx, true, "compute_gravity_let", real_bits, mass_bits, x, y, z, m, first, last, groups,
-                          num_groups, box_host, child_offsets, internal_to_leaf, layout, expansion_centers, multipoles,
-                          order, G, eps2, ax, ay, az, phi, p2p_counts, m2p_counts, let_m2p_counts);
+    return cstone_hip_compute_gravity_let_h(ctx, real_bits, mass_bits, x, y, z, m, nullptr, first, last, groups,
+                                            num_groups, box_host, child_offsets, internal_to_leaf, layout,
+                                            expansion_centers, multipoles, order, G, eps2, ax, ay, az, phi, p2p_counts,
+                                            m2p_counts, let_m2p_counts);
+}
+
+int cstone_hip_direct_gravity(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
+                              const void* z, const void* m, const void* h, uint32_t n, uint32_t first, uint32_t last,
+                              const uint32_t* targets, uint32_t num_targets, int num_segments, double G, double eps2,
+                              void* ax, void* ay, void* az, void* phi)
+{
+    if (!ctx || badBits(real_bits) || badBits(mass_bits) || !(eps2 >= 0.0) || num_segments < 0 || n > 0xffffffffu - 64u)
+        return fail(ctx, CSTONE_E_ARG, "direct_gravity: bad argument");
+    if (!targets && (last < first || last > n)) return fail(ctx, CSTONE_E_ARG, "direct_gravity: [first, last) is not a range of [0, n)");
+    const uint32_t nt = targets ? num_targets : last - first;
+    if (nt == 0) return CSTONE_OK;
+    if (n == 0 || !x || !y || !z || !m || !ax || !ay || !az)
+        return fail(ctx, CSTONE_E_ARG, "direct_gravity: bad argument");
+
+    const uint32_t tiles = (n + 63u) / 64u;
+    const uint32_t segs  = std::min(std::min(num_segments ? uint32_t(num_segments) : directSegments(nt, n), tiles), 65535u);
+    const size_t wsBytes = alignUp(size_t(segs) * nt * 4 * size_t(real_bits / 8));
+    CS_TRY(arenaReserve(ctx, wsBytes + 512));
+    void* partial = arenaTake(ctx, wsBytes);
+    int rc        = CSTONE_OK;
+    if (targets)
+    {
+        // an index that is no particle must not reach the loads: looked for on the device, the flag read before the sum
+        int* flag     = (int*)arenaTake(ctx, 256);
+        int bad       = 0;
+        hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), ctx->stream);
+        if (e == hipSuccess)
+        {
+            hipLaunchKernelGGL(checkTargetsKernel, gridFor(nt, 256), 256, 0, ctx->stream, targets, nt, n, flag);
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) rc = fail(ctx, CSTONE_E_HIP, "direct_gravity: %s", hipGetErrorString(e));
+        if (rc == CSTONE_OK) rc = copyToHost(ctx, &bad, flag, sizeof(int));
+        if (rc == CSTONE_OK && bad) rc = fail(ctx, CSTONE_E_ARG, "direct_gravity: a target index is not below n");
+    }
+    if (rc == CSTONE_OK)
+    {
+        StageTimer timer(ctx, CSTONE_STAGE_GRAVITY);
+#define CSTONE_DIRECT(T, Tm)                                                                                           \
+    launchDirect<T, Tm>(ctx, x, y, z, m, h, n, first, targets, nt, segs, G, eps2, partial, ax, ay, az, phi)
+        if (real_bits == 64) rc = mass_bits == 64 ? CSTONE_DIRECT(double, double) : CSTONE_DIRECT(double, float);
+        else rc = mass_bits == 64 ? CSTONE_DIRECT(float, double) : CSTONE_DIRECT(float, float);
+#undef CSTONE_DIRECT
+    }
+    arenaReset(ctx);
+    return rc;
 }
 
 int cstone_hip_upsweep_multipoles_nodes(cstone_hip_ctx* ctx, int real_bits, int num_levels,

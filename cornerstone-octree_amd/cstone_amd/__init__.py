@@ -62,6 +62,9 @@ EXPORTS = [
     # ... on a locally essential tree and on several ranks (csrc/let.hpp, FocusLet::updateMultipoles)
     "cstone_hip_upsweep_multipoles_nodes", "cstone_hip_compute_gravity_let", "cstone_hip_domain_mr_compute_gravity",
     "cstone_hip_domain_mr_multipoles_get",
+    # ... with per-particle softening lengths, and the all-pairs direct sum
+    "cstone_hip_compute_gravity_h", "cstone_hip_compute_gravity_let_h", "cstone_hip_direct_gravity",
+    "cstone_hip_domain_compute_gravity_h", "cstone_hip_domain_mr_compute_gravity_h",
 ]
 
 GRAVITY_GROUP_TOL = 2.0  # CSTONE_GRAVITY_GROUP_TOL: tol_factor of the target groups of cstone_hip_domain_compute_gravity
@@ -570,9 +573,10 @@ class Context:
         return multipoles
 
     def compute_gravity(self, x, y, z, m, first, last, groups, box, child_offsets, internal_to_leaf, layout,
-                        expansion_centers, multipoles, order=2, G=1.0, eps2=0.0, potential=True, counts=False):
+                        expansion_centers, multipoles, order=2, G=1.0, eps2=0.0, potential=True, counts=False, h=None):
         """(ax, ay, az, phi, p2p_counts, m2p_counts) of the targets [first, last) (phi None unless potential, the counts
-        None unless counts); groups: num_groups + 1 indices as compute_group_splits returns them"""
+        None unless counts); groups: num_groups + 1 indices as compute_group_splits returns them; h: per-particle
+        softening lengths laid out like x (cstone_hip_compute_gravity_h), None: Plummer softening with eps2 alone"""
         torch = _torch()
         nt = last - first
 
@@ -582,19 +586,29 @@ class Context:
         ax, ay, az = out(x.dtype), out(x.dtype), out(x.dtype)
         phi = out(x.dtype) if potential else None
         p2p, m2p = (out(torch.int32), out(torch.int32)) if counts else (None, None)
-        self._chk(self.lib.cstone_hip_compute_gravity(
-            self.h, C.c_int(x.element_size() * 8), C.c_int(m.element_size() * 8), _ptr(x), _ptr(y), _ptr(z), _ptr(m),
-            C.c_uint32(first), C.c_uint32(last), _ptr(groups), C.c_uint32(groups.numel() - 1), C.byref(box),
-            _ptr(child_offsets), _ptr(internal_to_leaf), _ptr(layout), _ptr(expansion_centers), _ptr(multipoles),
-            C.c_int(order), C.c_double(G), C.c_double(eps2), _ptr(ax), _ptr(ay), _ptr(az), _ptr(phi), _ptr(p2p),
-            _ptr(m2p)), "compute_gravity")
+        head = (self.h, C.c_int(x.element_size() * 8), C.c_int(m.element_size() * 8), _ptr(x), _ptr(y), _ptr(z), _ptr(m))
+        tail = (C.c_uint32(first), C.c_uint32(last), _ptr(groups), C.c_uint32(groups.numel() - 1), C.byref(box),
+                _ptr(child_offsets), _ptr(internal_to_leaf), _ptr(layout), _ptr(expansion_centers), _ptr(multipoles),
+                C.c_int(order), C.c_double(G), C.c_double(eps2), _ptr(ax), _ptr(ay), _ptr(az), _ptr(phi), _ptr(p2p),
+                _ptr(m2p))
+        if h is None:
+            self._chk(self.lib.cstone_hip_compute_gravity(*head, *tail), "compute_gravity")
+        else:
+            self._check_h(x, h)
+            self._chk(self.lib.cstone_hip_compute_gravity_h(*head, _ptr(h), *tail), "compute_gravity_h")
         return ax, ay, az, phi, p2p, m2p
 
+    @staticmethod
+    def _check_h(x, h):
+        if h.dtype != x.dtype or h.numel() < x.numel():
+            raise CstoneError("h must have the type of the coordinates and an element for every particle")
+
     def compute_gravity_let(self, x, y, z, m, first, last, groups, box, child_offsets, internal_to_leaf, layout,
-                            expansion_centers, multipoles, order=2, G=1.0, eps2=0.0, potential=True, counts=False):
+                            expansion_centers, multipoles, order=2, G=1.0, eps2=0.0, potential=True, counts=False,
+                            h=None):
         """compute_gravity on a locally essential tree (cstone_hip_compute_gravity_let): an opened leaf WITHOUT particles
         is applied as a multipole.  Returns (ax, ay, az, phi, p2p_counts, m2p_counts, let_m2p_counts), the last one the
-        number of such leaves per target (they are counted in m2p_counts too)"""
+        number of such leaves per target (they are counted in m2p_counts too).  h: as in compute_gravity"""
         torch = _torch()
         nt = last - first
 
@@ -604,13 +618,40 @@ class Context:
         ax, ay, az = out(x.dtype), out(x.dtype), out(x.dtype)
         phi = out(x.dtype) if potential else None
         p2p, m2p, let = (out(torch.int32), out(torch.int32), out(torch.int32)) if counts else (None, None, None)
-        self._chk(self.lib.cstone_hip_compute_gravity_let(
-            self.h, C.c_int(x.element_size() * 8), C.c_int(m.element_size() * 8), _ptr(x), _ptr(y), _ptr(z), _ptr(m),
-            C.c_uint32(first), C.c_uint32(last), _ptr(groups), C.c_uint32(groups.numel() - 1), C.byref(box),
-            _ptr(child_offsets), _ptr(internal_to_leaf), _ptr(layout), _ptr(expansion_centers), _ptr(multipoles),
-            C.c_int(order), C.c_double(G), C.c_double(eps2), _ptr(ax), _ptr(ay), _ptr(az), _ptr(phi), _ptr(p2p),
-            _ptr(m2p), _ptr(let)), "compute_gravity_let")
+        head = (self.h, C.c_int(x.element_size() * 8), C.c_int(m.element_size() * 8), _ptr(x), _ptr(y), _ptr(z), _ptr(m))
+        tail = (C.c_uint32(first), C.c_uint32(last), _ptr(groups), C.c_uint32(groups.numel() - 1), C.byref(box),
+                _ptr(child_offsets), _ptr(internal_to_leaf), _ptr(layout), _ptr(expansion_centers), _ptr(multipoles),
+                C.c_int(order), C.c_double(G), C.c_double(eps2), _ptr(ax), _ptr(ay), _ptr(az), _ptr(phi), _ptr(p2p),
+                _ptr(m2p), _ptr(let))
+        if h is None:
+            self._chk(self.lib.cstone_hip_compute_gravity_let(*head, *tail), "compute_gravity_let")
+        else:
+            self._check_h(x, h)
+            self._chk(self.lib.cstone_hip_compute_gravity_let_h(*head, _ptr(h), *tail), "compute_gravity_let_h")
         return ax, ay, az, phi, p2p, m2p, let
+
+    def direct_gravity(self, x, y, z, m, h=None, first=0, last=None, targets=None, num_segments=0, G=1.0, eps2=0.0,
+                       potential=True):
+        """all-pairs direct sum (cstone_hip_direct_gravity): (ax, ay, az, phi) of every source [0, n) on the targets
+        [first, last) (last None: n) or, if targets (int32 tensor of particle indices, any order, duplicates allowed) is
+        given, on those; outputs indexed by target position.  h: per-particle softening lengths or None;
+        num_segments: how many pieces the sources are cut into (0: the library chooses)"""
+        torch = _torch()
+        n = x.numel()
+        last = n if last is None else last
+        if h is not None:
+            self._check_h(x, h)
+        if targets is not None and targets.dtype != torch.int32:
+            raise CstoneError("targets must be an int32 tensor (u32 bit patterns)")
+        nt = targets.numel() if targets is not None else max(0, last - first)
+        ax, ay, az = [torch.zeros(nt, dtype=x.dtype, device=x.device) for _ in range(3)]
+        phi = torch.zeros(nt, dtype=x.dtype, device=x.device) if potential else None
+        self._chk(self.lib.cstone_hip_direct_gravity(
+            self.h, C.c_int(x.element_size() * 8), C.c_int(m.element_size() * 8), _ptr(x), _ptr(y), _ptr(z), _ptr(m),
+            _ptr(h), C.c_uint32(n), C.c_uint32(first), C.c_uint32(last), _ptr(targets),
+            C.c_uint32(targets.numel() if targets is not None else 0), C.c_int(num_segments), C.c_double(G),
+            C.c_double(eps2), _ptr(ax), _ptr(ay), _ptr(az), _ptr(phi)), "direct_gravity")
+        return ax, ay, az, phi
 
 
 _DEFAULT = None

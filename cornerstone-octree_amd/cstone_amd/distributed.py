@@ -308,22 +308,30 @@ class NativeDistributedDomain:
             raise err
         self.ctx._chk(rc, "domain_mr_exchange_halos")
 
-    def gravity(self, x, y, z, m, G=1.0, eps=0.0, order=2, potential=True, exchange_masses=True):
+    def gravity(self, x, y, z, m, G=1.0, eps=0.0, order=2, potential=True, exchange_masses=True, h=None):
         """Barnes-Hut gravity on several ranks (cstone_hip_domain_mr_compute_gravity): (ax, ay, az, phi) laid out like the
         result arrays of the last sync_grav, their assigned range [start, end) filled (phi None unless potential).
         x, y, z, m: laid out like those arrays and read on the halo ranges too.  The sync fills the halo ranges of the
         coordinates but not those of the masses, so the masses' halos are exchanged first (in place) unless
-        exchange_masses is False, in which case the caller has done that.  Collective"""
+        exchange_masses is False, in which case the caller has done that.  h: per-particle softening lengths laid out
+        like x and read on the halo ranges too (cstone_hip_domain_mr_compute_gravity_h); the sync's h has its halo
+        ranges filled already, they travel with x, y, z, so nothing is exchanged for it.  Collective"""
         torch = _torch()
         if exchange_masses:
             self.exchange_halos(m)
         ax, ay, az = [torch.zeros_like(x) for _ in range(3)]
         phi = torch.zeros_like(x) if potential else None
-        rc = self.ctx.lib.cstone_hip_domain_mr_compute_gravity(
-            self.h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(z.data_ptr()),
-            C.c_void_p(m.data_ptr()), C.c_int(m.element_size() * 8), C.c_int(order), C.c_double(G),
-            C.c_double(eps * eps), C.c_void_p(ax.data_ptr()), C.c_void_p(ay.data_ptr()), C.c_void_p(az.data_ptr()),
-            C.c_void_p(phi.data_ptr() if phi is not None else 0))
+        head = (self.h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(z.data_ptr()),
+                C.c_void_p(m.data_ptr()))
+        tail = (C.c_int(m.element_size() * 8), C.c_int(order), C.c_double(G), C.c_double(eps * eps),
+                C.c_void_p(ax.data_ptr()), C.c_void_p(ay.data_ptr()), C.c_void_p(az.data_ptr()),
+                C.c_void_p(phi.data_ptr() if phi is not None else 0))
+        if h is None:
+            rc = self.ctx.lib.cstone_hip_domain_mr_compute_gravity(*head, *tail)
+        else:
+            if h.dtype != x.dtype or h.numel() != x.numel():
+                raise ValueError("h must be laid out like x")
+            rc = self.ctx.lib.cstone_hip_domain_mr_compute_gravity_h(*head, C.c_void_p(h.data_ptr()), *tail)
         if rc != 0 and self.coll.error is not None:
             err, self.coll.error = self.coll.error, None
             raise err

@@ -131,20 +131,26 @@ class Domain:
                                                                      C.c_int(m.element_size() * 8))
         self.ctx._chk(rc, "domain_update_expansion_centers")
 
-    def gravity(self, x, y, z, m, G=1.0, eps=0.0, order=2, potential=True):
+    def gravity(self, x, y, z, m, G=1.0, eps=0.0, order=2, potential=True, h=None):
         """Barnes-Hut gravity on the focus tree (cstone_hip_domain_compute_gravity) after sync_grav /
         update_expansion_centers: (ax, ay, az, phi) of the end_index particles, phi None unless potential; x, y, z, m laid
-        out like the last sync's results"""
+        out like the last sync's results.  h: per-particle softening lengths laid out like x (the sync's h), None: Plummer
+        softening with eps alone"""
         import torch
 
         ne = self.view().end_index
         ax, ay, az = [torch.zeros(ne, dtype=x.dtype, device=x.device) for _ in range(3)]
         phi = torch.zeros(ne, dtype=x.dtype, device=x.device) if potential else None
-        rc = self.ctx.lib.cstone_hip_domain_compute_gravity(
-            self.h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(z.data_ptr()), C.c_void_p(m.data_ptr()),
-            C.c_int(m.element_size() * 8), C.c_int(order), C.c_double(G), C.c_double(float(eps) * float(eps)),
-            C.c_void_p(ax.data_ptr()), C.c_void_p(ay.data_ptr()), C.c_void_p(az.data_ptr()),
-            C.c_void_p(phi.data_ptr() if phi is not None else 0))
+        head = (self.h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(z.data_ptr()),
+                C.c_void_p(m.data_ptr()))
+        tail = (C.c_int(m.element_size() * 8), C.c_int(order), C.c_double(G), C.c_double(float(eps) * float(eps)),
+                C.c_void_p(ax.data_ptr()), C.c_void_p(ay.data_ptr()), C.c_void_p(az.data_ptr()),
+                C.c_void_p(phi.data_ptr() if phi is not None else 0))
+        if h is None:
+            rc = self.ctx.lib.cstone_hip_domain_compute_gravity(*head, *tail)
+        else:
+            self.ctx._check_h(x, h)
+            rc = self.ctx.lib.cstone_hip_domain_compute_gravity_h(*head, C.c_void_p(h.data_ptr()), *tail)
         self.ctx._chk(rc, "domain_compute_gravity")
         return ax, ay, az, phi
 

@@ -681,6 +681,24 @@ void findNeighborsGpu(const T* x, const T* y, const T* z, const T* h, const Grou
  *  (R/domain/domaindecomp_mpi_gpu.cuh:86-185, R/halos/exchange_halos_gpu.cuh:35-119).  One rank obtains the id
  *  (RcclComm::uniqueId) and passes its 128 bytes to the others by whatever means the application has; every rank then
  *  constructs an RcclComm (collective) and hands ops() to Domain / MultiRankDomain. */
+/*! All-pairs direct sum of gravity (cstone_hip_direct_gravity), the arbiter of the tree walk: every particle [0, n) on
+ *  the targets [first, last) or, if targets is not null, on the numTargets particle indices of that device list (any
+ *  order, duplicates allowed); ax, ay, az and phi (nullable) are indexed by target position.  h (nullable): per-particle
+ *  softening lengths, the pair rule of Domain::computeGravity with h; eps: Plummer softening length.  numSegments: how
+ *  many pieces the sources are cut into, 0 = the library chooses.  Open boundaries. */
+template<class T, class Tm>
+void directGravity(const T* x, const T* y, const T* z, const Tm* m, const T* h, LocalIndex n, LocalIndex first,
+                   LocalIndex last, const LocalIndex* targets, LocalIndex numTargets, T G, T eps, T* ax, T* ay, T* az,
+                   T* phi, int numSegments = 0)
+{
+    static_assert(std::is_same_v<T, float> || std::is_same_v<T, double>);
+    static_assert(std::is_same_v<Tm, float> || std::is_same_v<Tm, double>);
+    Context::check(cstone_hip_direct_gravity(Context::get(), int(sizeof(T)) * 8, int(sizeof(Tm)) * 8, x, y, z, m, h, n,
+                                             first, last, targets, numTargets, numSegments, double(G),
+                                             double(eps) * double(eps), ax, ay, az, phi),
+                   "directGravity");
+}
+
 class RcclComm
 {
 public:
@@ -814,6 +832,19 @@ public:
         if (exchangeMasses) exchangeHalos(m);
         Context::check(cstone_hip_domain_mr_compute_gravity(dom_, x, y, z, m, int(sizeof(Tm)) * 8, order, double(G),
                                                             double(eps) * double(eps), ax, ay, az, phi),
+                       "MultiRankDomain::computeGravity");
+    }
+    /*! The same with per-particle softening lengths (cstone_hip_domain_mr_compute_gravity_h): h is laid out like x and
+     *  read on the halo ranges too.  The h array of the last sync has them filled (the sync exchanges x, y, z and h of
+     *  the halos together), so nothing is exchanged for it here; an h recomputed since needs exchangeHalos(h) first. */
+    template<class Tm>
+    void computeGravity(const T* x, const T* y, const T* z, Tm* m, const T* h, T* ax, T* ay, T* az, T* phi, T G, T eps,
+                        int order = 2, bool exchangeMasses = true)
+    {
+        static_assert(std::is_same_v<Tm, float> || std::is_same_v<Tm, double>);
+        if (exchangeMasses) exchangeHalos(m);
+        Context::check(cstone_hip_domain_mr_compute_gravity_h(dom_, x, y, z, m, h, int(sizeof(Tm)) * 8, order, double(G),
+                                                              double(eps) * double(eps), ax, ay, az, phi),
                        "MultiRankDomain::computeGravity");
     }
     //! the multipoles of the focus tree that the last computeGravity built: 8 values of T per node (device), or null
@@ -1151,6 +1182,38 @@ public:
         Context::check(cstone_hip_domain_compute_gravity(dom_, x.data(), y.data(), z.data(), m.data(), int(sizeof(Tm)) * 8,
                                                          order, double(G), double(eps) * double(eps), ax.data(),
                                                          ay.data(), az.data(), phi ? phi->data() : nullptr),
+                       "Domain::computeGravity");
+    }
+    /*! The same with per-particle softening lengths h, laid out like x (the h of the sync's result): a pair closer than
+     *  H = h_i + h_j interacts like a point with a homogeneous sphere of radius H (include/cstone_hip.h,
+     *  compute_gravity_h); eps is added as before.  M2P is not softened. */
+    template<class Tm>
+    void computeGravity(const DeviceVector<T>& x, const DeviceVector<T>& y, const DeviceVector<T>& z,
+                        const DeviceVector<Tm>& m, const DeviceVector<T>& h, DeviceVector<T>& ax, DeviceVector<T>& ay,
+                        DeviceVector<T>& az, DeviceVector<T>* phi, T G, T eps, int order = 2)
+    {
+        static_assert(std::is_same_v<Tm, float> || std::is_same_v<Tm, double>);
+        if (h.size() != x.size()) throw std::runtime_error("Domain computeGravity: h is not laid out like x\n");
+        if (mr_)
+        {
+            const std::size_t nh = mr_->nParticlesWithHalos();
+            ax.resize(nh);
+            ay.resize(nh);
+            az.resize(nh);
+            if (phi) phi->resize(nh);
+            mr_->computeGravity(x.data(), y.data(), z.data(), const_cast<Tm*>(m.data()), h.data(), ax.data(), ay.data(),
+                                az.data(), phi ? phi->data() : nullptr, G, eps, order);
+            return;
+        }
+        const std::size_t ne = endIndex();
+        ax.resize(ne);
+        ay.resize(ne);
+        az.resize(ne);
+        if (phi) phi->resize(ne);
+        Context::check(cstone_hip_domain_compute_gravity_h(dom_, x.data(), y.data(), z.data(), m.data(), h.data(),
+                                                           int(sizeof(Tm)) * 8, order, double(G),
+                                                           double(eps) * double(eps), ax.data(), ay.data(), az.data(),
+                                                           phi ? phi->data() : nullptr),
                        "Domain::computeGravity");
     }
     //! R/domain/domain.hpp:411: stores the flag like the reference does (its member convergeTrees, :661, has no reader

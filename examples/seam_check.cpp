@@ -177,9 +177,56 @@ bool runAll(const char* name, Curve curve)
     DeviceVector<unsigned> nc2(n);
     findNeighborsGpu(xs.data(), ys.data(), zs.data(), hs.data(), gv, box, view, ngmax, nidx.data(), nc2.data());
     expect(toHost(nc2) == brute && gv.numGroups >= fixed.view().numGroups, "computeGroupSplits / findNeighborsGpu over groups");
+
+    // the direct sum of gravity with per-particle softening lengths against the same loop on the host (double)
+    {
+        const T G = T(1), eps = T(0.01);
+        std::vector<T> hm(n);
+        for (std::size_t i = 0; i < n; ++i)
+            hm[i] = T(0.5 + double(i % 7) / 7) / T(n);
+        DeviceVector<T> m(hm.data(), hm.data() + n), ax(n), ay(n), az(n), phi(n);
+        directGravity(xs.data(), ys.data(), zs.data(), m.data(), hs.data(), LocalIndex(n), 0, LocalIndex(n),
+                      static_cast<const LocalIndex*>(nullptr), 0, G, eps, ax.data(), ay.data(), az.data(), phi.data());
+        auto gax = toHost(ax);
+        auto gphi = toHost(phi);
+        auto shh  = toHost(hs);
+        double worst = 0;
+        for (std::size_t i = 0; i < n; i += 37)
+        {
+            double a = 0, p = 0, sa = 0;
+            for (std::size_t j = 0; j < n; ++j)
+            {
+                if (j == i) continue;
+                const double dx = double(sx[j]) - sx[i], dy = double(sy[j]) - sy[i], dz = double(sz[j]) - sz[i];
+                const double r2 = dx * dx + dy * dy + dz * dz + double(eps) * eps, H = double(shh[i]) + shh[j];
+                const double rinv = 1 / std::sqrt(std::max(r2, H * H));
+                const double w    = r2 < H * H ? 1.5 - 0.5 * r2 * rinv * rinv : 1.0;
+                a += hm[j] * rinv * rinv * rinv * dx;
+                sa += std::abs(hm[j] * rinv * rinv * rinv * dx);
+                p -= hm[j] * rinv * w;
+            }
+            worst = std::max({worst, std::abs(gax[i] - a) / sa, std::abs(gphi[i] - p) / std::abs(p)});
+        }
+        expect(worst <= (sizeof(T) == 8 ? 1e-12 : 2e-4), "directGravity");
+    }
     syncGpu();
     std::printf("%s: %s\n", name, ok ? "ok" : "FAILED");
     return ok;
+}
+
+//! Domain::computeGravity and MultiRankDomain::computeGravity with softening lengths, instantiated (not run here:
+//! tests/test_gravity_soft.py runs the entry points behind them)
+template<class KeyType, class T, class Tm>
+void instantiateSoftGravity()
+{
+    using D  = Domain<KeyType, T>;
+    using V  = DeviceVector<T>;
+    using Mr = MultiRankDomain<KeyType, T>;
+    [[maybe_unused]] auto single = static_cast<void (D::*)(const V&, const V&, const V&, const DeviceVector<Tm>&, const V&,
+                                                           V&, V&, V&, V*, T, T, int)>(&D::template computeGravity<Tm>);
+    [[maybe_unused]] auto multi  = static_cast<void (Mr::*)(const T*, const T*, const T*, Tm*, const T*, T*, T*, T*, T*, T,
+                                                           T, int, bool)>(&Mr::template computeGravity<Tm>);
+    [[maybe_unused]] auto direct = &directGravity<T, Tm>;
 }
 
 //! computeContinuumCsarray for the two concentration functions the oracle's reference build can name (oracle/ref_driver.cpp,
@@ -217,6 +264,10 @@ void continuumDigest(const char* name, int kind)
 
 int main()
 {
+    instantiateSoftGravity<std::uint64_t, double, double>();
+    instantiateSoftGravity<std::uint64_t, double, float>();
+    instantiateSoftGravity<std::uint64_t, float, float>();
+    instantiateSoftGravity<std::uint32_t, float, double>();
     continuumDigest<std::uint64_t>("u64", 0);
     continuumDigest<std::uint64_t>("u64", 1);
     continuumDigest<std::uint32_t>("u32", 0);

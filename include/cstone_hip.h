@@ -920,6 +920,42 @@ extern "C"
      *                 domain_mr_compute_gravity built (NULL before the first), and the number of nodes; the tree itself
      *                 and its expansion centres come from cstone_hip_domain_mr_octree_get (which, in halo mode
      *                 CSTONE_MR_HALOS_LET, describes the focus tree).  Valid until the next sync.
+     * compute_gravity_h, compute_gravity_let_h : the two walks with per-particle softening lengths h (real_bits, one per
+     *                 particle, indexed like x by the ABSOLUTE particle index -- not by i - first -- and read for every
+     *                 source, on halo ranges too).  ONE pair rule, shared with direct_gravity, for target i and source
+     *                 j != i (index inequality): d = r_j - r_i, r2 = |d|^2 + eps2, H = h_i + h_j, s2 = max(r2, H H),
+     *                 rinv = 1 / sqrt(s2), w = r2 < H H ? 1.5 - 0.5 r2 rinv^2 : 1;  a_i += G m_j rinv^3 d,
+     *                 phi_i -= G m_j rinv w.  That is the field of a homogeneous sphere of radius H: inside, the force is
+     *                 linear in d and phi = -G m (3 H^2 - r2) / (2 H^3); both are continuous at r2 = H^2, the force is
+     *                 minus the gradient of phi, and the rule is symmetric in i and j.  Coincident particles with H > 0
+     *                 add no force and -3 G m / (2 H) to phi.  M2P is unchanged (eps2 only), and so are the MAC, the walk
+     *                 and both counts.  h == NULL: the bits of compute_gravity / compute_gravity_let, which forward here;
+     *                 h == 0 everywhere: the same bits as well.  A NaN in h does not surface: r2 < H H is then false and
+     *                 the pair takes the Plummer branch.  Everything else as for the h-free calls.
+     * direct_gravity : the all-pairs sum of the same pair rule, the arbiter of the walks: every source j in [0, n) on
+     *                 every target, the target itself skipped.  Targets: the range [first, last) of [0, n], or, if
+     *                 targets != NULL, the num_targets particle indices of that DEVICE list (u32, any order, duplicates
+     *                 allowed; first / last are then ignored).  ax, ay, az, phi (nullable) are indexed by TARGET
+     *                 POSITION (i - first, or the position in the list) and overwritten.  h nullable as above.  No box:
+     *                 open boundaries only.  One wave per 64 targets; the sources are cut into num_segments contiguous
+     *                 runs of 64-particle tiles that different workgroups sum (so that a few thousand targets still fill
+     *                 the device), the partial sums go to the context's workspace (num_segments * targets * 4 reals) and
+     *                 are added in segment order: no atomics, the same bits from call to call for the same arguments.
+     *                 num_segments > 0 is taken as given, clipped to ceil(n / 64) (and 65535); num_segments == 0:
+     *                 min(ceil(1024 / ceil(targets / 256)), ceil(n / 64) / 8), at least 1 -- enough workgroups of 256
+     *                 targets for 16 waves on each of 256 CUs, and no segment shorter than 8 tiles; the choice depends
+     *                 on the shapes alone, not on the device.  Results for different num_segments differ by rounding.
+     *                 CSTONE_E_ARG, with nothing written: bad bits, eps2 < 0, num_segments < 0, last < first or
+     *                 last > n, n > 2^32 - 65, a NULL array with targets to compute, a target index >= n (the list is
+     *                 checked on the device before the sum, which costs one synchronisation of the stream; a range
+     *                 costs none).  Asynchronous on the context's stream otherwise.
+     * domain_compute_gravity_h, domain_mr_compute_gravity_h : the domains' calls with h (nullable), laid out like x --
+     *                 the h array of the sync's result.  Same refusals, decided at the same place (on several ranks
+     *                 before any collective).  On several ranks h is read ON THE HALO RANGES TOO, and unlike the masses
+     *                 the sync's h has them filled: the sync exchanges x, y, z and h of the halos in one message
+     *                 (csrc/domain_mr.hip, C5; R/domain/domain.hpp exchangeHalos(x, y, z, h)), so no exchange is needed
+     *                 for the h that a sync returned; an h the caller recomputed afterwards on its assigned range needs
+     *                 _exchange_halos(h) first, like any other field.
      * ------------------------------------------------------------------------------------------- */
 #define CSTONE_GRAVITY_GROUP_TOL 2.0f
     int cstone_hip_upsweep_multipoles(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
@@ -950,6 +986,30 @@ extern "C"
                                              const void* m, int mass_bits, int order, double G, double eps2, void* ax,
                                              void* ay, void* az, void* phi);
     int cstone_hip_domain_mr_multipoles_get(cstone_hip_domain_mr* dom, const void** multipoles, int32_t* num_nodes);
+    int cstone_hip_compute_gravity_h(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
+                                     const void* z, const void* m, const void* h, uint32_t first, uint32_t last,
+                                     const uint32_t* groups, uint32_t num_groups, const cstone_box* box_host,
+                                     const int32_t* child_offsets, const int32_t* internal_to_leaf,
+                                     const uint32_t* layout, const void* expansion_centers, const void* multipoles,
+                                     int order, double G, double eps2, void* ax, void* ay, void* az, void* phi,
+                                     uint32_t* p2p_counts, uint32_t* m2p_counts);
+    int cstone_hip_compute_gravity_let_h(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
+                                         const void* z, const void* m, const void* h, uint32_t first, uint32_t last,
+                                         const uint32_t* groups, uint32_t num_groups, const cstone_box* box_host,
+                                         const int32_t* child_offsets, const int32_t* internal_to_leaf,
+                                         const uint32_t* layout, const void* expansion_centers, const void* multipoles,
+                                         int order, double G, double eps2, void* ax, void* ay, void* az, void* phi,
+                                         uint32_t* p2p_counts, uint32_t* m2p_counts, uint32_t* let_m2p_counts);
+    int cstone_hip_direct_gravity(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
+                                  const void* z, const void* m, const void* h, uint32_t n, uint32_t first, uint32_t last,
+                                  const uint32_t* targets, uint32_t num_targets, int num_segments, double G, double eps2,
+                                  void* ax, void* ay, void* az, void* phi);
+    int cstone_hip_domain_compute_gravity_h(cstone_hip_domain* dom, const void* x, const void* y, const void* z,
+                                            const void* m, const void* h, int mass_bits, int order, double G,
+                                            double eps2, void* ax, void* ay, void* az, void* phi);
+    int cstone_hip_domain_mr_compute_gravity_h(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z,
+                                               const void* m, const void* h, int mass_bits, int order, double G,
+                                               double eps2, void* ax, void* ay, void* az, void* phi);
 
 #ifdef __cplusplus
 }

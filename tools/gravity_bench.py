@@ -14,7 +14,18 @@ essential tree (with its exchanges, which a single rank skips) and mr_walk_ms th
 stage timers, mr_call_ms the whole call between device events.  The single-rank figures of the same process stand
 beside them in the same line.
 
-    python tools/gravity_bench.py [--sizes 1e6 1e7] [--clouds plummer uniform] [--reals 64 32] [--reps 5] [--mr]
+With --h the walk is also timed with per-particle softening lengths (cstone_hip_compute_gravity_h, h = the smoothing
+lengths of the cloud as the sync returned them): walk_h_ms beside walk_ms.  A softened pair costs 29 FLOP by the same
+convention (H 1, H^2 1, 1/r^2 1, w 4, phi 1 more than the 21).
+
+With --direct-sample K the all-pairs direct sum (cstone_hip_direct_gravity) of K sampled targets against the whole cloud
+is timed (direct_ms, direct_pairs_per_s, direct_flop_per_s and its share of the vector FP peak of the precision, FMA
+counted as two operations as in DESIGN section 7d -- this code issues none, so 0.5 is its ceiling), and the walk's
+relative errors against it on those targets are printed (median / p99 of |da| and |dphi|, orders 0 and 2); with --h the
+same for the softened walk against the softened direct sum.
+
+    python tools/gravity_bench.py [--sizes 1e6 1e7] [--clouds plummer uniform] [--reals 64 32] [--reps 5] [--mr] [--h]
+                                  [--direct-sample K]
 """
 import argparse
 import json
@@ -26,6 +37,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "cornerstone-octree_amd"))
 
 P2P_FLOP, M2P_FLOP = 21, 54
+P2P_SOFT_FLOP = 29
+PEAK_FLOPS = {64: 78.6e12, 32: 157.3e12}  # AMD's specification of the MI355X, vector units, an FMA counted as two
 
 
 def main():
@@ -37,6 +50,9 @@ def main():
     p.add_argument("--reps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--mr", action="store_true", help="also time the multi-rank route on a world of one rank")
+    p.add_argument("--h", action="store_true", help="also time the walk with per-particle softening lengths")
+    p.add_argument("--direct-sample", type=int, default=0, metavar="K",
+                   help="time the direct sum of K sampled targets and print the walk's error against it")
     a = p.parse_args()
 
     import numpy as np
@@ -105,6 +121,39 @@ def main():
                 p2p_mean, m2p_mean = p2p.double().mean().item(), m2p.double().mean().item()
                 inter = (p2p_mean + m2p_mean) * ne
                 flop = (p2p_mean * P2P_FLOP + m2p_mean * M2P_FLOP) * ne
+                soft = {}
+                if a.h:
+                    walk_h = lambda: ctx.compute_gravity(x, y, z, m, 0, ne, groups, v.box, child, itl, layout, centers,
+                                                         mp, order=2, potential=True, h=h)  # noqa: E731
+                    walk_h_ms, walk_h_min = timed(walk_h)
+                    soft = dict(walk_h_ms=round(walk_h_ms, 3), walk_h_ms_min=round(walk_h_min, 3),
+                                walk_h_over_walk=round(walk_h_ms / walk_ms, 3))
+                if a.direct_sample:
+                    K = min(a.direct_sample, ne)
+                    tg = torch.randperm(ne, device="cuda", generator=torch.Generator("cuda").manual_seed(5))[:K].int()
+                    pick = tg.long()
+
+                    def errors(hh):
+                        ref = ctx.direct_gravity(x, y, z, m, hh, targets=tg)
+                        ra = torch.stack(ref[:3], 1)
+                        out = {}
+                        for order in (0, 2):
+                            got = ctx.compute_gravity(x, y, z, m, 0, ne, groups, v.box, child, itl, layout, centers, mp,
+                                                      order=order, potential=True, h=hh)
+                            e = (torch.stack(got[:3], 1)[pick] - ra).norm(dim=1) / ra.norm(dim=1)
+                            ep = (got[3][pick] - ref[3]).abs() / ref[3].abs()
+                            out[f"order{order}"] = [float(f"{t.double().quantile(q).item():.3g}") for t in (e, ep)
+                                                    for q in (0.5, 0.99)]
+                        return out
+
+                    for key, hh, per_pair in (("direct", None, P2P_FLOP),) + ((("direct_h", h, P2P_SOFT_FLOP),) if a.h else ()):
+                        d_ms, d_min = timed(lambda: ctx.direct_gravity(x, y, z, m, hh, targets=tg))
+                        pairs = float(K) * float(ne)
+                        soft.update({f"{key}_targets": K, f"{key}_ms": round(d_ms, 3), f"{key}_ms_min": round(d_min, 3),
+                                     f"{key}_pairs_per_s": float(f"{pairs / (d_ms * 1e-3):.4g}"),
+                                     f"{key}_flop_per_s": float(f"{pairs * per_pair / (d_ms * 1e-3):.4g}"),
+                                     f"{key}_share_of_fp_peak": round(pairs * per_pair / (d_ms * 1e-3) / PEAK_FLOPS[rb], 4),
+                                     f"walk_vs_{key}": errors(hh)})
                 mr = {}
                 if a.mr:
                     x0, y0, z0, h0, _ = make_cloud(cloud, n, n, "cuda", dt, 7)
@@ -124,7 +173,7 @@ def main():
                               mr_multipoles_ms=round(mp_ms / a.reps, 4), mr_walk_ms=round(wk_ms / max(wk_cnt, 1), 3))
                     del mdom, r, x0, y0, z0, h0, m0
                 print(json.dumps(dict(
-                    n=n, cloud=cloud, real_bits=rb, theta=a.theta, leaves=L, groups=int(groups.numel() - 1), **mr,
+                    n=n, cloud=cloud, real_bits=rb, theta=a.theta, leaves=L, groups=int(groups.numel() - 1), **mr, **soft,
                     upsweep_ms=round(up_ms, 4), walk_ms=round(walk_ms, 3), walk_ms_min=round(walk_min, 3),
                     p2p_per_target=round(p2p_mean, 1), m2p_per_target=round(m2p_mean, 1),
                     interactions_per_s=float(f"{inter / (walk_ms * 1e-3):.4g}"),
