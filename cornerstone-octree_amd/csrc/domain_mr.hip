@@ -2,16 +2,15 @@
 // all device work live here; the three collectives come from the host application through cstone_hip_comm_ops.
 //
 //   C1  global box            makeGlobalBox (R/sfc/box_mpi.hpp:85-121): local min/max, all_reduce(MIN) of (lo, -hi)
-//   C2  global tree           GlobalAssignment (R/domain/assignment.hpp:42-103): spanning tree of numRanks segments,
-//                             updateOctreeGlobal = rebalance + recount + all_reduce(SUM) (R/tree/update_mpi.hpp:71-94)
-//       assignment            uniformBins / makeSfcAssignment / limitBoundaryShifts (R/domain/domaindecomp.hpp:50-172)
+//   C2  global tree           GlobalAssignment (R/domain/assignment.hpp:42-103): updateOctreeGlobal = rebalance + recount +
+//                             all_reduce(SUM) (R/tree/update_mpi.hpp:71-94); uniformBins / makeSfcAssignment /
+//                             limitBoundaryShifts (R/domain/domaindecomp.hpp:50-172)
 //   C3  particle exchange     createSendRanges (:218-230) on the sorted keys; the fields are NOT reordered first
-//                             (assignment.hpp:121-127): leaving particles are packed through the ordering as
-//                             (x,y,z,h) rows, ONE all_to_all_v; newcomers are sorted among themselves and merged into
-//                             the kept, already sorted range instead of the second full sort of assignment.hpp:156
-//   C4  halo discovery        owner side: every rank exports the radius-dilated boxes of its boundary leaves
-//                             (all_gather), each owner marks the leaves of its own tree that a foreign box touches
+//                             (assignment.hpp:121-127): ONE all_to_all_v of (x,y,z,h) rows; newcomers are merged into the
+//                             kept, already sorted range instead of the second full sort of assignment.hpp:156
+//   C4  halo discovery        on the locally essential tree (let.hpp) or on the owner's side
 //   C5  halo exchange         ONE all_to_all_v of packed rows
+// The stages of a sync, with their collectives and read-backs: DESIGN.md section 2c.
 // Result: [halos of lower ranks | assigned, SFC sorted | halos of higher ranks] in domain-owned arrays.
 // Box, SFC ranges, global tree and the assigned particles are bit-identical to the reference Domain under MPI
 // (tests/golden/ref_domain_mpi_*.npz); the halo set is compared there as well.
@@ -344,6 +343,9 @@ __global__ __launch_bounds__(256) void fillIndicesKernel(const int32_t* __restri
         out[o + (j - a)] = j - base;
 }
 
+//! the element sizes gatherGpu is instantiated for (R/primitives/primitives_gpu.cu:126-148)
+constexpr bool gatherableElement(int e) { return e == 1 || e == 2 || e == 4 || e == 8 || e == 12 || e == 16 || e == 24 || e == 32; }
+
 //! one set of result arrays
 constexpr int MAX_PROPS = 16;
 struct Out
@@ -419,18 +421,11 @@ public:
      *  of 1, 2, 4, 8, 12, 16, 24 or 32 bytes); its assigned range is read, its halo ranges are overwritten. */
     int exchangeHalos(void* array, int elemBytes) override
     {
-        // the element sizes gatherGpu is instantiated for (R/primitives/primitives_gpu.cu:126-148)
-        if (elemBytes != 1 && elemBytes != 2 && elemBytes != 4 && elemBytes != 8 && elemBytes != 12 && elemBytes != 16 &&
-            elemBytes != 24 && elemBytes != 32)
-            return fail(ctx_, CSTONE_E_ARG, "exchange_halos: element size %d", elemBytes);
+        if (!gatherableElement(elemBytes)) return fail(ctx_, CSTONE_E_ARG, "exchange_halos: element size %d", elemBytes);
         if (firstCall_) return fail(ctx_, CSTONE_E_ARG, "exchange_halos: no sync yet");
         if (useLet_) return let_->exchangeHalos(array, elemBytes);
-        uint64_t any = 0;
-        for (int p = 0; p < P_; ++p)
-            any += haloSend_[p] + haloRecv_[p];
         // every rank must take part if anybody exchanges: the totals of the last sync's count matrix decide
         if (P_ == 1 || haloAnyLast_ == 0) return CSTONE_OK;
-        (void)any;
         char* a = static_cast<char*>(array);
         std::vector<size_t> sb(P_), rb(P_);
         for (int p = 0; p < P_; ++p)
@@ -457,9 +452,7 @@ public:
      *  (num_particles_with_halos elements), only its assigned range is written (exchangeHalos fills the rest). */
     int reapplySync(const void* in, size_t n, int elemBytes, void* out) override
     {
-        if (elemBytes != 1 && elemBytes != 2 && elemBytes != 4 && elemBytes != 8 && elemBytes != 12 && elemBytes != 16 &&
-            elemBytes != 24 && elemBytes != 32)
-            return fail(ctx_, CSTONE_E_ARG, "reapply_sync: element size %d", elemBytes);
+        if (!gatherableElement(elemBytes)) return fail(ctx_, CSTONE_E_ARG, "reapply_sync: element size %d", elemBytes);
         if (firstCall_) return fail(ctx_, CSTONE_E_ARG, "reapply_sync: no sync yet");
         if (n != rsN_) // checkSizesEqual(prevBufDesc_.size, arrays...), R/domain/domain.hpp:341
             return fail(ctx_, CSTONE_E_ARG, "reapply_sync: array of %zu elements, the last sync took %zu", n, size_t(rsN_));
@@ -470,13 +463,7 @@ public:
         const void* recvSorted = nullptr;
         if (rsMoved_)
         {
-            std::vector<size_t> sb(P_, 0), rbv(P_, 0);
-            for (int p = 0; p < P_; ++p)
-            {
-                if (p == rank_) continue;
-                sb[p]  = rsSendCounts_[p] * e;
-                rbv[p] = rsRecvCounts_[p] * e;
-            }
+            const std::vector<size_t> sb = peerBytes(rsSendCounts_.data(), 1, e), rbv = peerBytes(rsRecvCounts_.data(), 1, e);
             // 32-byte elements are moved as 16-byte vectors: keep every staging buffer 16-byte aligned (DevBuf is)
             CS_TRY(sendRows_.ensure(ctx_, std::max<size_t>(rsSend_, 1) * e));
             CS_TRY(recvRows_.ensure(ctx_, std::max<size_t>(rsNb_, 1) * e));
@@ -631,808 +618,823 @@ public:
         return CSTONE_OK;
     }
 
-    /*! Domain::sync on several ranks (R/domain/domain.hpp:196-243).  Phases, in the order of the tick() marks:
-     *    1  global box (min/max + all-reduce)                      R/sfc/box_mpi.hpp:85-121
-     *    2  keys + SFC ordering of the present particles            R/domain/assignment.hpp:81-86
-     *    3  global tree update + counts all-reduce, SFC assignment  R/domain/assignment.hpp:88-103
-     *    4  send ranges, particle all-to-all, merge of the newcomers, every field written once to its final slot
-     *                                                               R/domain/assignment.hpp:105-158, domaindecomp_mpi.hpp:86-174
-     *    5  this rank's finest tree over its assigned particles, range boundaries enforced, linked octree
-     *    6  owner-side halo discovery (boxes all-gathered, one traversal for all peers), halo count matrix
-     *    7  room for the halos left and right of the assigned block
-     *    8  halo all-to-all, keys of the halo particles             R/halos/halos.hpp:224-257
-     *  then the bookkeeping reapplySync / exchangeHalos / octree() work from. */
-    int sync(const void* xIn, const void* yIn, const void* zIn, const void* hIn, size_t n, const void* const* propsIn,
-             const int* propBytesIn, int numPropsIn, const void* keysIn, const void* mass, int massBits) override
+    /*! Domain::sync on several ranks (R/domain/domain.hpp:196-243): a list of stages that share one SyncState.  What
+     *  each stage decides, which collective and which read-back it issues and where the status word rides: DESIGN.md,
+     *  section 2c.  The tick() marks are the phases CSTONE_MR_TIMING reports. */
+    int sync(const void* x, const void* y, const void* z, const void* h, size_t n, const void* const* props,
+             const int* propBytes, int numProps, const void* keysIn, const void* mass, int massBits) override
     {
-        // syncGrav: the masses travel as one more property behind the caller's
-        const bool grav = massBits != 0;
-        const void* propList[MAX_PROPS + 1];
-        int propSizes[MAX_PROPS + 1];
-        const void* const* props = propsIn;
-        const int* propBytes     = propBytesIn;
-        int numProps             = numPropsIn;
-        if (grav)
-        {
-            if (!useLet_) return fail(ctx_, CSTONE_E_ARG, "domain_mr_sync_grav: needs the locally essential tree (CSTONE_MR_HALOS_LET)");
-            if ((massBits != 32 && massBits != 64) || massBits > rb || (n && !mass) || numPropsIn < 0 || numPropsIn >= MAX_PROPS)
-                return fail(ctx_, CSTONE_E_ARG, "domain_mr_sync_grav: masses of 32 or 64 bits (not wider than the coordinates), "
-                                                "at most %d further properties", MAX_PROPS - 1);
-            for (int q = 0; q < numPropsIn; ++q)
-                propList[q] = propsIn[q], propSizes[q] = propBytesIn[q];
-            propList[numPropsIn] = mass, propSizes[numPropsIn] = massBits / 8;
-            props = propList, propBytes = propSizes, numProps = numPropsIn + 1;
-        }
-        // A rank-local failure must reach the peers: they are about to enter the collectives of this sync and would wait
-        // there for ever.  Failures of the arguments (and the failures injected by the tests, CSTONE_MR_FAIL_AT) are
-        // therefore kept as a pending status; the rank goes on as an EMPTY rank, the status word rides on the next
-        // collective (box all-reduce, count all-gathers) and every rank returns an error behind it.
-        pending_ = 0, toggled_ = false;
-        if (placeForked_)
-        {
-            // (a sync that was abandoned behind its fork: whatever it left on the second stream comes first)
-            CS_HIP(ctx_, hipStreamWaitEvent(ctx_->stream, ctx_->evJoin, 0));
-            placeForked_ = false;
-        }
-        ctx_->auxBusy = false;
-        if (numProps < 0 || numProps > MAX_PROPS) setPending(CSTONE_E_ARG, "domain_mr_sync: at most %d properties", MAX_PROPS);
-        for (int q = 0; q < numProps && !pending_; ++q)
-        {
-            const int e = propBytes[q]; // the element sizes gatherGpu is instantiated for (R/primitives/primitives_gpu.cu:126-148)
-            const bool sizeOk = e == 1 || e == 2 || e == 4 || e == 8 || e == 12 || e == 16 || e == 24 || e == 32;
-            if ((n && !props[q]) || !sizeOk) // an empty rank may pass null arrays
-                setPending(CSTONE_E_ARG, "domain_mr_sync: property %d must have elements of 1, 2, 4, 8, 12, 16, 24 or 32 bytes", q);
-        }
-        const T* x = static_cast<const T*>(xIn);
-        const T* y = static_cast<const T*>(yIn);
-        const T* z = static_cast<const T*>(zIn);
-        const T* h = static_cast<const T*>(hIn);
-        if (n >= (size_t(1) << 30)) setPending(CSTONE_E_ARG, "domain_mr_sync: too many particles per rank");
-        injectFailure("start");
-        if (pending_)
-        {
-            if (P_ == 1) return agreed(rank_);
-            n = 0, numProps = 0; // limp on as an empty rank until the peers know
-        }
-        CS_TRY(scal_.ensure(ctx_, 4096 + size_t(P_) * (P_ + 1) * 8 + size_t(P_ + 1) * 16));
-        ++syncs_;
+        SyncState s{static_cast<const T*>(x), static_cast<const T*>(y), static_cast<const T*>(z), static_cast<const T*>(h),
+                    n, keysIn, props, propBytes, numProps, massBits};
+        CS_TRY(beginSync(s, mass));
         tick(nullptr);
-
-        // ---- the box.  Measuring it costs a pass over x, y, z and a round trip before the first key can be computed.
-        //      A sync that is going to re-sort (below) computes its keys with the box of the previous sync instead and
-        //      measures the extents in the same pass; the all-reduce of the extents follows the encode, the result comes
-        //      back with the re-sort's counters, and only a box that really changed costs a second encode (with the
-        //      radix path, as every key changes then).  After such a sync the extents are measured first again until a
-        //      sync finds the box unchanged (an open box whose outermost particles move changes every time).
-        //      The box all-reduce stays the first collective of the sync on every rank either way.
-        const bool anyOpen = !(box_.bc[0] == 1 && box_.bc[1] == 1 && box_.bc[2] == 1);
-        const bool boxSame = sameLimits(box_, layoutBox_);
-        const int tileLeavesSpec = LeafResort<K>::leavesPerTile(bucketFocus_);
-        // What the re-sort of THIS sync starts from: the leaves of my range and their layout as the last COMPLETED sync
-        // left them.  The members are invalidated here and set again only at the end of the tree update below: a sync
-        // that fails half way (a peer's failure, an unmatched halo ...) may have rebalanced, swapped or freed the
-        // buffers resortTree_ points into, and the retry must then sort from scratch instead of reading them.
-        const K* const resortTree       = resortTree_;
-        const int resortLeaves          = resortLeaves_;
-        const uint64_t layoutParticles  = layoutParticles_;
-        resortTree_ = nullptr, resortLeaves_ = 0, layoutParticles_ = 0;
-        bool speculate = anyOpen && !firstCall_ && !measureFirst_ && !pending_ && boxSame && n >= resortMinParticles() &&
-                         n == layoutParticles && tileLeavesSpec > 0 && resortLeaves > 0 && resortBackoff_ == 0 &&
-                         mayResort(sortMode_) && speculativeBox_; // (CSTONE_NO_SPECULATIVE_BOX: read once, in the
-                                                                   //  constructor; the single-rank path reads it per sync)
-        if (!speculate)
-        {
-            const cstone_box before = box_;
-            CS_TRY(updateBox(x, y, z, n));
-            if (!firstCall_ && anyOpen) measureFirst_ = !sameLimits(box_, before);
-        }
+        CS_TRY(chooseBox(s));
         tick("1 box");
-
-        // ---- keys + SFC ordering of the present particles
-        const size_t nAlloc = std::max<size_t>(n, 64);
-        CS_TRY(keys_.ensure(ctx_, nAlloc * sizeof(K)));
-        CS_TRY(order_.ensure(ctx_, nAlloc * sizeof(uint32_t)));
-        CS_TRY(ensureSortScratch(nAlloc));
-        // encode leaves entries that hold the remove marker 2^(3 maxLevel) alone (R/sfc/sfc.hpp:284-291): such particles
-        // sort behind the end of the curve and leave the domain
-        // (without a key array from the caller there are no markers: the key buffer is then pure output)
-        if (keysIn && n)
-            CS_HIP(ctx_, hipMemcpyAsync(keys_.p, keysIn, n * sizeof(K), hipMemcpyDeviceToDevice, ctx_->stream));
-        bool partialSort = false;
-        // the level ranges of the previous sync's tree (copied to the pinned block behind its build, many stream
-        // synchronisations ago): refreshed at EVERY sync -- buildFocusOctree() bounds its digit passes by it, also on
-        // the syncs that re-sort
-        if (levelRangePending_)
-        {
-            prevMaxLeafLevel_  = deepestLevel<K>(hostLevelRange_);
-            levelRangePending_ = false;
-        }
-        // ---- the incremental re-sort (resort.hpp), as in the single-rank domain: the input arrays are the assigned block
-        //      the previous sync handed out, ordered by the leaves of this rank's tree (layout_); particles still inside
-        //      their leaf are ordered leaf by leaf, the others are binned.  Rank-local: no collective depends on it.
-        bool resorted         = false;
-        bool boxChecked       = false;
-        const int tileLeaves  = LeafResort<K>::leavesPerTile(bucketFocus_);
-        const bool sameBox    = sameLimits(box_, layoutBox_); // (box_ may be a freshly measured one by now)
-        const size_t resortMin = resortMinParticles();
-        const bool tryResort = !firstCall_ && n >= resortMin && n == layoutParticles && tileLeaves > 0 && sameBox && resortLeaves > 0 &&
-                               resortBackoff_ == 0 && !pending_ && mayResort(sortMode_);
-        if (resortBackoff_ > 0) --resortBackoff_;
-        if (tryResort)
-        {
-            CS_TRY(resort_.prepare(ctx_, resortTree, layout_.as<uint32_t>(), resortLeaves, n, keysAlt_.as<K>(),
-                                   lastMovers_ > 100000));
-            const ResortArgs<K> ra = resort_.args();
-            bool done              = false;
-            T* extentsDev = reinterpret_cast<T*>(scal_.as<char>() + 256); // {min, max} per axis, measured by the encode
-            CS_TRY(computeKeysResort(ctx_, curve_, kb, rb, x, y, z, keysIn ? keys_.p : nullptr, n, box_, &ra,
-                                     speculate ? extentsDev : nullptr, &done));
-            bool boxHolds = true, foundHere = false;
-            int counters[4] = {0, 0, 0, 0};
-            if (speculate)
-            {
-                boxChecked = true;
-                // (the keys above were computed with the box of the previous sync: was it still the box?)
-                double* dev = scal_.as<double>();
-                if (done)
-                {
-                    CS_TRY(resort_.binMovers(ctx_, tileLeaves));
-                    // (the re-sort's counters and this rank's status word become part of the operand: one launch, and
-                    //  one copy and one synchronisation bring the reduced extents and the counters)
-                    CS_TRY(extentsToReduceOperand(ctx_, rb, extentsDev, dev, statusWord(), ctx_->devScalars + RESORT_SCALARS));
-                    foundHere = true;
-                }
-                else
-                {
-                    const void* arrays[3] = {x, y, z};
-                    CS_TRY(minMaxCoordinatesDev(ctx_, rb, arrays, 3, n, dev));
-                }
-                cstone_box next;
-                CS_TRY(reduceBox(dev, &next, foundHere, foundHere ? counters : nullptr));
-                boxHolds = sameLimits(next, box_);
-                if (!boxHolds)
-                {
-                    box_          = next;
-                    measureFirst_ = true;
-                    ++boxRedos_;
-                }
-            }
-            else if (done) { CS_TRY(resort_.binMovers(ctx_, tileLeaves)); }
-            if (done && boxHolds)
-            {
-                int found[4];
-                if (foundHere) { std::copy(counters, counters + 4, found); }
-                else { CS_TRY(toHost(found, ctx_->devScalars + RESORT_SCALARS, sizeof found)); }
-                const uint32_t markers = uint32_t(found[0]), J = uint32_t(found[2]), movers = uint32_t(found[3]);
-                if (resortAccepted(found[1], movers, n))
-                {
-                    CS_TRY(resort_.sortLeaves(ctx_, keysAlt_.as<K>(), keys_.as<K>(), order_.as<uint32_t>(), movers, markers,
-                                              J, tileLeaves, (found[1] & RESORT_LARGE_QUIET_TILES) != 0));
-                    resorted    = true;
-                    lastMovers_ = movers;
-                    ++resorts_;
-                }
-                else { resortBackoff_ = RESORT_BACKOFF_SYNCS; } // (not counted here, unlike the single-rank path)
-            }
-        }
-        if (speculate && !boxChecked)
-        {
-            // (cannot happen: the conditions of the speculation are those of the attempt above; a box is never left unmeasured)
-            CS_TRY(updateBox(x, y, z, n));
-        }
-        if (n && !resorted)
-        {
-            // radix passes only over the digits above the leaf level (+1) of the previous tree, runs of equal high digits
-            // are finished by a fix-up pass; a run that is too long raises a flag and the regular sort completes the job
-            int startPass = 0;
-            // (the deepest level: as the last read of the pinned block left it; the single-rank path keeps the whole array)
-            if (!firstCall_ && prevMaxLeafLevel_ >= 0 && !allDigits(sortMode_))
-                startPass = partialSortStartPass<K>(prevMaxLeafLevel_, bucketFocus_);
-            int* tooLong = reinterpret_cast<int*>(scal_.as<char>() + 128);
-            CS_TRY(sfcKeysAndOrderingHint(ctx_, curve_, kb, rb, x, y, z, keys_.p, order_.as<uint32_t>(), n, box_,
-                                          keysAlt_.p, orderAlt_.as<uint32_t>(), sortTmp_.p, sortTmp_.bytes, startPass,
-                                          tooLong, keysIn != nullptr));
-            // the flag travels to the (pinned) host block behind the sort; the read-back of the global tree update below
-            // completes the stream, so no synchronisation of its own is needed (the global leaf boundaries cannot fall
-            // inside a run: the update is not affected by an unfinished order)
-            partialSort = startPass > 0;
-            if (partialSort)
-                CS_TRY(copyToPinned(ctx_, ctx_->hostScalars + 3, tooLong, sizeof(int)));
-        }
-
+        CS_TRY(reserveSortBuffers(s));
+        takeLevelRanges();
+        CS_TRY(tryResort(s));
+        CS_TRY(encodeAndSort(s));
         tick("2 encode+sort");
-        CS_TRY(updateGlobalTree(n));
-        // (counts, and the leaf array when the device made it; room behind them for the cut points and the count matrix)
-        CS_TRY(gHost_.queueReadBack(ctx_, gTree_, gCounts_, gLeaves_, !gLeavesOnHost_, size_t(P_ + 1) * (P_ + 2) * 8 + 1024));
-
-        // ---- C3 (first half): send ranges on the sorted keys and the counts of everybody.  The assignment follows from
-        //      the global counts that are on their way to the host; it rarely changes from one sync to the next (a
-        //      boundary moves by whole leaves of the global tree), so the cut points for the assignment of the LAST sync
-        //      are computed and all-gathered right behind the counts, and ONE read-back brings global counts, cut points
-        //      and count matrix.  Only a sync whose assignment did change asks again.  (A partially sorted key array --
-        //      runs of equal high digits still to be fixed up -- answers these searches correctly: an assignment boundary
-        //      is a leaf boundary of the global tree and cannot fall inside a run.)
-        std::vector<uint64_t> cut(P_ + 1);
-        std::vector<uint64_t> sendCounts(P_), matrix(size_t(P_) * P_, 0);
-        std::vector<uint64_t> rows(size_t(P_) * (P_ + 1), 0);
-        std::vector<K> cutKeys; // the assignment the queued cut points belong to
-        uint64_t *pinRows = nullptr, *pinCut = nullptr;
-        auto queueCuts = [&](const std::vector<K>& asg) -> int
-        {
-            cutKeys      = asg;
-            K* dq        = reinterpret_cast<K*>(scal_.as<char>() + 2048);
-            uint64_t* dr = reinterpret_cast<uint64_t*>(scal_.as<char>() + 2048 + size_t(P_ + 1) * 8);
-            CS_TRY(cstone_hip_upload(ctx_, dq, asg.data(), size_t(P_ + 1) * sizeof(K)));
-            // the send counts go from the device into the all-gather; word P of every row: the status of that rank
-            // (0 = fine), see the top of sync()
-            uint64_t* send = scal_.as<uint64_t>() + 32;
-            uint64_t* recv = reinterpret_cast<uint64_t*>(scal_.as<char>() + 4096);
-            hipLaunchKernelGGL(cutPointsKernel<K>, gridFor(size_t(P_) + 1, 64), 64, 0, ctx_->stream, keys_.as<K>(), n, dq, P_,
-                               dr, send, uint64_t(pending_ ? 1 : 0));
-            CS_HIP(ctx_, hipGetLastError());
-            if (!pinRows)
-            {
-                pinRows = static_cast<uint64_t*>(gHost_.pin.take(rows.size() * 8));
-                pinCut  = static_cast<uint64_t*>(gHost_.pin.take(size_t(P_ + 1) * 8));
-            }
-            if (P_ > 1)
-            {
-                CS_TRY(callComm(comm_.all_gather(comm_.user, send, recv, size_t(P_ + 1) * 8), "all_gather (counts)"));
-                CS_TRY(copyToPinned(ctx_, pinRows, recv, rows.size() * 8));
-            }
-            CS_TRY(copyToPinned(ctx_, pinCut, dr, size_t(P_ + 1) * 8));
-            return CSTONE_OK;
-        };
-        auto takeCuts = [&]()
-        {
-            std::copy(pinCut, pinCut + P_ + 1, cut.begin());
-            if (P_ > 1) std::copy(pinRows, pinRows + rows.size(), rows.begin());
-        };
-        injectFailure("assign");
-        const bool speculateCuts = !firstCall_ && int(assignment_.size()) == P_ + 1 && speculateCuts_;
-        if (speculateCuts) CS_TRY(queueCuts(assignment_));
-        CS_HIP(ctx_, hipStreamSynchronize(ctx_->stream)); // global counts (+ leaves), the sort's flag, cut points, matrix
-        gHost_.takeReadBack();
-        if (speculateCuts) takeCuts();
-        if (partialSort && ctx_->hostScalars[3] != 0)
-            CS_TRY(cstone_hip_sort_pairs(ctx_, kb, keys_.p, order_.as<uint32_t>(), n, keysAlt_.p, orderAlt_.as<uint32_t>(),
-                                         sortTmp_.p, sortTmp_.bytes));
-        CS_TRY(assign());
+        CS_TRY(stepGlobalTreeAndAssign(s));
         tick("3 global tree+assign");
-        if (!speculateCuts || cutKeys != assignment_)
-        {
-            if (speculateCuts) ++cutRedos_;
-            CS_TRY(queueCuts(assignment_));
-            CS_HIP(ctx_, hipStreamSynchronize(ctx_->stream));
-            takeCuts();
-        }
-        {
-            for (int p = 0; p < P_; ++p)
-                sendCounts[p] = cut[p + 1] - cut[p];
-            if (P_ == 1) matrix[0] = sendCounts[0];
-            for (int p = 0; p < P_ && P_ > 1; ++p)
-            {
-                if (rows[size_t(p) * (P_ + 1) + P_] != 0) return agreed(p);
-                for (int q = 0; q < P_; ++q)
-                    matrix[size_t(p) * P_ + q] = rows[size_t(p) * (P_ + 1) + q];
-            }
-        }
-        // conditions every rank derives from the same matrix: all of them return the same error, nobody is left waiting
-        for (int q = 0; q < P_; ++q)
-        {
-            uint64_t arriving = 0;
-            for (int p = 0; p < P_; ++p)
-                arriving += matrix[size_t(p) * P_ + q];
-            if (arriving == 0) return fail(ctx_, CSTONE_E_ARG, "domain_mr_sync: rank %d is left without particles", q);
-            if (arriving >= (uint64_t(1) << 30))
-                return fail(ctx_, CSTONE_E_ARG, "domain_mr_sync: too many particles for rank %d", q);
-        }
-        std::vector<size_t> sendBytes(P_, 0), recvBytes(P_, 0);
-        uint64_t movedAny = 0, mSend = 0, nb = 0;
-        for (int p = 0; p < P_; ++p)
-        {
-            for (int q = 0; q < P_; ++q)
-                if (p != q) movedAny += matrix[size_t(p) * P_ + q];
-            if (p == rank_) continue;
-            sendBytes[p] = sendCounts[p] * 4 * sizeof(T);
-            recvBytes[p] = matrix[size_t(p) * P_ + rank_] * 4 * sizeof(T);
-            mSend += sendCounts[p];
-            nb += matrix[size_t(p) * P_ + rank_];
-        }
-        const uint64_t na     = sendCounts[rank_];
-        const K* keptKeys     = keys_.as<K>() + cut[rank_];
-        const uint32_t* keptO = order_.as<uint32_t>() + cut[rank_];
-        const uint64_t nm     = na + nb;
-
-        if (movedAny)
-        {
-            CS_TRY(leaving_.ensure(ctx_, std::max<size_t>(mSend, 1) * sizeof(uint32_t)));
-            CS_TRY(sendRows_.ensure(ctx_, std::max<size_t>(mSend, 1) * 4 * sizeof(T)));
-            CS_TRY(recvRows_.ensure(ctx_, std::max<size_t>(nb, 1) * 4 * sizeof(T)));
-            size_t nLow = cut[rank_] - cut[0], nHigh = cut[P_] - cut[rank_ + 1];
-            if (nLow)
-                CS_HIP(ctx_, hipMemcpyAsync(leaving_.p, order_.as<uint32_t>() + cut[0], nLow * 4,
-                                            hipMemcpyDeviceToDevice, ctx_->stream));
-            if (nHigh)
-                CS_HIP(ctx_, hipMemcpyAsync(leaving_.as<uint32_t>() + nLow, order_.as<uint32_t>() + cut[rank_ + 1],
-                                            nHigh * 4, hipMemcpyDeviceToDevice, ctx_->stream));
-            if (mSend)
-                hipLaunchKernelGGL(packRowsKernel<T>, gridFor(mSend, 256), 256, 0, ctx_->stream,
-                                   leaving_.as<uint32_t>(), size_t(mSend), x, y, z, h, sendRows_.as<T>());
-            CS_TRY(callComm(comm_.all_to_all_v(comm_.user, sendRows_.p, sendBytes.data(), recvRows_.p, recvBytes.data()),
-                            "all_to_all_v (particles)"));
-        }
-
-        // ---- newcomers: sorted among themselves
-        const T* recvSorted[4] = {nullptr, nullptr, nullptr, nullptr};
-        if (nb)
-        {
-            for (int c = 0; c < 4; ++c)
-            {
-                CS_TRY(rcol_[c].ensure(ctx_, nb * sizeof(T)));
-                CS_TRY(rcolS_[c].ensure(ctx_, nb * sizeof(T)));
-            }
-            hipLaunchKernelGGL(unpackRowsKernel<T>, gridFor(nb, 256), 256, 0, ctx_->stream, recvRows_.as<T>(), size_t(nb),
-                               rcol_[0].as<T>(), rcol_[1].as<T>(), rcol_[2].as<T>(), rcol_[3].as<T>());
-            CS_TRY(rk_.ensure(ctx_, nb * sizeof(K)));
-            CS_TRY(ro_.ensure(ctx_, nb * sizeof(uint32_t)));
-            CS_TRY(ensureSortScratch(std::max<size_t>(nAlloc, nb)));
-            CS_HIP(ctx_, hipMemsetAsync(rk_.p, 0, nb * sizeof(K), ctx_->stream));
-            CS_TRY(cstone_hip_compute_sfc_keys(ctx_, curve_, kb, rb, rcol_[0].p, rcol_[1].p, rcol_[2].p, rk_.p, nb,
-                                               &box_));
-            CS_TRY(cstone_hip_sort_keys_ordering(ctx_, kb, rk_.p, ro_.as<uint32_t>(), nb, keysAlt_.p,
-                                                 orderAlt_.as<uint32_t>(), sortTmp_.p, sortTmp_.bytes));
-            for (int c = 0; c < 4; ++c)
-            {
-                CS_TRY(cstone_hip_gather(ctx_, sizeof(T), ro_.as<uint32_t>(), nb, rcol_[c].p, rcolS_[c].p));
-                recvSorted[c] = rcolS_[c].as<T>();
-            }
-        }
-
-        // ---- further conserved fields travel the same way, one collective per field (the volume is small in the steady
-        //      state); received values are brought into the newcomers' sorted order
-        DevBuf* propRecvSorted[MAX_PROPS] = {};
-        for (int q = 0; q < numProps && movedAny; ++q)
-        {
-            const size_t e = size_t(propBytes[q]);
-            std::vector<size_t> sb(P_, 0), rbv(P_, 0);
-            for (int p = 0; p < P_; ++p)
-            {
-                if (p == rank_) continue;
-                sb[p]  = sendCounts[p] * e;
-                rbv[p] = matrix[size_t(p) * P_ + rank_] * e;
-            }
-            CS_TRY(sendRows_.ensure(ctx_, std::max<size_t>(mSend, 1) * e));
-            CS_TRY(propRecv_[q].ensure(ctx_, std::max<size_t>(nb, 1) * e));
-            CS_TRY(propRecvS_[q].ensure(ctx_, std::max<size_t>(nb, 1) * e));
-            if (mSend) CS_TRY(cstone_hip_gather(ctx_, int(e), leaving_.as<uint32_t>(), mSend, props[q], sendRows_.p));
-            CS_TRY(callComm(comm_.all_to_all_v(comm_.user, sendRows_.p, sb.data(), propRecv_[q].p, rbv.data()),
-                            "all_to_all_v (property)"));
-            if (nb) CS_TRY(cstone_hip_gather(ctx_, int(e), ro_.as<uint32_t>(), nb, propRecv_[q].p, propRecvS_[q].p));
-            propRecvSorted[q] = &propRecvS_[q];
-        }
-
-        // ---- Result arrays.  The assigned block is written ONCE, at an offset M that leaves room for the halos of the
-        //      lower ranks (their number is only known after the discovery below; M is generous and follows the
-        //      previous sync).  The arrays handed out start at M - (halos of lower ranks).
-        cur_ ^= 1; // the inputs may live in the other buffer set
-        toggled_ = true;
-        Out& o           = out_[cur_];
-        const bool margins = P_ > 1 && !noMargin_;
-        // (a multiple of 4 elements: the assigned range the client passes back as the next input then starts on a
-        //  16-byte boundary, which the fused encode + digit counting kernel needs for its vector loads)
-        const uint64_t M   = margins ? (std::max<uint64_t>(2 * prevLo_ + 4096, firstCall_ ? nm / 4 : 0) + 3) & ~uint64_t(3) : 0;
-        uint64_t cap       = M + nm + (margins ? std::max<uint64_t>(2 * prevHi_ + 4096, firstCall_ ? nm / 4 : 0) : 0);
-        CS_TRY(o.keys.ensure(ctx_, cap * sizeof(K)));
-        for (DevBuf* b : {&o.x, &o.y, &o.z, &o.h})
-            CS_TRY(b->ensure(ctx_, cap * sizeof(T)));
-        for (int q = 0; q < numProps; ++q)
-            CS_TRY(o.props[q].ensure(ctx_, cap * size_t(propBytes[q])));
-
-        // ---- merge of the kept, already sorted range with the newcomers: positions, then every field from its input
-        //      slot straight to its final slot
-        K* keysM = o.keys.as<K>() + M;
-        if (nb)
-        {
-            CS_TRY(posA_.ensure(ctx_, std::max<size_t>(na, 1) * sizeof(uint32_t)));
-            CS_TRY(posB_.ensure(ctx_, nb * sizeof(uint32_t)));
-            CS_TRY(cstone_hip_merge_positions(ctx_, kb, keptKeys, na, rk_.p, nb, 0, posA_.as<uint32_t>(),
-                                              posB_.as<uint32_t>()));
-            CS_TRY(cstone_hip_scatter(ctx_, sizeof(K), posB_.as<uint32_t>(), nb, rk_.p, keysM));
-        }
-        {
-            T* dst[4] = {o.x.as<T>() + M, o.y.as<T>() + M, o.z.as<T>() + M, o.h.as<T>() + M};
-            // keys and h first: the locally essential tree and the halo discovery work on them.  x, y, z are not read
-            // before the halo exchange: they go to their final slots on the context's second stream, next to the tree
-            // update (chains of small kernels and read-backs), and are joined in front of the exchange
-            const bool overlap = useLet_ && overlapPlace_ && !grav; // (syncGrav reads x, y, z for the mass centres)
-            if (overlap) CS_TRY(ensureAuxStream(ctx_));
-            if (na)
-            {
-                StageTimer timer(ctx_, CSTONE_STAGE_PLACE);
-                if (overlap)
-                    hipLaunchKernelGGL((placeColumnsKernel<K, T, 1>), gridFor(na, 256, PLACE_PER), 256, 0, ctx_->stream, keptO,
-                                       nb ? posA_.as<uint32_t>() : nullptr, size_t(na), keptKeys, x, y, z, h, keysM, dst[0],
-                                       dst[1], dst[2], dst[3]);
-                else
-                    hipLaunchKernelGGL((placeColumnsKernel<K, T, 0>), gridFor(na, 256, PLACE_PER), 256, 0, ctx_->stream, keptO,
-                                       nb ? posA_.as<uint32_t>() : nullptr, size_t(na), keptKeys, x, y, z, h, keysM, dst[0],
-                                       dst[1], dst[2], dst[3]);
-            }
-            if (nb) CS_TRY(cstone_hip_scatter(ctx_, sizeof(T), posB_.as<uint32_t>(), nb, recvSorted[3], dst[3]));
-            if (overlap)
-            {
-                CS_HIP(ctx_, hipEventRecord(ctx_->evFork, ctx_->stream));
-                CS_HIP(ctx_, hipStreamWaitEvent(ctx_->aux, ctx_->evFork, 0));
-                int rc = CSTONE_OK;
-                {
-                    StreamScope scope(ctx_, ctx_->aux);
-                    if (na)
-                    {
-                        StageTimer timer(ctx_, CSTONE_STAGE_PLACE);
-                        hipLaunchKernelGGL((placeColumnsKernel<K, T, 2>), gridFor(na, 256, PLACE_PER), 256, 0, ctx_->stream, keptO,
-                                           nb ? posA_.as<uint32_t>() : nullptr, size_t(na), keptKeys, x, y, z, h, keysM,
-                                           dst[0], dst[1], dst[2], dst[3]);
-                    }
-                    for (int c = 0; c < 3 && nb && rc == CSTONE_OK; ++c)
-                        rc = cstone_hip_scatter(ctx_, sizeof(T), posB_.as<uint32_t>(), nb, recvSorted[c], dst[c]);
-                }
-                CS_TRY(rc);
-                CS_HIP(ctx_, hipEventRecord(ctx_->evJoin, ctx_->aux));
-                placeForked_  = true;
-                ctx_->auxBusy = true;
-            }
-            else
-            {
-                for (int c = 0; c < 3 && nb; ++c)
-                    CS_TRY(cstone_hip_scatter(ctx_, sizeof(T), posB_.as<uint32_t>(), nb, recvSorted[c], dst[c]));
-            }
-        }
-        for (int q = 0; q < numProps; ++q)
-        {
-            const int e = propBytes[q];
-            char* dst   = o.props[q].as<char>() + M * e;
-            if (nb)
-            {
-                CS_TRY(cstone_hip_gather_scatter(ctx_, e, keptO, posA_.as<uint32_t>(), na, props[q], dst));
-                CS_TRY(cstone_hip_scatter(ctx_, e, posB_.as<uint32_t>(), nb, propRecvSorted[q]->p, dst));
-            }
-            else { CS_TRY(cstone_hip_gather(ctx_, e, keptO, na, props[q], dst)); }
-        }
+        CS_TRY(redoCutsIfAssignmentChanged(s));
+        CS_TRY(planExchange(s));
+        CS_TRY(exchangeParticles(s));
+        CS_TRY(sortNewcomers(s));
+        CS_TRY(exchangeProperties(s));
+        CS_TRY(reserveResultArrays(s));
+        CS_TRY(mergeAndPlace(s));
         tick("4 exchange+merge+place");
-
-        std::vector<uint64_t> hsCounts(P_, 0), hmatrix(size_t(P_) * P_, 0);
-        uint64_t numMyBoxes = 0, selTotal = 0;
-        uint64_t nlo = 0, nhi = 0, haloAny = 0; // haloAny: the same on every rank, it decides about the collective
-        std::vector<size_t> hSendBytes(P_, 0), hRecvBytes(P_, 0);
         if (useLet_)
         {
-            // ---- the reference's way (R/domain/domain.hpp:217-237): peers, locally essential tree (focus tree), halo
-            //      discovery on it, key-range requests to the owners -- csrc/let.hpp.  h is in SFC order at o.h + M.
-            if (!let_) let_ = std::make_unique<FocusLet<K, T>>(ctx_, curve_, rank_, P_, bucketFocus_, theta_, comm_);
-            injectFailure("exchange");
-            int rc;
-            if (grav)
-            {
-                const char* mSorted = o.props[numProps - 1].as<char>() + M * size_t(massBits / 8);
-                rc = let_->updateGrav(box_, keysM, size_t(nm), assignment_.data(), gTree_.as<K>(), gHost_.leaves.data(),
-                                      gCounts_.as<uint32_t>(), gLeaves_, o.x.as<T>() + M, o.y.as<T>() + M, o.z.as<T>() + M,
-                                      mSorted, massBits, o.h.as<T>() + M, haloExt_, &centerDriftTol_,
-                                      pending_ ? rank_ + 1 : 0, gTreeSame_);
-                haveExpansionCenters_ = rc == CSTONE_OK;
-            }
-            else
-            {
-                rc = let_->update(box_, keysM, size_t(nm), assignment_.data(), gTree_.as<K>(), gCounts_.as<uint32_t>(),
-                                  gLeaves_, o.h.as<T>() + M, haloExt_, pending_ ? rank_ + 1 : 0, gTreeSame_);
-                haveExpansionCenters_ = false;
-            }
-            if (rc != CSTONE_OK)
-            {
-                // (a failure of my own that the status word of the tree's last count exchange has told everybody about:
-                //  reported with its own message)
-                if (pending_) return agreed(rank_);
-                if (toggled_) cur_ ^= 1, toggled_ = false;
-                return rc;
-            }
-            if (uint64_t(let_->endIndex() - let_->startIndex()) != nm)
-                return fail(ctx_, CSTONE_E_INTERNAL, "domain_mr_sync: the focus tree counts %u assigned particles, %llu are here",
-                            let_->endIndex() - let_->startIndex(), (unsigned long long)nm);
-            nlo      = let_->startIndex();
-            nhi      = let_->numParticlesWithHalos() - let_->endIndex();
-            haloAny  = 1;
-            selTotal = let_->halosSent();
-            // the leaves of my own range and their offsets among my particles: what the next sync's re-sort starts from
-            const int first = let_->startCell(), last = let_->endCell();
-            fLeaves_        = let_->numLeaves();
-            resortTree_     = let_->leaves() + first;
-            resortLeaves_   = last - first;
-            CS_TRY(layout_.ensure(ctx_, size_t(resortLeaves_ + 1) * sizeof(uint32_t)));
-            CS_TRY(cstone_hip_increment(ctx_, 32, let_->layout() + first, layout_.p, size_t(resortLeaves_) + 1,
-                                        uint64_t(uint32_t(0u - uint32_t(nlo)))));
-            layoutParticles_ = nm;
-            layoutBox_       = box_;
-            if (!hostLevelRange_)
-                CS_HIP(ctx_, hipHostMalloc(reinterpret_cast<void**>(&hostLevelRange_), 32 * sizeof(NodeIdx), hipHostMallocDefault));
-            // (the level ranges came back with the layout: no copy of their own)
-            std::copy(let_->levelRangeHost().begin(), let_->levelRangeHost().end(), hostLevelRange_);
-            levelRangePending_ = true;
+            CS_TRY(updateLet(s));
             tick("5 focus tree (LET)");
         }
         else
         {
             // ---- this rank's finest tree over its assigned particles; its SFC range must end on leaf boundaries
-            CS_TRY(updateFocusTree(keysM, nm));
+            CS_TRY(updateFocusTree(s.keysM, s.nm));
             tick("5a focus update");
-            int first = 0, last = 0;
-            CS_TRY(enforceBoundaries(keysM, nm, &first, &last));
+            CS_TRY(enforceBoundaries(s.keysM, s.nm, &s.first, &s.last));
             tick("5b boundaries");
             CS_TRY(buildFocusOctree());
             tick("5c linked octree");
-            // the level ranges are only needed by the NEXT sync (how many digits to sort): they travel to a pinned block of
-            // this domain now and are looked at then, behind many later synchronisations of the stream
-            if (!hostLevelRange_)
-                CS_HIP(ctx_, hipHostMalloc(reinterpret_cast<void**>(&hostLevelRange_), 32 * sizeof(NodeIdx), hipHostMallocDefault));
-            CS_TRY(copyToPinned(ctx_, hostLevelRange_, fLevelRange_.p, (maxLevel<K>() + 2) * sizeof(NodeIdx)));
-            levelRangePending_ = true;
-            const int L = fLeaves_;
-            CS_TRY(layout_.ensure(ctx_, size_t(L + 1) * sizeof(uint32_t)));
-            CS_HIP(ctx_, hipMemsetAsync(layout_.p, 0, sizeof(uint32_t), ctx_->stream));
-            CS_TRY(cstone_hip_inclusive_scan_u32(ctx_, fCounts_.as<uint32_t>(), layout_.as<uint32_t>() + 1, size_t(L)));
-            layoutParticles_ = nm; // the next sync's re-sort starts from this layout: nm particles in this box
-            layoutBox_       = box_;
-            resortTree_      = fTree_.as<K>();
-            resortLeaves_    = fLeaves_;
+            CS_TRY(layoutOwnTree(s));
             tick("5 focus tree");
-
-            // ---- C4: owner-side halo discovery
-            if (P_ > 1)
-            {
-                const int nLocal = last - first;
-                CS_TRY(radii_.ensure(ctx_, size_t(L) * sizeof(float)));
-                CS_TRY(boxes_.ensure(ctx_, size_t(std::max(nLocal, 1)) * 32));
-                CS_TRY(boxFlags_.ensure(ctx_, size_t(nLocal + 1) * sizeof(uint32_t)));
-                CS_TRY(cstone_hip_halo_radii(ctx_, rb, o.h.as<T>() + M, layout_.as<uint32_t>() + first, first, last, L, haloExt_,
-                                             radii_.as<float>()));
-                // only boxes that really reach a leaf outside my range are exported (a third to a tenth of those the
-                // enclosing-node test alone lets through: less to gather, fewer targets for every owner's traversal)
-                CS_TRY(cstone_hip_halo_boxes_foreign(ctx_, curve_, kb, rb, fPrefixes_.p, fChild_.as<int32_t>(),
-                                                     fItl_.as<int32_t>(), fTree_.p, radii_.as<float>(), &box_, first, last,
-                                                     boxes_.as<int32_t>()));
-                hipLaunchKernelGGL(boxFlagsKernel, gridFor(nLocal, 256), 256, 0, ctx_->stream, boxes_.as<int32_t>(), nLocal,
-                                   boxFlags_.as<uint32_t>());
-                uint32_t* total = scal_.as<uint32_t>() + 16;
-                CS_TRY(exclusiveScanWithTotal(boxFlags_.as<uint32_t>(), nLocal, total));
-                // box counts of everybody straight from the device scalar (one read-back for mine and theirs), then the
-                // boxes themselves padded to the longest list
-                std::vector<uint64_t> boxCounts(P_);
-                {
-                    uint32_t* recv = reinterpret_cast<uint32_t*>(scal_.as<char>() + 4096);
-                    injectFailure("exchange");
-                    statusW32_ = pending_ ? 1u : 0u; // second word: the status of this rank (a member, see above)
-                    CS_HIP(ctx_, hipMemcpyAsync(total + 1, &statusW32_, 4, hipMemcpyHostToDevice, ctx_->stream));
-                    CS_TRY(callComm(comm_.all_gather(comm_.user, total, recv, 8), "all_gather (box counts)"));
-                    std::vector<uint32_t> c32(size_t(P_) * 2);
-                    CS_TRY(toHost(c32.data(), recv, c32.size() * 4));
-                    for (int p = 0; p < P_; ++p)
-                    {
-                        if (c32[2 * p + 1] != 0) return agreed(p);
-                        boxCounts[p] = c32[2 * p];
-                    }
-                }
-                const uint32_t nbx = uint32_t(boxCounts[rank_]);
-                numMyBoxes         = nbx;
-                CS_TRY(myBoxes_.ensure(ctx_, size_t(std::max<uint32_t>(nbx, 1)) * 32));
-                hipLaunchKernelGGL(compactBoxesKernel, gridFor(nLocal, 256), 256, 0, ctx_->stream, boxes_.as<int32_t>(),
-                                   boxFlags_.as<uint32_t>(), nLocal, rank_, myBoxes_.as<int32_t>());
-                uint64_t maxBoxes = *std::max_element(boxCounts.begin(), boxCounts.end());
-                if (maxBoxes)
-                {
-                    CS_TRY(myBoxes_.ensure(ctx_, size_t(maxBoxes) * 32, true));
-                    if (maxBoxes > numMyBoxes) // padding records must read "no box"
-                        CS_HIP(ctx_, hipMemsetAsync(myBoxes_.as<char>() + numMyBoxes * 32, 0, (maxBoxes - numMyBoxes) * 32,
-                                                    ctx_->stream));
-                    CS_TRY(allBoxes_.ensure(ctx_, size_t(maxBoxes) * 32 * P_));
-                    CS_TRY(callComm(comm_.all_gather(comm_.user, myBoxes_.p, allBoxes_.p, size_t(maxBoxes) * 32),
-                                    "all_gather (halo boxes)"));
-                }
-                CS_TRY(oflags_.ensure(ctx_, size_t(L) * sizeof(int32_t)));
-                bool haveMatrix = false;
-                if (maxBoxes && P_ <= 32 && !peerLoop_)
-                {
-                    // all peers in one go: the records carry their exporter, find_overlaps sets one bit per exporter
-                    // (two calls: the records before and behind my own); then counts, one scan and one fill for all peers
-                    const int np = P_ - 1;
-                    CS_HIP(ctx_, hipMemsetAsync(oflags_.p, 0, size_t(L) * sizeof(int32_t), ctx_->stream));
-                    if (rank_ > 0)
-                        CS_TRY(cstone_hip_find_overlaps(ctx_, curve_, kb, fPrefixes_.p, fChild_.as<int32_t>(),
-                                                        fItl_.as<int32_t>(), fTree_.p, allBoxes_.as<int32_t>(),
-                                                        int(size_t(rank_) * maxBoxes), first, last, oflags_.as<int32_t>()));
-                    if (rank_ + 1 < P_)
-                        CS_TRY(cstone_hip_find_overlaps(ctx_, curve_, kb, fPrefixes_.p, fChild_.as<int32_t>(),
-                                                        fItl_.as<int32_t>(), fTree_.p,
-                                                        allBoxes_.as<int32_t>() + size_t(rank_ + 1) * maxBoxes * 8,
-                                                        int(size_t(P_ - rank_ - 1) * maxBoxes), first, last,
-                                                        oflags_.as<int32_t>()));
-                    const size_t items = size_t(np) * nLocal;
-                    CS_TRY(cnt_.ensure(ctx_, (items + 1) * sizeof(uint32_t)));
-                    hipLaunchKernelGGL(peerCountsKernel, gridFor(nLocal, 256), 256, 0, ctx_->stream, oflags_.as<int32_t>(),
-                                       layout_.as<uint32_t>(), first, last, P_, rank_, cnt_.as<uint32_t>());
-                    CS_TRY(exclusiveScanWithTotal(cnt_.as<uint32_t>(), int(items), total));
-                    // my row of the count matrix goes from the device into the all-gather of the rows; one read-back
-                    uint64_t* row  = scal_.as<uint64_t>() + 32;
-                    uint64_t* rows = reinterpret_cast<uint64_t*>(scal_.as<char>() + 4096);
-                    hipLaunchKernelGGL(peerTotalsKernel, 1, 64, 0, ctx_->stream, cnt_.as<uint32_t>(), total, nLocal, np,
-                                       rank_, row);
-                    CS_TRY(callComm(comm_.all_gather(comm_.user, row, rows, size_t(P_) * 8), "all_gather (halo counts)"));
-                    hmatrix.assign(size_t(P_) * P_, 0);
-                    CS_TRY(toHost(hmatrix.data(), rows, size_t(P_) * P_ * 8));
-                    haveMatrix = true;
-                    for (int p = 0; p < P_; ++p)
-                    {
-                        hsCounts[p] = hmatrix[size_t(rank_) * P_ + p];
-                        selTotal += hsCounts[p];
-                    }
-                    if (selTotal)
-                    {
-                        CS_TRY(sel_.ensure(ctx_, selTotal * sizeof(uint32_t)));
-                        hipLaunchKernelGGL(peerFillKernel, gridFor(items, 16), 256, 0, ctx_->stream, oflags_.as<int32_t>(),
-                                           layout_.as<uint32_t>(), cnt_.as<uint32_t>(), first, last, P_, rank_,
-                                           sel_.as<uint32_t>());
-                    }
-                }
-                else
-                {
-                CS_TRY(cnt_.ensure(ctx_, size_t(nLocal + 1) * sizeof(uint32_t)));
-                for (int p = 0; p < P_; ++p)
-                {
-                    if (p == rank_ || boxCounts[p] == 0) continue;
-                    CS_HIP(ctx_, hipMemsetAsync(oflags_.p, 0, size_t(L) * sizeof(int32_t), ctx_->stream));
-                    CS_TRY(cstone_hip_find_overlaps(ctx_, curve_, kb, fPrefixes_.p, fChild_.as<int32_t>(),
-                                                    fItl_.as<int32_t>(), fTree_.p,
-                                                    allBoxes_.as<int32_t>() + size_t(p) * maxBoxes * 8, int(boxCounts[p]),
-                                                    first, last, oflags_.as<int32_t>()));
-                    hipLaunchKernelGGL(flaggedCountsKernel, gridFor(nLocal, 256), 256, 0, ctx_->stream,
-                                       oflags_.as<int32_t>(), layout_.as<uint32_t>(), first, last, cnt_.as<uint32_t>());
-                    CS_TRY(exclusiveScanWithTotal(cnt_.as<uint32_t>(), nLocal, total));
-                    uint32_t tp = 0;
-                    CS_TRY(toHost(&tp, total, 4));
-                    if (tp)
-                    {
-                        CS_TRY(sel_.ensure(ctx_, (selTotal + tp) * sizeof(uint32_t), true));
-                        hipLaunchKernelGGL(fillIndicesKernel, gridFor(nLocal, 16), 256, 0, ctx_->stream,
-                                           oflags_.as<int32_t>(), layout_.as<uint32_t>(), cnt_.as<uint32_t>(), first, last,
-                                           sel_.as<uint32_t>() + selTotal);
-                    }
-                    hsCounts[p] = tp;
-                    selTotal += tp;
-                }
-                }
-                if (!haveMatrix) CS_TRY(countMatrix(hsCounts, hmatrix));
-            }
-            for (uint64_t v : hmatrix)
-                haloAny += v;
-            for (int p = 0; p < P_; ++p)
-            {
-                uint64_t r = hmatrix[size_t(p) * P_ + rank_];
-                (p < rank_ ? nlo : nhi) += (p == rank_ ? 0 : r);
-                hSendBytes[p] = hsCounts[p] * 4 * sizeof(T);
-                hRecvBytes[p] = (p == rank_ ? 0 : r) * 4 * sizeof(T);
-            }
-
+            CS_TRY(discoverHalosOwnerSide(s));
         }
         tick("6 halo discovery");
-        if (placeForked_)
-        {
-            // x, y, z of the assigned block are needed from here on (a block that has to be moved, the halo exchange)
-            CS_HIP(ctx_, hipStreamWaitEvent(ctx_->stream, ctx_->evJoin, 0));
-            placeForked_  = false;
-            ctx_->auxBusy = false;
-        }
-        // ---- room for the halos on both sides of the assigned block
-        const uint64_t total = nlo + nm + nhi;
-        uint64_t off = M - std::min(M, nlo); // start of the arrays handed out
-        if (nlo > M || M + nm + nhi > cap)
-        {
-            // the margins were too small (first syncs, abrupt changes): move the block once, through a scratch copy
-            const uint64_t M2 = (nlo + 3) & ~uint64_t(3), cap2 = M2 + nm + nhi;
-            auto shift = [&](DevBuf& buf, size_t elem) -> int
-            {
-                CS_TRY(moveTmp_.ensure(ctx_, nm * elem));
-                CS_HIP(ctx_, hipMemcpyAsync(moveTmp_.p, buf.as<char>() + M * elem, nm * elem, hipMemcpyDeviceToDevice,
-                                            ctx_->stream));
-                CS_TRY(buf.ensure(ctx_, cap2 * elem));
-                CS_HIP(ctx_, hipMemcpyAsync(buf.as<char>() + M2 * elem, moveTmp_.p, nm * elem, hipMemcpyDeviceToDevice,
-                                            ctx_->stream));
-                return CSTONE_OK;
-            };
-            CS_TRY(shift(o.keys, sizeof(K)));
-            for (DevBuf* b : {&o.x, &o.y, &o.z, &o.h})
-                CS_TRY(shift(*b, sizeof(T)));
-            for (int q = 0; q < numProps; ++q)
-                CS_TRY(shift(o.props[q], size_t(propBytes[q])));
-            off = M2 - nlo;
-        }
-        const uint64_t A = off + nlo; // first assigned slot
-        prevLo_ = nlo, prevHi_ = nhi;
+        CS_TRY(joinPlace());
+        CS_TRY(makeRoomForHalos(s));
         tick("7 margins");
-        // ---- C5: halo exchange
-        if (useLet_ && P_ > 1)
+        CS_TRY(exchangeHaloParticles(s));
+        tick("8 halo exchange");
+        return finishSync(s);
+    }
+
+private:
+    //! What the stages of one sync share: the caller's arrays and what the stages before have decided.  Made by sync().
+    struct SyncState
+    {
+        const T *x, *y, *z, *h;
+        size_t n; // (0 from beginSync on for a rank that limps on as an empty rank)
+        const void* keysIn;
+        const void* const* props; // the caller's properties; syncGrav: propList, the masses behind them
+        const int* propBytes;
+        int numProps, massBits; // massBits 0: not a syncGrav
+        const void* propList[MAX_PROPS + 1] = {};
+        int propSizes[MAX_PROPS + 1]        = {};
+        const K* resortTree = nullptr; // the leaves of my range as the last COMPLETED sync left them, and their number
+        int resortLeaves    = 0;
+        bool resortReady    = false; // everything a re-sort needs holds, but for the box being that of the layout still
+        bool speculate      = false; // the keys are computed with the box of the previous sync, the same pass measures
+        bool resorted       = false; // the re-sort has put keys_ and order_ into their final order
+        bool partialSort    = false; // the radix sort left runs to the fix-up: its flag is on its way to the pinned block
+        bool speculateCuts  = false; // the cut points were asked for before assign()
+        std::vector<K> cutKeys;      // ... for this assignment
+        std::vector<uint64_t> cut, rows; // cut points in my sorted keys; the all-gathered count rows, word P = status
+        uint64_t *pinRows = nullptr, *pinCut = nullptr;
+        ExchangePlan plan;
+        uint64_t nm = 0; // assigned particles: plan.na kept (keys and input slots at keptKeys, keptO) + plan.nb received
+        const K* keptKeys     = nullptr;
+        const uint32_t* keptO = nullptr;
+        Out* o        = nullptr;
+        uint64_t M = 0, cap = 0, off = 0; // first assigned slot, length of the result arrays, start of what is handed out
+        K* keysM      = nullptr;
+        int first = 0, last = 0; // my leaves in the focus tree
+        std::vector<uint64_t> hsCounts, hmatrix; // halos I send to rank p; hmatrix[src * P + dst] (owner-side mode)
+        uint64_t numMyBoxes = 0, selTotal = 0, nlo = 0, nhi = 0, haloAny = 0; // haloAny: the same on every rank
+    };
+
+    // ---- The slots of scal_, one block of device scalars (sized in beginSync).  extentsDev and gatherRow are the SAME
+    //      address: the box reduction of tryResort consumes the extents before the first cut points are queued.  The four
+    //      counters of the re-sort follow boxOperand (bytes 56..71) and overlap scanTotal: they are read back in tryResort,
+    //      scanTotal belongs to the owner-side halo discovery.
+    template<class V>
+    V* slot(size_t byte) const { return reinterpret_cast<V*>(scal_.as<char>() + byte); }
+    double* boxOperand() const { return slot<double>(0); }        // (lo, -hi) per axis, status: the MIN all-reduce
+    uint32_t* scanTotal() const { return slot<uint32_t>(64); }    // {total of a scan, status word}
+    int* tooLongFlag() const { return slot<int>(128); }           // the partial sort met a run it cannot fix up
+    T* extentsDev() const { return slot<T>(256); }                // {min, max} per axis, measured by the encode
+    uint64_t* gatherRow() const { return slot<uint64_t>(256); }   // my row of an all-gather, up to P + 1 words
+    uint64_t* leafQuery() const { return slot<uint64_t>(1024); }  // enforceBoundaries: 2 x (index, start, end)
+    K* cutKeysDev() const { return slot<K>(2048); }               // the assignment, P + 1 keys, then as many cut points
+    uint64_t* cutPointsDev() const { return slot<uint64_t>(2048 + size_t(P_ + 1) * 8); }
+    uint64_t* gatherRecv() const { return slot<uint64_t>(4096); } // the rows of everybody, up to P (P + 1) words
+
+    //! bytes[p] = counts[p * stride] elements of e bytes for every peer p, 0 for myself: what all_to_all_v takes
+    std::vector<size_t> peerBytes(const uint64_t* counts, size_t stride, size_t e) const
+    {
+        std::vector<size_t> bytes(P_, 0);
+        for (int p = 0; p < P_; ++p)
+            if (p != rank_) bytes[p] = counts[p * stride] * e;
+        return bytes;
+    }
+
+    //! The arguments; syncGrav: the masses travel as one more property behind the caller's.  A failure of the arguments (or
+    //! one injected by the tests, CSTONE_MR_FAIL_AT) becomes the pending status the peers must learn about
+    int beginSync(SyncState& s, const void* mass)
+    {
+        if (s.massBits)
         {
-            // the particle buffers start at `off`: halos below | assigned | halos above, in the order of the focus tree's
-            // leaves (R/domain/domain.hpp:522-540: exchangeHalos(x, y, z, h), then the keys of the halo particles)
-            // (x, y, z and h travel together: one message per peer instead of four)
+            if (!useLet_) return fail(ctx_, CSTONE_E_ARG, "domain_mr_sync_grav: needs the locally essential tree (CSTONE_MR_HALOS_LET)");
+            if ((s.massBits != 32 && s.massBits != 64) || s.massBits > rb || (s.n && !mass) || s.numProps < 0 || s.numProps >= MAX_PROPS)
+                return fail(ctx_, CSTONE_E_ARG, "domain_mr_sync_grav: masses of 32 or 64 bits (not wider than the coordinates), "
+                                                "at most %d further properties", MAX_PROPS - 1);
+            for (int q = 0; q < s.numProps; ++q)
+                s.propList[q] = s.props[q], s.propSizes[q] = s.propBytes[q];
+            s.propList[s.numProps] = mass, s.propSizes[s.numProps] = s.massBits / 8;
+            s.props = s.propList, s.propBytes = s.propSizes, ++s.numProps;
+        }
+        pending_ = 0, toggled_ = false;
+        CS_TRY(joinPlace()); // (a sync that was abandoned behind its fork: whatever it left on the second stream comes first)
+        ctx_->auxBusy = false;
+        if (s.numProps < 0 || s.numProps > MAX_PROPS) setPending(CSTONE_E_ARG, "domain_mr_sync: at most %d properties", MAX_PROPS);
+        for (int q = 0; q < s.numProps && !pending_; ++q)
+            if ((s.n && !s.props[q]) || !gatherableElement(s.propBytes[q])) // an empty rank may pass null arrays
+                setPending(CSTONE_E_ARG, "domain_mr_sync: property %d must have elements of 1, 2, 4, 8, 12, 16, 24 or 32 bytes", q);
+        if (s.n >= (size_t(1) << 30)) setPending(CSTONE_E_ARG, "domain_mr_sync: too many particles per rank");
+        injectFailure("start");
+        if (pending_)
+        {
+            if (P_ == 1) return agreed(rank_);
+            s.n = 0, s.numProps = 0; // limp on as an empty rank until the peers know
+        }
+        s.hsCounts.assign(P_, 0), s.hmatrix.assign(size_t(P_) * P_, 0);
+        CS_TRY(scal_.ensure(ctx_, 4096 + size_t(P_) * (P_ + 1) * 8 + size_t(P_ + 1) * 16));
+        ++syncs_;
+        return CSTONE_OK;
+    }
+
+    //! The box: measured first, or, in a sync that is going to re-sort, speculated to be that of the previous sync and
+    //! measured by the encode (tryResort).  The box all-reduce is the first collective of the sync either way
+    int chooseBox(SyncState& s)
+    {
+        const bool anyOpen = !(box_.bc[0] == 1 && box_.bc[1] == 1 && box_.bc[2] == 1);
+        // What the re-sort of THIS sync starts from.  The members are set again only behind the tree update: a sync that
+        // fails half way may have rebalanced, swapped or freed the buffers they point into, and the retry sorts from scratch
+        s.resortTree = resortTree_, s.resortLeaves = resortLeaves_;
+        const uint64_t layoutParticles = layoutParticles_;
+        resortTree_ = nullptr, resortLeaves_ = 0, layoutParticles_ = 0;
+        s.resortReady = !firstCall_ && s.n >= resortMinParticles() && s.n == layoutParticles &&
+                        LeafResort<K>::leavesPerTile(bucketFocus_) > 0 && s.resortLeaves > 0 && resortBackoff_ == 0 &&
+                        !pending_ && mayResort(sortMode_);
+        // (CSTONE_NO_SPECULATIVE_BOX: read once, in the constructor; the single-rank path reads it per sync)
+        s.speculate = s.resortReady && anyOpen && !measureFirst_ && speculativeBox_ && sameLimits(box_, layoutBox_);
+        if (s.speculate) return CSTONE_OK;
+        const cstone_box before = box_;
+        CS_TRY(updateBox(s.x, s.y, s.z, s.n));
+        if (!firstCall_ && anyOpen) measureFirst_ = !sameLimits(box_, before);
+        return CSTONE_OK;
+    }
+
+    //! buffers of keys + SFC ordering of the present particles, and the caller's keys into them
+    int reserveSortBuffers(SyncState& s)
+    {
+        const size_t nAlloc = std::max<size_t>(s.n, 64);
+        CS_TRY(keys_.ensure(ctx_, nAlloc * sizeof(K)));
+        CS_TRY(order_.ensure(ctx_, nAlloc * sizeof(uint32_t)));
+        CS_TRY(ensureSortScratch(nAlloc));
+        // encode leaves entries that hold the remove marker 2^(3 maxLevel) alone (R/sfc/sfc.hpp:284-291): such particles sort
+        // behind the end of the curve and leave the domain (no key array from the caller: no markers, keys_ is pure output)
+        if (s.keysIn && s.n)
+            CS_HIP(ctx_, hipMemcpyAsync(keys_.p, s.keysIn, s.n * sizeof(K), hipMemcpyDeviceToDevice, ctx_->stream));
+        return CSTONE_OK;
+    }
+
+    //! the level ranges of the previous sync's tree (in the pinned block since its build, many stream synchronisations
+    //! ago): at EVERY sync -- buildFocusOctree() bounds its digit passes by them, also on the syncs that re-sort
+    void takeLevelRanges()
+    {
+        if (levelRangePending_) prevMaxLeafLevel_ = deepestLevel<K>(hostLevelRange_);
+        levelRangePending_ = false;
+    }
+
+    /*! The incremental re-sort (resort.hpp), as in the single-rank domain: the input is the assigned block the previous
+     *  sync handed out, ordered by the leaves of this rank's tree (layout_).  Unlike there, a sync that speculates on the
+     *  box has the box all-reduce in the middle, whose read-back brings the re-sort's counters too.  Sets s.resorted. */
+    int tryResort(SyncState& s)
+    {
+        // (box_ may be a freshly measured one by now; a sync that speculates has left it alone, so it always attempts:
+        //  no box is left unmeasured)
+        const bool attempt = s.resortReady && sameLimits(box_, layoutBox_);
+        if (resortBackoff_ > 0) --resortBackoff_;
+        if (!attempt) return CSTONE_OK;
+        const int tileLeaves = LeafResort<K>::leavesPerTile(bucketFocus_);
+        CS_TRY(resort_.prepare(ctx_, s.resortTree, layout_.as<uint32_t>(), s.resortLeaves, s.n, keysAlt_.as<K>(),
+                               lastMovers_ > 100000));
+        const ResortArgs<K> ra = resort_.args();
+        bool done              = false;
+        CS_TRY(computeKeysResort(ctx_, curve_, kb, rb, s.x, s.y, s.z, s.keysIn ? keys_.p : nullptr, s.n, box_, &ra,
+                                 s.speculate ? extentsDev() : nullptr, &done));
+        bool boxHolds = true, foundHere = false;
+        int found[4] = {0, 0, 0, 0};
+        if (s.speculate)
+        {
+            // (the keys above were computed with the box of the previous sync: was it still the box?)
+            double* dev = boxOperand();
+            if (done)
+            {
+                CS_TRY(resort_.binMovers(ctx_, tileLeaves));
+                // (the re-sort's counters and this rank's status word become part of the operand: one launch, and
+                //  one copy and one synchronisation bring the reduced extents and the counters)
+                CS_TRY(extentsToReduceOperand(ctx_, rb, extentsDev(), dev, statusWord(), ctx_->devScalars + RESORT_SCALARS));
+                foundHere = true;
+            }
+            else
+            {
+                const void* arrays[3] = {s.x, s.y, s.z};
+                CS_TRY(minMaxCoordinatesDev(ctx_, rb, arrays, 3, s.n, dev));
+            }
+            cstone_box next;
+            CS_TRY(reduceBox(dev, &next, foundHere, foundHere ? found : nullptr));
+            boxHolds = sameLimits(next, box_);
+            if (!boxHolds) box_ = next, measureFirst_ = true, ++boxRedos_;
+        }
+        else if (done) { CS_TRY(resort_.binMovers(ctx_, tileLeaves)); }
+        if (!done || !boxHolds) return CSTONE_OK;
+        if (!foundHere) CS_TRY(copyToHost(ctx_, found, ctx_->devScalars + RESORT_SCALARS, sizeof found));
+        const uint32_t markers = uint32_t(found[0]), J = uint32_t(found[2]), movers = uint32_t(found[3]);
+        if (!resortAccepted(found[1], movers, s.n))
+        {
+            resortBackoff_ = RESORT_BACKOFF_SYNCS; // (not counted here, unlike the single-rank path)
+            return CSTONE_OK;
+        }
+        CS_TRY(resort_.sortLeaves(ctx_, keysAlt_.as<K>(), keys_.as<K>(), order_.as<uint32_t>(), movers, markers, J,
+                                  tileLeaves, (found[1] & RESORT_LARGE_QUIET_TILES) != 0));
+        s.resorted  = true;
+        lastMovers_ = movers;
+        ++resorts_;
+        return CSTONE_OK;
+    }
+
+    //! the radix path: passes only over the digits above the leaf level (+1) of the previous tree, runs of equal high
+    //! digits are finished by a fix-up pass; a run that is too long raises a flag and the regular sort completes the job
+    int encodeAndSort(SyncState& s)
+    {
+        if (!s.n || s.resorted) return CSTONE_OK;
+        int startPass = 0;
+        // (the deepest level: as the last read of the pinned block left it; the single-rank path keeps the whole array)
+        if (!firstCall_ && prevMaxLeafLevel_ >= 0 && !allDigits(sortMode_))
+            startPass = partialSortStartPass<K>(prevMaxLeafLevel_, bucketFocus_);
+        CS_TRY(sfcKeysAndOrderingHint(ctx_, curve_, kb, rb, s.x, s.y, s.z, keys_.p, order_.as<uint32_t>(), s.n, box_,
+                                      keysAlt_.p, orderAlt_.as<uint32_t>(), sortTmp_.p, sortTmp_.bytes, startPass,
+                                      tooLongFlag(), s.keysIn != nullptr));
+        // the flag travels to the pinned host block behind the sort; the read-back of the global tree update completes the
+        // stream (the global leaf boundaries cannot fall inside a run: that update is not affected by an unfinished order)
+        s.partialSort = startPass > 0;
+        if (s.partialSort) CS_TRY(copyToPinned(ctx_, ctx_->hostScalars + 3, tooLongFlag(), sizeof(int)));
+        return CSTONE_OK;
+    }
+
+    //! cut points of assignment_ in my sorted keys and my row of the count matrix, which goes from the device into the
+    //! all-gather of the rows (word P of a row: the status of that rank, 0 = fine); all queued, into gHost_'s pinned block
+    int queueCuts(SyncState& s)
+    {
+        s.cutKeys = assignment_;
+        CS_TRY(cstone_hip_upload(ctx_, cutKeysDev(), assignment_.data(), size_t(P_ + 1) * sizeof(K)));
+        hipLaunchKernelGGL(cutPointsKernel<K>, gridFor(size_t(P_) + 1, 64), 64, 0, ctx_->stream, keys_.as<K>(), s.n,
+                           cutKeysDev(), P_, cutPointsDev(), gatherRow(), uint64_t(pending_ ? 1 : 0));
+        CS_HIP(ctx_, hipGetLastError());
+        if (!s.pinRows)
+        {
+            s.pinRows = static_cast<uint64_t*>(gHost_.pin.take(s.rows.size() * 8));
+            s.pinCut  = static_cast<uint64_t*>(gHost_.pin.take(size_t(P_ + 1) * 8));
+        }
+        if (P_ > 1)
+        {
+            CS_TRY(callComm(comm_.all_gather(comm_.user, gatherRow(), gatherRecv(), size_t(P_ + 1) * 8),
+                            "all_gather (counts)"));
+            CS_TRY(copyToPinned(ctx_, s.pinRows, gatherRecv(), s.rows.size() * 8));
+        }
+        return copyToPinned(ctx_, s.pinCut, cutPointsDev(), size_t(P_ + 1) * 8);
+    }
+    //! ... behind a synchronisation of the stream
+    void takeCuts(SyncState& s)
+    {
+        std::copy(s.pinCut, s.pinCut + P_ + 1, s.cut.begin());
+        if (P_ > 1) std::copy(s.pinRows, s.pinRows + s.rows.size(), s.rows.begin());
+    }
+
+    //! C2 and the first half of C3.  The assignment rarely changes: the cut points for that of the LAST sync are queued
+    //! right behind the global counts, and ONE read-back brings counts, cut points and count matrix
+    int stepGlobalTreeAndAssign(SyncState& s)
+    {
+        CS_TRY(updateGlobalTree(s.n));
+        // (counts, and the leaf array when the device made it; room behind them for the cut points and the count matrix)
+        CS_TRY(gHost_.queueReadBack(ctx_, gTree_, gCounts_, gLeaves_, !gLeavesOnHost_, size_t(P_ + 1) * (P_ + 2) * 8 + 1024));
+        s.cut.assign(P_ + 1, 0), s.rows.assign(size_t(P_) * (P_ + 1), 0);
+        injectFailure("assign");
+        s.speculateCuts = !firstCall_ && int(assignment_.size()) == P_ + 1 && speculateCuts_;
+        if (s.speculateCuts) CS_TRY(queueCuts(s));
+        CS_HIP(ctx_, hipStreamSynchronize(ctx_->stream)); // global counts (+ leaves), the sort's flag, cut points, matrix
+        gHost_.takeReadBack();
+        if (s.speculateCuts) takeCuts(s);
+        if (s.partialSort && ctx_->hostScalars[3] != 0)
+            CS_TRY(cstone_hip_sort_pairs(ctx_, kb, keys_.p, order_.as<uint32_t>(), s.n, keysAlt_.p, orderAlt_.as<uint32_t>(),
+                                         sortTmp_.p, sortTmp_.bytes));
+        return assign();
+    }
+
+    //! only a sync whose assignment did change (or that did not speculate on it) asks for the cut points again
+    int redoCutsIfAssignmentChanged(SyncState& s)
+    {
+        if (s.speculateCuts && s.cutKeys == assignment_) return CSTONE_OK;
+        if (s.speculateCuts) ++cutRedos_;
+        CS_TRY(queueCuts(s));
+        CS_HIP(ctx_, hipStreamSynchronize(ctx_->stream));
+        takeCuts(s);
+        return CSTONE_OK;
+    }
+
+    //! who sends what to whom (exchangePlan, host_rules.hpp); every rank derives the same errors from the same matrix
+    int planExchange(SyncState& s)
+    {
+        s.plan                = exchangePlan(rank_, P_, s.cut, s.rows);
+        const ExchangePlan& e = s.plan;
+        if (e.failedRank >= 0) return agreed(e.failedRank);
+        if (e.badRank >= 0 && e.badArriving == 0)
+            return fail(ctx_, CSTONE_E_ARG, "domain_mr_sync: rank %d is left without particles", e.badRank);
+        if (e.badRank >= 0) return fail(ctx_, CSTONE_E_ARG, "domain_mr_sync: too many particles for rank %d", e.badRank);
+        s.keptKeys = keys_.as<K>() + s.cut[rank_];
+        s.keptO    = order_.as<uint32_t>() + s.cut[rank_];
+        s.nm       = e.na + e.nb;
+        return CSTONE_OK;
+    }
+
+    //! C3: leaving particles are packed through the ordering as (x, y, z, h) rows, ONE all_to_all_v
+    int exchangeParticles(SyncState& s)
+    {
+        const uint64_t mSend = s.plan.mSend;
+        if (!s.plan.movedAny) return CSTONE_OK;
+        CS_TRY(leaving_.ensure(ctx_, std::max<size_t>(mSend, 1) * sizeof(uint32_t)));
+        CS_TRY(sendRows_.ensure(ctx_, std::max<size_t>(mSend, 1) * 4 * sizeof(T)));
+        CS_TRY(recvRows_.ensure(ctx_, std::max<size_t>(s.plan.nb, 1) * 4 * sizeof(T)));
+        size_t nLow = s.cut[rank_] - s.cut[0], nHigh = s.cut[P_] - s.cut[rank_ + 1];
+        if (nLow)
+            CS_HIP(ctx_, hipMemcpyAsync(leaving_.p, order_.as<uint32_t>() + s.cut[0], nLow * 4, hipMemcpyDeviceToDevice,
+                                        ctx_->stream));
+        if (nHigh)
+            CS_HIP(ctx_, hipMemcpyAsync(leaving_.as<uint32_t>() + nLow, order_.as<uint32_t>() + s.cut[rank_ + 1], nHigh * 4,
+                                        hipMemcpyDeviceToDevice, ctx_->stream));
+        if (mSend)
+            hipLaunchKernelGGL(packRowsKernel<T>, gridFor(mSend, 256), 256, 0, ctx_->stream, leaving_.as<uint32_t>(),
+                               size_t(mSend), s.x, s.y, s.z, s.h, sendRows_.as<T>());
+        const std::vector<size_t> sb = peerBytes(s.plan.sendCounts.data(), 1, 4 * sizeof(T)),
+                                  rbv = peerBytes(s.plan.matrix.data() + rank_, P_, 4 * sizeof(T));
+        return callComm(comm_.all_to_all_v(comm_.user, sendRows_.p, sb.data(), recvRows_.p, rbv.data()), "all_to_all_v (particles)");
+    }
+
+    //! newcomers: sorted among themselves
+    int sortNewcomers(SyncState& s)
+    {
+        const uint64_t nb = s.plan.nb;
+        if (!nb) return CSTONE_OK;
+        for (int c = 0; c < 4; ++c)
+        {
+            CS_TRY(rcol_[c].ensure(ctx_, nb * sizeof(T)));
+            CS_TRY(rcolS_[c].ensure(ctx_, nb * sizeof(T)));
+        }
+        hipLaunchKernelGGL(unpackRowsKernel<T>, gridFor(nb, 256), 256, 0, ctx_->stream, recvRows_.as<T>(), size_t(nb),
+                           rcol_[0].as<T>(), rcol_[1].as<T>(), rcol_[2].as<T>(), rcol_[3].as<T>());
+        CS_TRY(rk_.ensure(ctx_, nb * sizeof(K)));
+        CS_TRY(ro_.ensure(ctx_, nb * sizeof(uint32_t)));
+        CS_TRY(ensureSortScratch(std::max<size_t>({s.n, 64, nb})));
+        CS_HIP(ctx_, hipMemsetAsync(rk_.p, 0, nb * sizeof(K), ctx_->stream));
+        CS_TRY(cstone_hip_compute_sfc_keys(ctx_, curve_, kb, rb, rcol_[0].p, rcol_[1].p, rcol_[2].p, rk_.p, nb, &box_));
+        CS_TRY(cstone_hip_sort_keys_ordering(ctx_, kb, rk_.p, ro_.as<uint32_t>(), nb, keysAlt_.p, orderAlt_.as<uint32_t>(),
+                                             sortTmp_.p, sortTmp_.bytes));
+        for (int c = 0; c < 4; ++c) // (rcolS_: in the newcomers' sorted order)
+            CS_TRY(cstone_hip_gather(ctx_, sizeof(T), ro_.as<uint32_t>(), nb, rcol_[c].p, rcolS_[c].p));
+        return CSTONE_OK;
+    }
+
+    //! further conserved fields travel the same way, one collective per field (the volume is small in the steady state);
+    //! received values are brought into the newcomers' sorted order (propRecvS_)
+    int exchangeProperties(SyncState& s)
+    {
+        const ExchangePlan& e = s.plan;
+        for (int q = 0; q < s.numProps && e.movedAny; ++q)
+        {
+            const size_t b = size_t(s.propBytes[q]);
+            const std::vector<size_t> sb = peerBytes(e.sendCounts.data(), 1, b), rbv = peerBytes(e.matrix.data() + rank_, P_, b);
+            CS_TRY(sendRows_.ensure(ctx_, std::max<size_t>(e.mSend, 1) * b));
+            CS_TRY(propRecv_[q].ensure(ctx_, std::max<size_t>(e.nb, 1) * b));
+            CS_TRY(propRecvS_[q].ensure(ctx_, std::max<size_t>(e.nb, 1) * b));
+            if (e.mSend) CS_TRY(cstone_hip_gather(ctx_, int(b), leaving_.as<uint32_t>(), e.mSend, s.props[q], sendRows_.p));
+            CS_TRY(callComm(comm_.all_to_all_v(comm_.user, sendRows_.p, sb.data(), propRecv_[q].p, rbv.data()),
+                            "all_to_all_v (property)"));
+            if (e.nb) CS_TRY(cstone_hip_gather(ctx_, int(b), ro_.as<uint32_t>(), e.nb, propRecv_[q].p, propRecvS_[q].p));
+        }
+        return CSTONE_OK;
+    }
+
+    //! Result arrays.  The assigned block is written ONCE, at an offset M that leaves room for the halos of the lower ranks
+    //! (resultMargins, host_rules.hpp: their number is only known after the discovery); what is handed out starts below M
+    int reserveResultArrays(SyncState& s)
+    {
+        cur_ ^= 1; // the inputs may live in the other buffer set
+        toggled_ = true;
+        Out& o   = out_[cur_];
+        s.o      = &o;
+        const ResultMargins m = resultMargins(s.nm, prevLo_, prevHi_, firstCall_, P_ > 1 && !noMargin_);
+        s.M = m.M, s.cap = m.cap;
+        CS_TRY(o.keys.ensure(ctx_, s.cap * sizeof(K)));
+        for (DevBuf* b : {&o.x, &o.y, &o.z, &o.h})
+            CS_TRY(b->ensure(ctx_, s.cap * sizeof(T)));
+        for (int q = 0; q < s.numProps; ++q)
+            CS_TRY(o.props[q].ensure(ctx_, s.cap * size_t(s.propBytes[q])));
+        s.keysM = o.keys.as<K>() + s.M;
+        return CSTONE_OK;
+    }
+
+    //! the columns WHICH of the kept particles to their final slots (placeColumnsKernel), on the current stream
+    template<int WHICH>
+    void placeColumns(const SyncState& s, T* const* dst)
+    {
+        if (!s.plan.na) return;
+        StageTimer timer(ctx_, CSTONE_STAGE_PLACE);
+        hipLaunchKernelGGL((placeColumnsKernel<K, T, WHICH>), gridFor(s.plan.na, 256, PLACE_PER), 256, 0, ctx_->stream, s.keptO,
+                           s.plan.nb ? posA_.as<uint32_t>() : nullptr, size_t(s.plan.na), s.keptKeys, s.x, s.y, s.z, s.h,
+                           s.keysM, dst[0], dst[1], dst[2], dst[3]);
+    }
+
+    //! merge of the kept, already sorted range with the newcomers: positions, then every field from its input slot
+    //! straight to its final slot
+    int mergeAndPlace(SyncState& s)
+    {
+        Out& o            = *s.o;
+        const uint64_t na = s.plan.na, nb = s.plan.nb, M = s.M;
+        if (nb)
+        {
+            CS_TRY(posA_.ensure(ctx_, std::max<size_t>(na, 1) * sizeof(uint32_t)));
+            CS_TRY(posB_.ensure(ctx_, nb * sizeof(uint32_t)));
+            CS_TRY(cstone_hip_merge_positions(ctx_, kb, s.keptKeys, na, rk_.p, nb, 0, posA_.as<uint32_t>(),
+                                              posB_.as<uint32_t>()));
+            CS_TRY(cstone_hip_scatter(ctx_, sizeof(K), posB_.as<uint32_t>(), nb, rk_.p, s.keysM));
+        }
+        T* dst[4] = {o.x.as<T>() + M, o.y.as<T>() + M, o.z.as<T>() + M, o.h.as<T>() + M};
+        // keys and h first: the locally essential tree and the halo discovery work on them.  x, y, z are not read before the
+        // halo exchange: they go out on the context's second stream, next to the tree update, and are joined by joinPlace
+        const bool overlap = useLet_ && overlapPlace_ && !s.massBits; // (syncGrav reads x, y, z for the mass centres)
+        if (overlap) CS_TRY(ensureAuxStream(ctx_));
+        if (overlap) placeColumns<1>(s, dst);
+        else placeColumns<0>(s, dst);
+        if (nb) CS_TRY(cstone_hip_scatter(ctx_, sizeof(T), posB_.as<uint32_t>(), nb, rcolS_[3].p, dst[3]));
+        if (overlap)
+        {
+            CS_HIP(ctx_, hipEventRecord(ctx_->evFork, ctx_->stream));
+            CS_HIP(ctx_, hipStreamWaitEvent(ctx_->aux, ctx_->evFork, 0));
+            int rc = CSTONE_OK;
+            {
+                StreamScope scope(ctx_, ctx_->aux);
+                placeColumns<2>(s, dst);
+                for (int c = 0; c < 3 && nb && rc == CSTONE_OK; ++c)
+                    rc = cstone_hip_scatter(ctx_, sizeof(T), posB_.as<uint32_t>(), nb, rcolS_[c].p, dst[c]);
+            }
+            CS_TRY(rc);
+            CS_HIP(ctx_, hipEventRecord(ctx_->evJoin, ctx_->aux));
+            placeForked_  = true;
+            ctx_->auxBusy = true;
+        }
+        for (int c = 0; c < 3 && nb && !overlap; ++c)
+            CS_TRY(cstone_hip_scatter(ctx_, sizeof(T), posB_.as<uint32_t>(), nb, rcolS_[c].p, dst[c]));
+        for (int q = 0; q < s.numProps; ++q)
+        {
+            const int b = s.propBytes[q];
+            char* to    = o.props[q].as<char>() + M * b;
+            if (nb)
+            {
+                CS_TRY(cstone_hip_gather_scatter(ctx_, b, s.keptO, posA_.as<uint32_t>(), na, s.props[q], to));
+                CS_TRY(cstone_hip_scatter(ctx_, b, posB_.as<uint32_t>(), nb, propRecvS_[q].p, to));
+            }
+            else { CS_TRY(cstone_hip_gather(ctx_, b, s.keptO, na, s.props[q], to)); }
+        }
+        return CSTONE_OK;
+    }
+
+    //! the pinned block the level ranges of this sync's tree travel to; the NEXT sync looks at it (takeLevelRanges)
+    int ensureHostLevelRange()
+    {
+        if (!hostLevelRange_)
+            CS_HIP(ctx_, hipHostMalloc(reinterpret_cast<void**>(&hostLevelRange_), 32 * sizeof(NodeIdx), hipHostMallocDefault));
+        return CSTONE_OK;
+    }
+
+    //! The reference's way (R/domain/domain.hpp:217-237): peers, locally essential tree, halo discovery on it, key-range
+    //! requests to the owners -- csrc/let.hpp, which carries the status word on its count exchanges.  h: in SFC order
+    int updateLet(SyncState& s)
+    {
+        Out& o           = *s.o;
+        const uint64_t M = s.M, nm = s.nm;
+        if (!let_) let_ = std::make_unique<FocusLet<K, T>>(ctx_, curve_, rank_, P_, bucketFocus_, theta_, comm_);
+        injectFailure("exchange");
+        int rc;
+        if (s.massBits)
+        {
+            const DevBuf& masses = o.props[s.numProps - 1];
+            const char* mSorted  = masses.as<char>() + M * size_t(s.massBits / 8);
+            rc = let_->updateGrav(box_, s.keysM, size_t(nm), assignment_.data(), gTree_.as<K>(), gHost_.leaves.data(),
+                                  gCounts_.as<uint32_t>(), gLeaves_, o.x.as<T>() + M, o.y.as<T>() + M, o.z.as<T>() + M, mSorted,
+                                  s.massBits, o.h.as<T>() + M, haloExt_, &centerDriftTol_, pending_ ? rank_ + 1 : 0, gTreeSame_);
+            haveExpansionCenters_ = rc == CSTONE_OK;
+        }
+        else
+        {
+            rc = let_->update(box_, s.keysM, size_t(nm), assignment_.data(), gTree_.as<K>(), gCounts_.as<uint32_t>(),
+                              gLeaves_, o.h.as<T>() + M, haloExt_, pending_ ? rank_ + 1 : 0, gTreeSame_);
+            haveExpansionCenters_ = false;
+        }
+        if (rc != CSTONE_OK)
+        {
+            // (a failure of my own that the status word of the tree's last count exchange has told everybody about:
+            //  reported with its own message)
+            if (pending_) return agreed(rank_);
+            if (toggled_) cur_ ^= 1, toggled_ = false;
+            return rc;
+        }
+        if (uint64_t(let_->endIndex() - let_->startIndex()) != nm)
+            return fail(ctx_, CSTONE_E_INTERNAL, "domain_mr_sync: the focus tree counts %u assigned particles, %llu are here",
+                        let_->endIndex() - let_->startIndex(), (unsigned long long)nm);
+        s.nlo      = let_->startIndex();
+        s.nhi      = let_->numParticlesWithHalos() - let_->endIndex();
+        s.haloAny  = 1;
+        s.selTotal = let_->halosSent();
+        // the leaves of my own range and their offsets among my particles: what the next sync's re-sort starts from
+        s.first = let_->startCell(), s.last = let_->endCell();
+        fLeaves_      = let_->numLeaves();
+        resortTree_   = let_->leaves() + s.first;
+        resortLeaves_ = s.last - s.first;
+        CS_TRY(layout_.ensure(ctx_, size_t(resortLeaves_ + 1) * sizeof(uint32_t)));
+        CS_TRY(cstone_hip_increment(ctx_, 32, let_->layout() + s.first, layout_.p, size_t(resortLeaves_) + 1,
+                                    uint64_t(uint32_t(0u - uint32_t(s.nlo)))));
+        layoutParticles_ = nm;
+        layoutBox_       = box_;
+        CS_TRY(ensureHostLevelRange());
+        // (the level ranges came back with the layout: no copy of their own)
+        std::copy(let_->levelRangeHost().begin(), let_->levelRangeHost().end(), hostLevelRange_);
+        levelRangePending_ = true;
+        return CSTONE_OK;
+    }
+
+    //! owner-side mode: the tree's level ranges to the pinned block (for the NEXT sync) and the layout of its leaves
+    int layoutOwnTree(SyncState& s)
+    {
+        CS_TRY(ensureHostLevelRange());
+        CS_TRY(copyToPinned(ctx_, hostLevelRange_, fLevelRange_.p, (maxLevel<K>() + 2) * sizeof(NodeIdx)));
+        levelRangePending_ = true;
+        const int L = fLeaves_;
+        CS_TRY(layout_.ensure(ctx_, size_t(L + 1) * sizeof(uint32_t)));
+        CS_HIP(ctx_, hipMemsetAsync(layout_.p, 0, sizeof(uint32_t), ctx_->stream));
+        CS_TRY(cstone_hip_inclusive_scan_u32(ctx_, fCounts_.as<uint32_t>(), layout_.as<uint32_t>() + 1, size_t(L)));
+        layoutParticles_ = s.nm; // the next sync's re-sort starts from this layout: nm particles in this box
+        layoutBox_       = box_;
+        resortTree_      = fTree_.as<K>();
+        resortLeaves_    = fLeaves_;
+        return CSTONE_OK;
+    }
+
+    //! C4, owner side.  Result: sel_ (what I send), s.hsCounts, s.hmatrix and what follows from it
+    int discoverHalosOwnerSide(SyncState& s)
+    {
+        if (P_ > 1)
+        {
+            std::vector<uint64_t> boxCounts(P_);
+            uint64_t maxBoxes = 0;
+            CS_TRY(exportHaloBoxes(s, boxCounts, maxBoxes));
+            CS_TRY(oflags_.ensure(ctx_, size_t(fLeaves_) * sizeof(int32_t)));
+            if (maxBoxes && P_ <= 32 && !peerLoop_) { CS_TRY(overlapsAllPeers(s, maxBoxes)); }
+            else
+            {
+                CS_TRY(overlapsPeerByPeer(s, boxCounts, maxBoxes));
+                CS_TRY(countMatrix(s.hsCounts, s.hmatrix));
+            }
+        }
+        s.haloAny = std::accumulate(s.hmatrix.begin(), s.hmatrix.end(), uint64_t(0));
+        for (int p = 0; p < P_; ++p)
+            if (p != rank_) (p < rank_ ? s.nlo : s.nhi) += s.hmatrix[size_t(p) * P_ + rank_];
+        return CSTONE_OK;
+    }
+
+    //! my boxes to everybody: boxCounts[p] and the boxes of rank p in allBoxes_, each list padded to maxBoxes records
+    int exportHaloBoxes(SyncState& s, std::vector<uint64_t>& boxCounts, uint64_t& maxBoxes)
+    {
+        const int first = s.first, last = s.last, nLocal = last - first, L = fLeaves_;
+        CS_TRY(radii_.ensure(ctx_, size_t(L) * sizeof(float)));
+        CS_TRY(boxes_.ensure(ctx_, size_t(std::max(nLocal, 1)) * 32));
+        CS_TRY(boxFlags_.ensure(ctx_, size_t(nLocal + 1) * sizeof(uint32_t)));
+        const DevBuf& h = s.o->h;
+        CS_TRY(cstone_hip_halo_radii(ctx_, rb, h.as<T>() + s.M, layout_.as<uint32_t>() + first, first, last, L,
+                                     haloExt_, radii_.as<float>()));
+        // only boxes that really reach a leaf outside my range are exported (a third to a tenth of those the
+        // enclosing-node test alone lets through: less to gather, fewer targets for every owner's traversal)
+        CS_TRY(cstone_hip_halo_boxes_foreign(ctx_, curve_, kb, rb, fPrefixes_.p, fChild_.as<int32_t>(), fItl_.as<int32_t>(),
+                                             fTree_.p, radii_.as<float>(), &box_, first, last, boxes_.as<int32_t>()));
+        hipLaunchKernelGGL(boxFlagsKernel, gridFor(nLocal, 256), 256, 0, ctx_->stream, boxes_.as<int32_t>(), nLocal,
+                           boxFlags_.as<uint32_t>());
+        uint32_t* total = scanTotal();
+        CS_TRY(exclusiveScanWithTotal(boxFlags_.as<uint32_t>(), nLocal, total));
+        // box counts of everybody straight from the device scalar (one read-back for mine and theirs), then the boxes
+        injectFailure("exchange");
+        statusW32_ = pending_ ? 1u : 0u; // second word: the status of this rank (a member: an asynchronous copy reads it)
+        CS_HIP(ctx_, hipMemcpyAsync(total + 1, &statusW32_, 4, hipMemcpyHostToDevice, ctx_->stream));
+        CS_TRY(callComm(comm_.all_gather(comm_.user, total, gatherRecv(), 8), "all_gather (box counts)"));
+        std::vector<uint32_t> c32(size_t(P_) * 2);
+        CS_TRY(copyToHost(ctx_, c32.data(), gatherRecv(), c32.size() * 4));
+        for (int p = 0; p < P_; ++p)
+        {
+            if (c32[2 * p + 1] != 0) return agreed(p);
+            boxCounts[p] = c32[2 * p];
+        }
+        s.numMyBoxes = boxCounts[rank_];
+        CS_TRY(myBoxes_.ensure(ctx_, size_t(std::max<uint64_t>(s.numMyBoxes, 1)) * 32));
+        hipLaunchKernelGGL(compactBoxesKernel, gridFor(nLocal, 256), 256, 0, ctx_->stream, boxes_.as<int32_t>(),
+                           boxFlags_.as<uint32_t>(), nLocal, rank_, myBoxes_.as<int32_t>());
+        maxBoxes = *std::max_element(boxCounts.begin(), boxCounts.end());
+        if (!maxBoxes) return CSTONE_OK;
+        const size_t mine = s.numMyBoxes * 32, longest = maxBoxes * 32; // bytes
+        CS_TRY(myBoxes_.ensure(ctx_, longest, true));
+        if (longest > mine) // padding records must read "no box"
+            CS_HIP(ctx_, hipMemsetAsync(myBoxes_.as<char>() + mine, 0, longest - mine, ctx_->stream));
+        CS_TRY(allBoxes_.ensure(ctx_, longest * P_));
+        return callComm(comm_.all_gather(comm_.user, myBoxes_.p, allBoxes_.p, longest), "all_gather (halo boxes)");
+    }
+
+    //! marks in oflags_ the leaves of [s.first, s.last) that one of numBoxes records touches
+    int findOverlaps(const SyncState& s, const int32_t* boxes, size_t numBoxes)
+    {
+        return cstone_hip_find_overlaps(ctx_, curve_, kb, fPrefixes_.p, fChild_.as<int32_t>(), fItl_.as<int32_t>(), fTree_.p,
+                                        boxes, int(numBoxes), s.first, s.last, oflags_.as<int32_t>());
+    }
+
+    //! all peers in one go: find_overlaps sets one bit per exporter (two calls: the records before and behind my own);
+    //! then counts, one scan, one fill.  My row of the count matrix goes from the device into the all-gather; one read-back
+    int overlapsAllPeers(SyncState& s, uint64_t maxBoxes)
+    {
+        const int first = s.first, last = s.last, nLocal = last - first, np = P_ - 1;
+        CS_HIP(ctx_, hipMemsetAsync(oflags_.p, 0, size_t(fLeaves_) * sizeof(int32_t), ctx_->stream));
+        if (rank_ > 0) CS_TRY(findOverlaps(s, allBoxes_.as<int32_t>(), size_t(rank_) * maxBoxes));
+        if (rank_ + 1 < P_)
+            CS_TRY(findOverlaps(s, allBoxes_.as<int32_t>() + size_t(rank_ + 1) * maxBoxes * 8,
+                                size_t(P_ - rank_ - 1) * maxBoxes));
+        const size_t items = size_t(np) * nLocal;
+        CS_TRY(cnt_.ensure(ctx_, (items + 1) * sizeof(uint32_t)));
+        hipLaunchKernelGGL(peerCountsKernel, gridFor(nLocal, 256), 256, 0, ctx_->stream, oflags_.as<int32_t>(),
+                           layout_.as<uint32_t>(), first, last, P_, rank_, cnt_.as<uint32_t>());
+        CS_TRY(exclusiveScanWithTotal(cnt_.as<uint32_t>(), int(items), scanTotal()));
+        hipLaunchKernelGGL(peerTotalsKernel, 1, 64, 0, ctx_->stream, cnt_.as<uint32_t>(), scanTotal(), nLocal, np, rank_,
+                           gatherRow());
+        CS_TRY(callComm(comm_.all_gather(comm_.user, gatherRow(), gatherRecv(), size_t(P_) * 8),
+                        "all_gather (halo counts)"));
+        CS_TRY(copyToHost(ctx_, s.hmatrix.data(), gatherRecv(), size_t(P_) * P_ * 8));
+        std::copy_n(s.hmatrix.begin() + size_t(rank_) * P_, P_, s.hsCounts.begin());
+        s.selTotal = std::accumulate(s.hsCounts.begin(), s.hsCounts.end(), uint64_t(0));
+        if (!s.selTotal) return CSTONE_OK;
+        CS_TRY(sel_.ensure(ctx_, s.selTotal * sizeof(uint32_t)));
+        hipLaunchKernelGGL(peerFillKernel, gridFor(items, 16), 256, 0, ctx_->stream, oflags_.as<int32_t>(),
+                           layout_.as<uint32_t>(), cnt_.as<uint32_t>(), first, last, P_, rank_, sel_.as<uint32_t>());
+        return CSTONE_OK;
+    }
+
+    //! more than 32 ranks (or CSTONE_MR_PEER_LOOP): one traversal, one scan, one read-back and one fill per peer
+    int overlapsPeerByPeer(SyncState& s, const std::vector<uint64_t>& boxCounts, uint64_t maxBoxes)
+    {
+        const int first = s.first, last = s.last, nLocal = last - first;
+        CS_TRY(cnt_.ensure(ctx_, size_t(nLocal + 1) * sizeof(uint32_t)));
+        for (int p = 0; p < P_; ++p)
+        {
+            if (p == rank_ || boxCounts[p] == 0) continue;
+            CS_HIP(ctx_, hipMemsetAsync(oflags_.p, 0, size_t(fLeaves_) * sizeof(int32_t), ctx_->stream));
+            CS_TRY(findOverlaps(s, allBoxes_.as<int32_t>() + size_t(p) * maxBoxes * 8, boxCounts[p]));
+            hipLaunchKernelGGL(flaggedCountsKernel, gridFor(nLocal, 256), 256, 0, ctx_->stream, oflags_.as<int32_t>(),
+                               layout_.as<uint32_t>(), first, last, cnt_.as<uint32_t>());
+            CS_TRY(exclusiveScanWithTotal(cnt_.as<uint32_t>(), nLocal, scanTotal()));
+            uint32_t tp = 0;
+            CS_TRY(copyToHost(ctx_, &tp, scanTotal(), 4));
+            if (tp)
+            {
+                CS_TRY(sel_.ensure(ctx_, (s.selTotal + tp) * sizeof(uint32_t), true));
+                hipLaunchKernelGGL(fillIndicesKernel, gridFor(nLocal, 16), 256, 0, ctx_->stream, oflags_.as<int32_t>(),
+                                   layout_.as<uint32_t>(), cnt_.as<uint32_t>(), first, last,
+                                   sel_.as<uint32_t>() + s.selTotal);
+            }
+            s.hsCounts[p] = tp;
+            s.selTotal += tp;
+        }
+        return CSTONE_OK;
+    }
+
+    //! x, y, z of the assigned block are needed from here on (a block that has to be moved, the halo exchange)
+    int joinPlace()
+    {
+        if (!placeForked_) return CSTONE_OK;
+        CS_HIP(ctx_, hipStreamWaitEvent(ctx_->stream, ctx_->evJoin, 0));
+        placeForked_  = false;
+        ctx_->auxBusy = false;
+        return CSTONE_OK;
+    }
+
+    //! the assigned block of one result array from slot s.M to slot M2 of an array of cap2 elements, through a scratch copy
+    int shiftBlock(const SyncState& s, DevBuf& buf, size_t elem, uint64_t M2, uint64_t cap2)
+    {
+        const size_t bytes = s.nm * elem;
+        CS_TRY(moveTmp_.ensure(ctx_, bytes));
+        CS_HIP(ctx_, hipMemcpyAsync(moveTmp_.p, buf.as<char>() + s.M * elem, bytes, hipMemcpyDeviceToDevice, ctx_->stream));
+        CS_TRY(buf.ensure(ctx_, cap2 * elem));
+        CS_HIP(ctx_, hipMemcpyAsync(buf.as<char>() + M2 * elem, moveTmp_.p, bytes, hipMemcpyDeviceToDevice, ctx_->stream));
+        return CSTONE_OK;
+    }
+
+    //! room for the halos on both sides of the assigned block (blockWithHalos, host_rules.hpp); margins that were too small
+    //! (first syncs, abrupt changes): the block is moved once
+    int makeRoomForHalos(SyncState& s)
+    {
+        const BlockWithHalos b = blockWithHalos(s.M, s.cap, s.nm, s.nlo, s.nhi);
+        if (b.move)
+        {
+            Out& o = *s.o;
+            CS_TRY(shiftBlock(s, o.keys, sizeof(K), b.M2, b.cap2));
+            for (DevBuf* f : {&o.x, &o.y, &o.z, &o.h})
+                CS_TRY(shiftBlock(s, *f, sizeof(T), b.M2, b.cap2));
+            for (int q = 0; q < s.numProps; ++q)
+                CS_TRY(shiftBlock(s, o.props[q], size_t(s.propBytes[q]), b.M2, b.cap2));
+        }
+        s.off   = b.off;
+        prevLo_ = s.nlo, prevHi_ = s.nhi;
+        return CSTONE_OK;
+    }
+
+    //! keys of `count` halo particles from slot `start` on (encode skips entries that hold the remove marker: clear first)
+    int encodeHaloKeys(Out& o, uint64_t start, uint64_t count)
+    {
+        if (!count) return CSTONE_OK;
+        CS_HIP(ctx_, hipMemsetAsync(o.keys.as<K>() + start, 0, count * sizeof(K), ctx_->stream));
+        return cstone_hip_compute_sfc_keys(ctx_, curve_, kb, rb, o.x.as<T>() + start, o.y.as<T>() + start,
+                                           o.z.as<T>() + start, o.keys.as<K>() + start, count, &box_);
+    }
+
+    //! C5: halos below | assigned | halos above; x, y, z and h travel together, then the keys of the halo particles
+    int exchangeHaloParticles(SyncState& s)
+    {
+        Out& o           = *s.o;
+        const uint64_t off = s.off, nlo = s.nlo, nhi = s.nhi, A = off + nlo, B = A + s.nm; // A: assigned, B: upper halos
+        if (P_ > 1 && useLet_)
+        {
+            // in the order of the focus tree's leaves (R/domain/domain.hpp:522-540), one message per peer instead of four
             void* xyzh[4] = {o.x.as<T>() + off, o.y.as<T>() + off, o.z.as<T>() + off, o.h.as<T>() + off};
             CS_TRY(let_->exchangeHalosRows(xyzh, 4, int(sizeof(T))));
-            if (nlo)
-            {
-                CS_HIP(ctx_, hipMemsetAsync(o.keys.as<K>() + off, 0, nlo * sizeof(K), ctx_->stream));
-                CS_TRY(cstone_hip_compute_sfc_keys(ctx_, curve_, kb, rb, o.x.as<T>() + off, o.y.as<T>() + off,
-                                                   o.z.as<T>() + off, o.keys.as<K>() + off, nlo, &box_));
-            }
-            if (nhi)
-            {
-                CS_HIP(ctx_, hipMemsetAsync(o.keys.as<K>() + A + nm, 0, nhi * sizeof(K), ctx_->stream));
-                CS_TRY(cstone_hip_compute_sfc_keys(ctx_, curve_, kb, rb, o.x.as<T>() + A + nm, o.y.as<T>() + A + nm,
-                                                   o.z.as<T>() + A + nm, o.keys.as<K>() + A + nm, nhi, &box_));
-            }
         }
-        else if (P_ > 1 && haloAny)
+        else if (P_ > 1 && s.haloAny)
         {
-            CS_TRY(sendRows_.ensure(ctx_, std::max<size_t>(selTotal, 1) * 4 * sizeof(T)));
+            CS_TRY(sendRows_.ensure(ctx_, std::max<size_t>(s.selTotal, 1) * 4 * sizeof(T)));
             CS_TRY(recvRows_.ensure(ctx_, std::max<size_t>(nlo + nhi, 1) * 4 * sizeof(T)));
-            if (selTotal)
-                hipLaunchKernelGGL(packRowsKernel<T>, gridFor(selTotal, 256), 256, 0, ctx_->stream, sel_.as<uint32_t>(),
-                                   size_t(selTotal), o.x.as<T>() + A, o.y.as<T>() + A, o.z.as<T>() + A,
-                                   o.h.as<T>() + A, sendRows_.as<T>());
-            CS_TRY(callComm(comm_.all_to_all_v(comm_.user, sendRows_.p, hSendBytes.data(), recvRows_.p,
-                                               hRecvBytes.data()),
-                            "all_to_all_v (halos)"));
+            if (s.selTotal)
+                hipLaunchKernelGGL(packRowsKernel<T>, gridFor(s.selTotal, 256), 256, 0, ctx_->stream, sel_.as<uint32_t>(),
+                                   size_t(s.selTotal), o.x.as<T>() + A, o.y.as<T>() + A, o.z.as<T>() + A, o.h.as<T>() + A,
+                                   sendRows_.as<T>());
+            const std::vector<size_t> sb = peerBytes(s.hsCounts.data(), 1, 4 * sizeof(T)),
+                                      rbv = peerBytes(s.hmatrix.data() + rank_, P_, 4 * sizeof(T));
+            CS_TRY(callComm(comm_.all_to_all_v(comm_.user, sendRows_.p, sb.data(), recvRows_.p, rbv.data()), "all_to_all_v (halos)"));
             if (nlo)
-                hipLaunchKernelGGL(unpackRowsKernel<T>, gridFor(nlo, 256), 256, 0, ctx_->stream, recvRows_.as<T>(),
-                                   size_t(nlo), o.x.as<T>() + off, o.y.as<T>() + off, o.z.as<T>() + off, o.h.as<T>() + off);
+                hipLaunchKernelGGL(unpackRowsKernel<T>, gridFor(nlo, 256), 256, 0, ctx_->stream, recvRows_.as<T>(), size_t(nlo),
+                                   o.x.as<T>() + off, o.y.as<T>() + off, o.z.as<T>() + off, o.h.as<T>() + off);
             if (nhi)
-                hipLaunchKernelGGL(unpackRowsKernel<T>, gridFor(nhi, 256), 256, 0, ctx_->stream,
-                                   recvRows_.as<T>() + 4 * nlo, size_t(nhi), o.x.as<T>() + A + nm,
-                                   o.y.as<T>() + A + nm, o.z.as<T>() + A + nm, o.h.as<T>() + A + nm);
-            // keys of the halo particles (encode skips entries that hold the remove marker: clear first)
-            if (nlo)
-            {
-                CS_HIP(ctx_, hipMemsetAsync(o.keys.as<K>() + off, 0, nlo * sizeof(K), ctx_->stream));
-                CS_TRY(cstone_hip_compute_sfc_keys(ctx_, curve_, kb, rb, o.x.as<T>() + off, o.y.as<T>() + off,
-                                                   o.z.as<T>() + off, o.keys.as<K>() + off, nlo, &box_));
-            }
-            if (nhi)
-            {
-                CS_HIP(ctx_, hipMemsetAsync(o.keys.as<K>() + A + nm, 0, nhi * sizeof(K), ctx_->stream));
-                CS_TRY(cstone_hip_compute_sfc_keys(ctx_, curve_, kb, rb, o.x.as<T>() + A + nm, o.y.as<T>() + A + nm,
-                                                   o.z.as<T>() + A + nm, o.keys.as<K>() + A + nm, nhi, &box_));
-            }
+                hipLaunchKernelGGL(unpackRowsKernel<T>, gridFor(nhi, 256), 256, 0, ctx_->stream, recvRows_.as<T>() + 4 * nlo,
+                                   size_t(nhi), o.x.as<T>() + B, o.y.as<T>() + B, o.z.as<T>() + B, o.h.as<T>() + B);
+        }
+        if (P_ > 1 && (useLet_ || s.haloAny))
+        {
+            CS_TRY(encodeHaloKeys(o, off, nlo));
+            CS_TRY(encodeHaloKeys(o, B, nhi));
         }
         CS_HIP(ctx_, hipGetLastError());
-        tick("8 halo exchange");
+        return CSTONE_OK;
+    }
 
+    //! the bookkeeping reapplySync / exchangeHalos / octree() work from, and the view
+    int finishSync(SyncState& s)
+    {
+        const ExchangePlan& e = s.plan;
+        const Out& o          = *s.o;
+        const uint64_t off = s.off, nlo = s.nlo, nhi = s.nhi, nm = s.nm;
         // the particle routes of this sync (reapplySync)
-        rsN_ = n, rsNa_ = na, rsNb_ = nb, rsSend_ = mSend, rsMoved_ = movedAny, rsKeptOffset_ = cut[rank_];
-        rsSendCounts_ = sendCounts;
-        rsRecvCounts_.assign(P_, 0);
+        rsN_ = s.n, rsNa_ = e.na, rsNb_ = e.nb, rsSend_ = e.mSend, rsMoved_ = e.movedAny, rsKeptOffset_ = s.cut[rank_];
+        rsSendCounts_ = e.sendCounts;
+        haloAnyLast_ = s.haloAny;
+        haloSend_ = s.hsCounts, haloRecvLo_ = nlo, haloRecvHi_ = nhi, haloAssigned_ = nm, haloSel_ = s.selTotal;
+        rsRecvCounts_.assign(P_, 0), haloRecv_.assign(P_, 0); // (what the others send me: my column of the two matrices)
         for (int p = 0; p < P_; ++p)
-            rsRecvCounts_[p] = p == rank_ ? 0 : matrix[size_t(p) * P_ + rank_];
-        haloAnyLast_ = haloAny;
-        haloSend_ = hsCounts, haloRecvLo_ = nlo, haloRecvHi_ = nhi, haloAssigned_ = nm, haloSel_ = selTotal;
-        haloRecv_.assign(P_, 0);
-        for (int p = 0; p < P_; ++p)
-            haloRecv_[p] = p == rank_ ? 0 : hmatrix[size_t(p) * P_ + rank_];
+            if (p != rank_) rsRecvCounts_[p] = e.matrix[size_t(p) * P_ + rank_], haloRecv_[p] = s.hmatrix[size_t(p) * P_ + rank_];
 
         firstCall_                     = false;
         view_.start_index              = uint32_t(nlo);
         view_.end_index                = uint32_t(nlo + nm);
-        view_.num_particles_with_halos = uint32_t(total);
+        view_.num_particles_with_halos = uint32_t(nlo + nm + nhi);
         view_.box                      = box_;
         view_.keys = o.keys.as<K>() + off;
         view_.x = o.x.as<T>() + off, view_.y = o.y.as<T>() + off, view_.z = o.z.as<T>() + off, view_.h = o.h.as<T>() + off;
         for (int q = 0; q < MAX_PROPS; ++q)
-            view_.props[q] = q < numProps ? static_cast<const void*>(o.props[q].as<char>() + off * propBytes[q]) : nullptr;
+            view_.props[q] = q < s.numProps ? static_cast<const void*>(o.props[q].as<char>() + off * s.propBytes[q]) : nullptr;
         view_.num_global_leaves = gLeaves_, view_.num_focus_leaves = fLeaves_;
         view_.global_leaves = gTree_.p, view_.global_counts = gCounts_.as<uint32_t>();
         view_.focus_leaves = fTree_.p, view_.focus_leaf_counts = fCounts_.as<uint32_t>();
@@ -1446,16 +1448,15 @@ public:
             view_.layout = let_->layout(), view_.halo_flags = let_->haloFlags();
         }
         view_.range_start = uint64_t(assignment_[rank_]), view_.range_end = uint64_t(assignment_[rank_ + 1]);
-        view_.particles_sent      = mSend;
+        view_.particles_sent      = e.mSend;
         view_.halos_received      = nlo + nhi;
-        view_.halos_sent          = selTotal;
-        view_.halo_boxes_exported = numMyBoxes;
+        view_.halos_sent          = s.selTotal;
+        view_.halo_boxes_exported = s.numMyBoxes;
         view_.resorts             = uint64_t(resorts_);
         // the sticky device-side error word: a sync that tripped a device-side check must not report success
         return cstone_hip_ctx_sync(ctx_);
     }
 
-private:
     //! CSTONE_MR_TIMING=1: synchronising wall clock per phase, printed by rank 0 when the domain is destroyed
     void tick(const char* name)
     {
@@ -1519,13 +1520,7 @@ private:
 
     int callComm(int rc, const char* what)
     {
-        if (rc != 0) return fail(ctx_, CSTONE_E_INTERNAL, "collective %s failed with code %d", what, rc);
-        return CSTONE_OK;
-    }
-
-    int toHost(void* dst, const void* src, size_t bytes)
-    {
-        return copyToHost(ctx_, dst, src, bytes); // (any host memory; synchronises the stream)
+        return rc == 0 ? CSTONE_OK : fail(ctx_, CSTONE_E_INTERNAL, "collective %s failed with code %d", what, rc);
     }
 
     int ensureSortScratch(size_t n)
@@ -1559,11 +1554,10 @@ private:
             matrix[0] = mine[0];
             return CSTONE_OK;
         }
-        uint64_t* send = scal_.as<uint64_t>() + 32;
-        uint64_t* recv = reinterpret_cast<uint64_t*>(scal_.as<char>() + 4096);
+        uint64_t *send = gatherRow(), *recv = gatherRecv();
         CS_HIP(ctx_, hipMemcpyAsync(send, mine.data(), size_t(P_) * 8, hipMemcpyHostToDevice, ctx_->stream));
         CS_TRY(callComm(comm_.all_gather(comm_.user, send, recv, size_t(P_) * 8), "all_gather (counts)"));
-        return toHost(matrix.data(), recv, size_t(P_) * P_ * 8);
+        return copyToHost(ctx_, matrix.data(), recv, size_t(P_) * P_ * 8);
     }
 
     // ---- C1
@@ -1573,10 +1567,8 @@ private:
         if (box_.bc[0] == 1 && box_.bc[1] == 1 && box_.bc[2] == 1) return CSTONE_OK;
         // (lo, -hi) per axis stay on the device from the reduction over the particles through the MIN all-reduce over
         // the ranks; one read-back at the end
-        static const double nothing[6] = {std::numeric_limits<double>::infinity(), std::numeric_limits<double>::infinity(),
-                                          std::numeric_limits<double>::infinity(), std::numeric_limits<double>::infinity(),
-                                          std::numeric_limits<double>::infinity(), std::numeric_limits<double>::infinity()};
-        double* dev = scal_.as<double>();
+        static const double inf = std::numeric_limits<double>::infinity(), nothing[6] = {inf, inf, inf, inf, inf, inf};
+        double* dev = boxOperand();
         if (n)
         {
             const void* arrays[3] = {x, y, z};
@@ -1589,12 +1581,11 @@ private:
         return CSTONE_OK;
     }
 
-    /*! dev: (lo, -hi) of this rank's particles per axis, six doubles on the device, room for a seventh.  All-reduces them
-     *  with the status word, reads them back and applies the box rule to box_ -> *next (box_ itself is not changed). */
     //! seventh value of the box reduction: the status of this rank (0, or -(rank + 1) if it has a failure pending)
     double statusWord() const { return pending_ ? -double(rank_ + 1) : 0.0; }
 
-    /*! MIN over the ranks of dev[0..6] = (min, -max) per axis + status.  statusSet: the operand is complete (the kernel
+    /*! MIN over the ranks of dev[0..6] = (min, -max) per axis + status, read back and put through the box rule: box_ ->
+     *  *next (box_ itself is not changed).  statusSet: the operand is complete (the kernel
      *  that wrote the extents wrote the status too); counters: four ints behind the operand come back in the same copy */
     int reduceBox(double* dev, cstone_box* next, bool statusSet = false, int* counters = nullptr)
     {
@@ -1605,7 +1596,7 @@ private:
         }
         if (P_ > 1) CS_TRY(callComm(comm_.all_reduce(comm_.user, dev, 7, 0, 1), "all_reduce (box)"));
         double ext[9];
-        CS_TRY(toHost(ext, dev, counters ? sizeof ext : 7 * sizeof(double)));
+        CS_TRY(copyToHost(ctx_, ext, dev, counters ? sizeof ext : 7 * sizeof(double)));
         if (counters) std::memcpy(counters, ext + 7, 4 * sizeof(int));
         if (ext[6] < 0) return agreed(int(-ext[6]) - 1);
         double fit[6]; // (lo, -hi) -> {min, max}; limitBoxShrinking keeps the limits of the periodic axes
@@ -1713,11 +1704,11 @@ private:
     {
         const uint64_t end = uint64_t(endKey<K>());
         const uint64_t b[2] = {uint64_t(assignment_[rank_]), uint64_t(assignment_[rank_ + 1])};
-        uint64_t* dq = reinterpret_cast<uint64_t*>(scal_.as<char>() + 1024);
+        uint64_t* dq = leafQuery();
         hipLaunchKernelGGL(containingLeavesKernel<K>, 1, 64, 0, ctx_->stream, fTree_.as<K>(), fLeaves_,
                            K(std::min(b[0], end)), K(std::min(b[1], end)), dq);
         uint64_t q[6];
-        CS_TRY(toHost(q, dq, sizeof q));
+        CS_TRY(copyToHost(ctx_, q, dq, sizeof q));
         const int L = fLeaves_;
         // leaves to replace, in ascending order: (index, start, end, boundary keys strictly inside)
         struct Cut
@@ -1886,8 +1877,7 @@ private:
     bool ctxGone_   = false; // the destructor runs behind the context's destruction (cstone_hip_domain_mr_destroy)
     bool toggled_   = false; // this sync has switched to the other output buffer set already
     int pending_    = 0; // status of this rank inside sync(): 0, or the error code the peers have to learn about
-    uint64_t statusW64_ = 0; // staging of the status words that ride on the collectives (asynchronous copies read them)
-    uint32_t statusW32_ = 0;
+    uint32_t statusW32_ = 0; // staging of the status word that rides on the box counts (an asynchronous copy reads it)
     std::string pendingMsg_;
     bool timing_    = std::getenv("CSTONE_MR_TIMING") != nullptr;
     bool noMargin_  = std::getenv("CSTONE_MR_NO_MARGIN") != nullptr; // tests: no room left for halos, the block is moved

@@ -83,6 +83,68 @@ inline bool mayResort(int sortMode)
 }
 inline bool allDigits(int sortMode) { return sortMode == CSTONE_SORT_ALL_DIGITS || std::getenv("CSTONE_FULL_SORT") != nullptr; }
 
+/*! Who sends what to whom in the particle exchange of a multi-rank sync, from the cut points of the assignment in this
+ *  rank's sorted keys (P + 1) and the all-gathered rows of everybody's send counts (P rows of P + 1 words, word P = the
+ *  status of that rank; not read for P = 1).  Every rank derives the same failedRank / badRank from the same rows. */
+struct ExchangePlan
+{
+    std::vector<uint64_t> sendCounts, matrix; // what I send to rank p; matrix[src * P + dst]
+    int failedRank = -1;                      // first rank whose status word is set (nothing below is filled then)
+    int badRank    = -1;                      // first rank left without particles or with 2^30 or more ...
+    uint64_t badArriving = 0;                 // ... and how many arrive there
+    uint64_t movedAny = 0, mSend = 0, na = 0, nb = 0; // particles moving anywhere; that I send, keep and receive
+};
+inline ExchangePlan exchangePlan(int rank, int P, const std::vector<uint64_t>& cut, const std::vector<uint64_t>& rows)
+{
+    ExchangePlan e;
+    e.sendCounts.resize(P), e.matrix.assign(size_t(P) * P, 0);
+    for (int p = 0; p < P; ++p)
+        e.sendCounts[p] = cut[p + 1] - cut[p];
+    if (P == 1) e.matrix[0] = e.sendCounts[0];
+    for (int p = 0; p < P && P > 1; ++p)
+    {
+        if (rows[size_t(p) * (P + 1) + P] != 0) { e.failedRank = p; return e; }
+        std::copy_n(rows.begin() + size_t(p) * (P + 1), P, e.matrix.begin() + size_t(p) * P);
+    }
+    for (int q = 0; q < P; ++q)
+    {
+        uint64_t arriving = 0;
+        for (int p = 0; p < P; ++p)
+            arriving += e.matrix[size_t(p) * P + q];
+        if (arriving == 0 || arriving >= (uint64_t(1) << 30)) { e.badRank = q, e.badArriving = arriving; return e; }
+    }
+    for (int p = 0; p < P; ++p)
+    {
+        for (int q = 0; q < P; ++q)
+            if (p != q) e.movedAny += e.matrix[size_t(p) * P + q];
+        if (p != rank) e.mSend += e.sendCounts[p], e.nb += e.matrix[size_t(p) * P + rank];
+    }
+    e.na = e.sendCounts[rank];
+    return e;
+}
+
+/*! The result arrays of a multi-rank sync: the nm assigned particles are written once, at slot M of arrays of cap
+ *  elements, with room on both sides for the halos, whose number is only known later: twice those of the previous sync
+ *  (a quarter of nm on the first call) and a page.  M is a multiple of 4 elements: the assigned range the client passes
+ *  back as the next input then starts on a 16-byte boundary, which the next sync's vector loads need. */
+struct ResultMargins { uint64_t M, cap; };
+inline ResultMargins resultMargins(uint64_t nm, uint64_t prevLo, uint64_t prevHi, bool firstCall, bool margins)
+{
+    if (!margins) return {0, nm};
+    const uint64_t first = firstCall ? nm / 4 : 0;
+    const uint64_t M     = (std::max(2 * prevLo + 4096, first) + 3) & ~uint64_t(3);
+    return {M, M + nm + std::max(2 * prevHi + 4096, first)};
+}
+//! ... once nlo halos below and nhi above are known: the arrays handed out start at off; where the margins were too small
+//! the block must move to slot M2 (again a multiple of 4) of arrays of cap2 elements
+struct BlockWithHalos { bool move; uint64_t M2, cap2, off; };
+inline BlockWithHalos blockWithHalos(uint64_t M, uint64_t cap, uint64_t nm, uint64_t nlo, uint64_t nhi)
+{
+    if (nlo <= M && M + nm + nhi <= cap) return {false, M, cap, M - nlo};
+    const uint64_t M2 = (nlo + 3) & ~uint64_t(3);
+    return {true, M2, M2 + nm + nhi, M2 - nlo};
+}
+
 /*! One update step of the (small, replicated) GLOBAL tree on the host: the decision of nodeOp (tree.hip,
  *  R/tree/csarray.hpp:270-310) and the expansion of rebalanceKernel (R/tree/csarray.hpp:360-385), restated for the host
  *  copies of the leaf array and the all-reduced counts that the last sync read back anyway.  The device then only counts

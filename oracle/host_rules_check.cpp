@@ -4,6 +4,7 @@
 // a drift, the removal of most of a region and a collapse onto a clump.  Each step starts from the ORACLE's tree and
 // counts; the product must say "unchanged" exactly when the oracle's leaf array is unchanged and otherwise produce the
 // same array.  Every decision (merge, keep, split by 8 / 64 / 512 / 4096) must have been taken on the way.
+// exchangePlan and resultMargins / blockWithHalos (the multi-rank sync) are held against known answers written by hand.
 // Built by `make -C oracle rules` as host_rules_check and, with -fsanitize=address,undefined, host_rules_check_asan.
 #include <algorithm>
 #include <cstdint>
@@ -141,10 +142,94 @@ void check(unsigned bucket, size_t n, unsigned seed)
         if (r.tally[o] == 0) r.fail("a decision was never taken");
 }
 
+// ---- known answers for the two rules of the multi-rank sync that need no oracle (exchangePlan, resultMargins)
+
+int cases = 0;
+void expect(bool ok, const char* what)
+{
+    ++cases;
+    if (ok) return;
+    std::printf("HOST_RULES FAILED %s\n", what);
+    std::exit(1);
+}
+
+using Rows = std::vector<uint64_t>;
+bool planIs(const cship::ExchangePlan& e, uint64_t movedAny, uint64_t mSend, uint64_t na, uint64_t nb)
+{
+    return e.failedRank == -1 && e.badRank == -1 && e.movedAny == movedAny && e.mSend == mSend && e.na == na && e.nb == nb;
+}
+
+void checkExchangePlan()
+{
+    using cship::exchangePlan;
+    // one rank: the rows are not read, everything stays
+    cship::ExchangePlan e = exchangePlan(0, 1, {0, 10}, {});
+    expect(planIs(e, 0, 0, 10, 0) && e.sendCounts == Rows{10} && e.matrix == Rows{10}, "exchangePlan: one rank");
+    // three ranks, rows of send counts with their status word; each rank's cut points are the prefix sums of its row
+    const Rows rows{5, 2, 1, 0, /**/ 0, 7, 3, 0, /**/ 4, 0, 6, 0};
+    const Rows matrix{5, 2, 1, 0, 7, 3, 4, 0, 6};
+    e = exchangePlan(0, 3, {0, 5, 7, 8}, rows);
+    expect(planIs(e, 10, 3, 5, 4) && e.sendCounts == Rows{5, 2, 1} && e.matrix == matrix, "exchangePlan: rank 0 of 3");
+    e = exchangePlan(1, 3, {0, 0, 7, 10}, rows);
+    expect(planIs(e, 10, 3, 7, 2) && e.sendCounts == Rows{0, 7, 3} && e.matrix == matrix, "exchangePlan: rank 1 of 3");
+    e = exchangePlan(2, 3, {0, 4, 4, 10}, rows);
+    expect(planIs(e, 10, 4, 6, 4) && e.sendCounts == Rows{4, 0, 6} && e.matrix == matrix, "exchangePlan: rank 2 of 3");
+    Rows r = rows;
+    r[1 * 4 + 3] = 1; // rank 1 reports a failure
+    expect(exchangePlan(0, 3, {0, 5, 7, 8}, r).failedRank == 1, "exchangePlan: status word of rank 1");
+    r = rows;
+    r[0 * 4 + 1] = r[1 * 4 + 1] = 0; // nobody keeps or sends anything for rank 1
+    e = exchangePlan(2, 3, {0, 4, 4, 10}, r);
+    expect(e.failedRank == -1 && e.badRank == 1 && e.badArriving == 0, "exchangePlan: a rank that receives nothing");
+    r = rows;
+    r[0 * 4 + 2] = (uint64_t(1) << 30) - 9; // 2^30 arrive at rank 2
+    e = exchangePlan(0, 3, {0, 5, 7, 7 + r[2]}, r);
+    expect(e.failedRank == -1 && e.badRank == 2 && e.badArriving == uint64_t(1) << 30, "exchangePlan: a rank at 2^30");
+    --r[0 * 4 + 2];
+    expect(exchangePlan(0, 3, {0, 5, 7, 7 + r[2]}, r).badRank == -1, "exchangePlan: a rank at 2^30 - 1");
+}
+
+bool blockIs(const cship::BlockWithHalos& b, bool move, uint64_t M2, uint64_t cap2, uint64_t off)
+{
+    return b.move == move && b.M2 == M2 && b.cap2 == cap2 && b.off == off;
+}
+
+void checkResultMargins()
+{
+    using cship::blockWithHalos;
+    using cship::resultMargins;
+    // the first call: a quarter of the block on either side, M rounded up to 4 elements
+    cship::ResultMargins m = resultMargins(40006, 0, 0, true, true);
+    expect(m.M == 10004 && m.cap == 10004 + 40006 + 10001, "resultMargins: first call");
+    m = resultMargins(1000, 0, 0, true, true);
+    expect(m.M == 4096 && m.cap == 4096 + 1000 + 4096, "resultMargins: first call of a small rank");
+    // steady state: twice the halos of the previous sync and a page; the block fits
+    m = resultMargins(1000, 11, 7, false, true);
+    expect(m.M == 4120 && m.cap == 4120 + 1000 + 14 + 4096, "resultMargins: steady state");
+    expect(blockIs(blockWithHalos(m.M, m.cap, 1000, 12, 9), false, m.M, m.cap, m.M - 12), "blockWithHalos: fits");
+    // the lower side
+    expect(blockIs(blockWithHalos(m.M, m.cap, 1000, m.M, 9), false, m.M, m.cap, 0), "blockWithHalos: nlo == M");
+    expect(blockIs(blockWithHalos(m.M, m.cap, 1000, m.M + 1, 9), true, m.M + 4, m.M + 4 + 1000 + 9, 3),
+           "blockWithHalos: nlo == M + 1");
+    // the upper side
+    const uint64_t room = m.cap - m.M - 1000;
+    expect(blockIs(blockWithHalos(m.M, m.cap, 1000, 12, room), false, m.M, m.cap, m.M - 12), "blockWithHalos: up to cap");
+    expect(blockIs(blockWithHalos(m.M, m.cap, 1000, 12, room + 1), true, 12, 12 + 1000 + room + 1, 0),
+           "blockWithHalos: up to cap + 1");
+    // no margins: the block starts the arrays and moves as soon as there is a halo
+    m = resultMargins(1000, 11, 7, false, false);
+    expect(m.M == 0 && m.cap == 1000, "resultMargins: no margins");
+    expect(blockIs(blockWithHalos(0, 1000, 1000, 0, 0), false, 0, 1000, 0), "blockWithHalos: no margins, no halos");
+    expect(blockIs(blockWithHalos(0, 1000, 1000, 5, 2), true, 8, 1010, 3), "blockWithHalos: no margins, halos");
+}
+
 } // namespace
 
 int main()
 {
+    checkExchangePlan();
+    checkResultMargins();
+    std::printf("HOST_RULES exchangePlan and resultMargins: %d known answers\n", cases);
     // more than 64 x 512 keys: the root itself splits by 4096 at either bucket size
     check<uint32_t>(16, 40000, 1);
     check<uint32_t>(64, 40000, 2);

@@ -2,7 +2,8 @@
 stand-alone program against the oracle (oracle/host_rules_check.cpp): the update step of the global tree that every
 steady-state sync makes on the host must decide and rebalance like the oracle's update_octree, step by step from the
 root to convergence and on through a drift, a removal and a collapse, for 32- and 64-bit keys and buckets of 16 and 64,
-and must have taken every decision (merge, keep, split by 8, 64, 512, 4096) on the way.  Run as a plain build and as a
+and must have taken every decision (merge, keep, split by 8, 64, 512, 4096) on the way; the exchange plan and the
+margins of the result arrays of the multi-rank sync give the answers worked out by hand.  Run as a plain build and as a
 build of its own with -fsanitize=address,undefined."""
 import os
 import re
@@ -32,3 +33,5 @@ def test_global_tree_step_on_the_host_equals_the_oracle(built, exe):
     assert sorted((int(r[0]), int(r[1])) for r in runs) == [(32, 16), (32, 64), (64, 16), (64, 64)]
     for r in runs:
         assert all(int(c) > 0 for c in r[3:]), r
+    # exchangePlan and resultMargins / blockWithHalos of the multi-rank sync: every known answer was checked
+    assert re.search(r"HOST_RULES exchangePlan and resultMargins: 19 known answers", out), out[-3000:]
