@@ -246,7 +246,8 @@ public:
 
     /*! Barnes-Hut gravity on the focus tree (csrc/gravity.hip): the multipoles about the current expansion centres, then
      *  the group walk over the end_index particles.  The target groups follow from the sync's tree and are kept until
-     *  the next sync.  h: per-particle softening lengths laid out like x, or null. */
+     *  the next sync.  h: per-particle softening lengths laid out like x, or null.  order 3: the octupoles after the
+     *  multipoles, and the walk that takes both. */
     int computeGravity(const void* x, const void* y, const void* z, const void* m, const void* h, int massBits,
                        int order, double G, double eps2, void* ax, void* ay, void* az, void* phi) override
     {
@@ -276,6 +277,17 @@ public:
         CS_TRY(cstone_hip_upsweep_multipoles(ctx_, rb, massBits, x, y, z, m, fLti_.as<int32_t>() + I, L,
                                              layout_.as<uint32_t>(), int(maxLevel<K>()), levels, fChild_.as<int32_t>(),
                                              M, fExpansion_.p, fMultipoles_.p));
+        if (order == 3)
+        {
+            CS_TRY(fOctupoles_.ensure(ctx_, size_t(M) * 8 * sizeof(T)));
+            CS_TRY(cstone_hip_upsweep_octupoles(ctx_, rb, massBits, x, y, z, m, fLti_.as<int32_t>() + I, L,
+                                                layout_.as<uint32_t>(), int(maxLevel<K>()), levels,
+                                                fChild_.as<int32_t>(), M, fExpansion_.p, fMultipoles_.p, fOctupoles_.p));
+            return cstone_hip_compute_gravity_o3(ctx_, rb, massBits, x, y, z, m, h, 0, endIndex_, groups_.as<uint32_t>(),
+                                                 numGroups_, &box_, fChild_.as<int32_t>(), fItl_.as<int32_t>(),
+                                                 layout_.as<uint32_t>(), fExpansion_.p, fMultipoles_.p, fOctupoles_.p, 0,
+                                                 G, eps2, ax, ay, az, phi, nullptr, nullptr, nullptr);
+        }
         return cstone_hip_compute_gravity_h(ctx_, rb, massBits, x, y, z, m, h, 0, endIndex_, groups_.as<uint32_t>(),
                                             numGroups_, &box_, fChild_.as<int32_t>(), fItl_.as<int32_t>(),
                                             layout_.as<uint32_t>(), fExpansion_.p, fMultipoles_.p, order, G, eps2, ax,
@@ -884,6 +896,7 @@ private:
     DevBuf fExpansion_;          // T[M][4]: centre of mass + MAC radius^2 per node (updateExpansionCenters)
     bool haveExpansion_ = false; // ... of the tree of the last sync
     DevBuf fMultipoles_;         // T[M][8]: multipoles about the expansion centres (computeGravity)
+    DevBuf fOctupoles_;          // T[M][8]: octupoles about them (computeGravity at order 3 only)
     DevBuf groups_;              // u32[numGroups_ + 1]: target groups of computeGravity, from the sync number groupsSync_
     uint32_t numGroups_ = 0, groupsSync_ = 0;
     DevBuf ops_, ops2_, leafOps_, layout_, radii_, flags_;

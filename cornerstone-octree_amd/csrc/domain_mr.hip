@@ -364,6 +364,7 @@ struct MrBase
     virtual int computeGravity(const void* x, const void* y, const void* z, const void* m, const void* h, int massBits,
                                int order, double G, double eps2, void* ax, void* ay, void* az, void* phi) = 0;
     virtual int multipoles(const void** out, int32_t* numNodes)                           = 0;
+    virtual int octupoles(const void** out, int32_t* numNodes)                            = 0;
     virtual int view(cstone_hip_domain_mr_view* out)                                     = 0;
     virtual void setHaloFactor(float f)                                                  = 0;
     virtual int exchangeHalos(void* array, int elemBytes)                                = 0;
@@ -541,7 +542,8 @@ public:
 
     /*! Barnes-Hut gravity on the locally essential tree (csrc/gravity.hip): the multipoles of every node of the focus
      *  tree about the current expansion centres (FocusLet::updateMultipoles, with its exchanges), then the LET walk over
-     *  the assigned particles.  x, y, z, m are laid out like the result arrays and read on the halo ranges too; the
+     *  the assigned particles (order 3: the octupoles with them, through the same exchanges once more).
+     *  x, y, z, m are laid out like the result arrays and read on the halo ranges too; the
      *  caller has exchanged the halos of m.  h (nullable): per-particle softening lengths laid out like x and read on the
      *  halo ranges too; the sync's h has them filled (sync: x, y, z and h travel in one halo message).  Whatever makes the call fail on its arguments is decided before the first
      *  collective, from state that is the same on every rank, so nobody is left waiting. */
@@ -560,7 +562,7 @@ public:
                                             "is not provided");
         // (a rank without particles may pass null arrays, like an empty rank of a sync)
         const bool null = view_.num_particles_with_halos > 0 && (!x || !y || !z || !m || !ax || !ay || !az);
-        if ((massBits != 32 && massBits != 64) || (order != 0 && order != 2) || !(eps2 >= 0.0) || null)
+        if ((massBits != 32 && massBits != 64) || (order != 0 && order != 2 && order != 3) || !(eps2 >= 0.0) || null)
             return fail(ctx_, CSTONE_E_ARG, "domain_mr_compute_gravity: bad argument");
         FocusLet<K, T>& t     = *let_;
         const uint32_t si = view_.start_index, ei = view_.end_index;
@@ -578,9 +580,15 @@ public:
         }
         CS_TRY(t.updateMultipoles(static_cast<const T*>(x) + si, static_cast<const T*>(y) + si,
                                   static_cast<const T*>(z) + si, static_cast<const char*>(m) + si * mb, massBits,
-                                  gTree_.as<K>(), gHost_.leaves.data(), gLeaves_));
+                                  gTree_.as<K>(), gHost_.leaves.data(), gLeaves_, order));
         if (ei == si) return CSTONE_OK;
         const size_t off = size_t(si) * sizeof(T);
+        if (order == 3)
+            return cstone_hip_compute_gravity_o3(
+                ctx_, rb, massBits, x, y, z, m, h, si, ei, gravGroups_.as<uint32_t>(), gravNumGroups_, &box_,
+                t.childOffsets(), t.internalToLeaf(), t.layout(), t.expansionCenters(), t.multipoles(), t.octupoles(), 1, G,
+                eps2, static_cast<char*>(ax) + off, static_cast<char*>(ay) + off, static_cast<char*>(az) + off,
+                phi ? static_cast<char*>(phi) + off : nullptr, nullptr, nullptr, nullptr);
         return cstone_hip_compute_gravity_let_h(
             ctx_, rb, massBits, x, y, z, m, h, si, ei, gravGroups_.as<uint32_t>(), gravNumGroups_, &box_, t.childOffsets(),
             t.internalToLeaf(), t.layout(), t.expansionCenters(), t.multipoles(), order, G, eps2,
@@ -592,6 +600,14 @@ public:
     {
         const bool have = useLet_ && let_ && !firstCall_ && haveExpansionCenters_;
         *out            = have ? let_->multipoles() : nullptr;
+        *numNodes       = have ? let_->numNodes() : 0;
+        return CSTONE_OK;
+    }
+
+    int octupoles(const void** out, int32_t* numNodes) override
+    {
+        const bool have = useLet_ && let_ && !firstCall_ && haveExpansionCenters_ && let_->octupoles();
+        *out            = have ? let_->octupoles() : nullptr;
         *numNodes       = have ? let_->numNodes() : 0;
         return CSTONE_OK;
     }
@@ -2059,6 +2075,12 @@ int cstone_hip_domain_mr_multipoles_get(cstone_hip_domain_mr* dom, const void** 
 {
     if (!dom || !multipoles || !num_nodes) return CSTONE_E_ARG;
     return dom->impl->multipoles(multipoles, num_nodes);
+}
+
+int cstone_hip_domain_mr_octupoles_get(cstone_hip_domain_mr* dom, const void** octupoles, int32_t* num_nodes)
+{
+    if (!dom || !octupoles || !num_nodes) return CSTONE_E_ARG;
+    return dom->impl->octupoles(octupoles, num_nodes);
 }
 
 int cstone_hip_domain_mr_sync(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z, const void* h,

@@ -28,6 +28,13 @@
 // H, force linear in d and phi = -G m (3 H^2 - r2) / (2 H^3), both continuous at r2 = H^2.  One sqrt and one division per
 // pair as before; h == 0 everywhere gives the Plummer rule's bits.  M2P keeps eps2 only.
 //
+// Octupoles (order 3): a second T[8] per node = (Oxxx, Oxxy, Oxxz, Oxyy, Oxyz, Oyyy, Oyyz, 0), the seven independent
+// components of the traceless symmetric rank-3 tensor O_abc = sum m (15 d_a d_b d_c - 3 |d|^2 (d_a delta_bc + d_b delta_ac
+// + d_c delta_ab)) about the same centre; Oxzz, Oyzz, Ozzz follow from the trace and are never formed.  The upsweep of a
+// level shifts the children's octupoles with their FINAL multipoles (M and Q enter the shift), so it runs after the
+// multipole upsweep.  The walk takes the order as a template parameter; order 3 adds one contraction per M2P and changes
+// no decision, so the counts are those of the other orders.
+//
 // Direct sum (cstone_hip_direct_gravity): one wave per 64 targets, the sources streamed through the same P2P tile, cut
 // into segments over gridDim.y whose partial sums a second kernel adds in segment order (no atomics).
 #include <algorithm>
@@ -135,6 +142,77 @@ __global__ __launch_bounds__(256) void upsweepMultipolesKernel(NodeIdx firstCell
     out[0] = M, out[1] = qxx, out[2] = qxy, out[3] = qxz, out[4] = qyy, out[5] = qyz, out[6] = qzz, out[7] = T(0);
 }
 
+//! octupole of every leaf from its particles, stored at its node index (layout as leafMultipolesKernel)
+template<class T, class Tm>
+__global__ __launch_bounds__(256) void leafOctupolesKernel(const T* __restrict__ x, const T* __restrict__ y,
+                                                           const T* __restrict__ z, const Tm* __restrict__ m,
+                                                           const NodeIdx* __restrict__ leafToInternal, NodeIdx numLeaves,
+                                                           const uint32_t* __restrict__ layout,
+                                                           const T* __restrict__ centers, T* __restrict__ oc)
+{
+    const NodeIdx leaf = blockIdx.x * 256 + threadIdx.x;
+    if (leaf >= numLeaves) return;
+    const NodeIdx n = leafToInternal[leaf];
+    const T cx = centers[4 * size_t(n)], cy = centers[4 * size_t(n) + 1], cz = centers[4 * size_t(n) + 2];
+    T oxxx = 0, oxxy = 0, oxxz = 0, oxyy = 0, oxyz = 0, oyyy = 0, oyyz = 0;
+    for (uint32_t i = layout[leaf]; i < layout[leaf + 1]; ++i)
+    {
+        const T w  = T(m[i]);
+        const T dx = x[i] - cx, dy = y[i] - cy, dz = z[i] - cz;
+        const T r2 = dx * dx + dy * dy + dz * dz;
+        const T tx = T(3) * r2 * dx, ty = T(3) * r2 * dy, tz = T(3) * r2 * dz;
+        oxxx += w * (T(15) * dx * dx * dx - T(3) * tx);
+        oxxy += w * (T(15) * dx * dx * dy - ty);
+        oxxz += w * (T(15) * dx * dx * dz - tz);
+        oxyy += w * (T(15) * dx * dy * dy - tx);
+        oxyz += w * (T(15) * dx * dy * dz);
+        oyyy += w * (T(15) * dy * dy * dy - T(3) * ty);
+        oyyz += w * (T(15) * dy * dy * dz - tz);
+    }
+    T* out = oc + 8 * size_t(n);
+    out[0] = oxxx, out[1] = oxxy, out[2] = oxxz, out[3] = oxyy, out[4] = oxyz, out[5] = oyyy, out[6] = oyyz, out[7] = T(0);
+}
+
+/*! one level of the octupole upsweep: internal nodes [firstCell, lastCell) from their 8 children shifted by
+ *  s = c_child - c_node: O' = O + 5 sym(s Q) - 2 sym(delta (Q s)) + M (15 s s s - 3 |s|^2 sym(s delta)); mp: the FINAL
+ *  multipoles of the children's level */
+template<class T>
+__global__ __launch_bounds__(256) void upsweepOctupolesKernel(NodeIdx firstCell, NodeIdx lastCell,
+                                                              const NodeIdx* __restrict__ childOffsets,
+                                                              const T* __restrict__ centers, const T* __restrict__ mp,
+                                                              T* __restrict__ oc)
+{
+    const NodeIdx cell = firstCell + blockIdx.x * 256 + threadIdx.x;
+    if (cell >= lastCell) return;
+    const NodeIdx child = childOffsets[cell];
+    if (!child) return;
+    const T cx = centers[4 * size_t(cell)], cy = centers[4 * size_t(cell) + 1], cz = centers[4 * size_t(cell) + 2];
+    T oxxx = 0, oxxy = 0, oxxz = 0, oxyy = 0, oxyz = 0, oyyy = 0, oyyz = 0;
+    for (int k = 0; k < 8; ++k)
+    {
+        const size_t c = size_t(child + k);
+        const T* q     = mp + 8 * c;
+        const T* o     = oc + 8 * c;
+        const T mc     = q[0];
+        const T qxx = q[1], qxy = q[2], qxz = q[3], qyy = q[4], qyz = q[5], qzz = q[6];
+        const T sx = centers[4 * c] - cx, sy = centers[4 * c + 1] - cy, sz = centers[4 * c + 2] - cz;
+        const T s2 = sx * sx + sy * sy + sz * sz;
+        const T qsx = qxx * sx + qxy * sy + qxz * sz;
+        const T qsy = qxy * sx + qyy * sy + qyz * sz;
+        const T qsz = qxz * sx + qyz * sy + qzz * sz;
+        const T tx = T(3) * s2 * sx, ty = T(3) * s2 * sy, tz = T(3) * s2 * sz;
+        oxxx += o[0] + T(15) * sx * qxx - T(6) * qsx + mc * (T(15) * sx * sx * sx - T(3) * tx);
+        oxxy += o[1] + T(5) * (T(2) * sx * qxy + sy * qxx) - T(2) * qsy + mc * (T(15) * sx * sx * sy - ty);
+        oxxz += o[2] + T(5) * (T(2) * sx * qxz + sz * qxx) - T(2) * qsz + mc * (T(15) * sx * sx * sz - tz);
+        oxyy += o[3] + T(5) * (sx * qyy + T(2) * sy * qxy) - T(2) * qsx + mc * (T(15) * sx * sy * sy - tx);
+        oxyz += o[4] + T(5) * (sx * qyz + sy * qxz + sz * qxy) + mc * (T(15) * sx * sy * sz);
+        oyyy += o[5] + T(15) * sy * qyy - T(6) * qsy + mc * (T(15) * sy * sy * sy - T(3) * ty);
+        oyyz += o[6] + T(5) * (T(2) * sy * qyz + sz * qyy) - T(2) * qsz + mc * (T(15) * sy * sy * sz - tz);
+    }
+    T* out = oc + 8 * size_t(cell);
+    out[0] = oxxx, out[1] = oxxy, out[2] = oxxz, out[3] = oxyy, out[4] = oxyz, out[5] = oyyy, out[6] = oyyz, out[7] = T(0);
+}
+
 /*! P2P of one tile: the cnt <= 64 sources that the lanes hold in (xl, yl, zl, ml[, hl]), source k being particle
  *  base + k, on the lane's target i; d = r_j - r_i, the target itself skipped.  The inner loop of the walk and of the
  *  direct sum: it touches no memory.  SOFT: the rule of the head of the file with H = hi + h_j */
@@ -178,15 +256,16 @@ __device__ __forceinline__ void p2pTile(T xl, T yl, T zl, T ml, T hl, int cnt, u
 
 /*! The walk of one target group per wave (see the head of the file).  Outputs are indexed by i - first; lanes without a
  *  target (the tail of a group) take the group's first particle as a stand-in and write nothing.  SOFT: h, indexed like
- *  x (by particle, not by i - first), softens the P2P pairs; without it h is not read. */
-template<class T, class Tm, bool QUAD, bool LET, bool SOFT>
+ *  x (by particle, not by i - first), softens the P2P pairs; without it h is not read.  ORDER: 0 monopole, 2 adds the
+ *  quadrupole, 3 the octupole as well (oc, read at order 3 only, through the scalar cache like mp). */
+template<class T, class Tm, int ORDER, bool LET, bool SOFT>
 __global__ __launch_bounds__(GW_BLOCK) void gravityWalkKernel(
     const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ z, const Tm* __restrict__ m, uint32_t first,
     uint32_t last, const uint32_t* __restrict__ groups, uint32_t numGroups, const NodeIdx* __restrict__ childOffsets,
     const NodeIdx* __restrict__ internalToLeaf, const uint32_t* __restrict__ layout, const T* __restrict__ centers,
     const T* __restrict__ mp, T G, T eps2, T* __restrict__ ax, T* __restrict__ ay, T* __restrict__ az,
     T* __restrict__ phi, uint32_t* __restrict__ p2pCounts, uint32_t* __restrict__ m2pCounts,
-    uint32_t* __restrict__ letCounts, int* __restrict__ errors, const T* __restrict__ h)
+    uint32_t* __restrict__ letCounts, int* __restrict__ errors, const T* __restrict__ h, const T* __restrict__ oc)
 {
     __shared__ NodeIdx stacks[GW_WAVES][GW_STACK];
     const int lane = int(threadIdx.x & 63u), wave = int(threadIdx.x >> 6);
@@ -265,7 +344,7 @@ __global__ __launch_bounds__(GW_BLOCK) void gravityWalkKernel(
                 const T rinv = T(1) / sqrt(r2);
                 const T rinv2 = rinv * rinv;
                 const T mr3   = M * rinv * rinv2;
-                if constexpr (QUAD)
+                if constexpr (ORDER >= 2)
                 {
                     const T qx  = q[1] * dx + q[2] * dy + q[3] * dz;
                     const T qy  = q[2] * dx + q[4] * dy + q[5] * dz;
@@ -277,6 +356,24 @@ __global__ __launch_bounds__(GW_BLOCK) void gravityWalkKernel(
                     ayi += r5 * qy - f * dy;
                     azi += r5 * qz - f * dz;
                     phii -= M * rinv + T(0.5) * dqd * r5;
+                    if constexpr (ORDER == 3)
+                    {
+                        // u_a = O_abc d_b d_c with Oxzz, Oyzz, Ozzz eliminated by the trace; w = u.d
+                        const T* o  = oc + 8 * size_t(node);
+                        const T xx = dx * dx - dz * dz, yy = dy * dy - dz * dz;
+                        const T xy = dx * dy, xz = dx * dz, yz = dy * dz;
+                        const T ux = o[0] * xx + o[3] * yy + T(2) * (o[1] * xy + o[2] * xz + o[4] * yz);
+                        const T uy = o[1] * xx + o[5] * yy + T(2) * (o[3] * xy + o[4] * xz + o[6] * yz);
+                        const T uz = o[2] * xx + o[6] * yy + T(2) * (o[4] * xy - (o[0] + o[3]) * xz - (o[1] + o[5]) * yz);
+                        const T w  = ux * dx + uy * dy + uz * dz;
+                        const T r7 = r5 * rinv2;
+                        const T hr = T(0.5) * r7;
+                        const T g  = (T(7) / T(6)) * w * r7 * rinv2;
+                        axi += hr * ux - g * dx;
+                        ayi += hr * uy - g * dy;
+                        azi += hr * uz - g * dz;
+                        phii -= (T(1) / T(6)) * w * r7;
+                    }
                 }
                 else
                 {
@@ -436,49 +533,91 @@ int upsweepMultipoles(cstone_hip_ctx* ctx, const void* x, const void* y, const v
     return upsweepLevels<T>(ctx, numLevels, levelRangeHost, childOffsets, centers, multipoles);
 }
 
-template<class T, class Tm, bool QUAD, bool LET, bool SOFT>
+//! the octupoles of the internal nodes of every level, deepest first; multipoles: already swept up
+template<class T>
+int upsweepOctupoleLevels(cstone_hip_ctx* ctx, int numLevels, const int32_t* levelRangeHost, const int32_t* childOffsets,
+                          const void* centers, const void* multipoles, void* octupoles)
+{
+    for (int level = numLevels - 1; level >= 0; --level)
+    {
+        const int first = levelRangeHost[level], last = levelRangeHost[level + 1];
+        if (last <= first) continue;
+        hipLaunchKernelGGL(upsweepOctupolesKernel<T>, gridFor(size_t(last - first), 256), 256, 0, ctx->stream, first,
+                           last, childOffsets, (const T*)centers, (const T*)multipoles, (T*)octupoles);
+    }
+    CS_HIP(ctx, hipGetLastError());
+    return CSTONE_OK;
+}
+
+template<class T, class Tm>
+int upsweepOctupoles(cstone_hip_ctx* ctx, const void* x, const void* y, const void* z, const void* m,
+                     const int32_t* leafToInternal, int numLeaves, const uint32_t* layout, int numLevels,
+                     const int32_t* levelRangeHost, const int32_t* childOffsets, const void* centers,
+                     const void* multipoles, void* octupoles)
+{
+    hipLaunchKernelGGL((leafOctupolesKernel<T, Tm>), gridFor(size_t(numLeaves), 256), 256, 0, ctx->stream, (const T*)x,
+                       (const T*)y, (const T*)z, (const Tm*)m, leafToInternal, numLeaves, layout, (const T*)centers,
+                       (T*)octupoles);
+    return upsweepOctupoleLevels<T>(ctx, numLevels, levelRangeHost, childOffsets, centers, multipoles, octupoles);
+}
+
+//! level_range_host must be num_levels + 1 ranges of [0, num_nodes)
+bool badLevelRanges(int num_levels, const int32_t* level_range_host, int num_nodes)
+{
+    for (int level = 0; level < num_levels; ++level)
+        if (level_range_host[level] < 0 || level_range_host[level + 1] < level_range_host[level] ||
+            level_range_host[level + 1] > num_nodes)
+            return true;
+    return false;
+}
+
+template<class T, class Tm, int ORDER, bool LET, bool SOFT>
 void launchWalk(cstone_hip_ctx* ctx, const void* x, const void* y, const void* z, const void* m, const void* h,
                 uint32_t first,
                 uint32_t last, const uint32_t* groups, uint32_t numGroups, const int32_t* childOffsets,
                 const int32_t* internalToLeaf, const uint32_t* layout, const void* centers, const void* multipoles,
-                double G, double eps2, void* ax, void* ay, void* az, void* phi, uint32_t* p2p, uint32_t* m2p,
-                uint32_t* letM2p)
+                const void* octupoles, double G, double eps2, void* ax, void* ay, void* az, void* phi, uint32_t* p2p,
+                uint32_t* m2p, uint32_t* letM2p)
 {
-    hipLaunchKernelGGL((gravityWalkKernel<T, Tm, QUAD, LET, SOFT>), gridFor(numGroups, GW_WAVES), GW_BLOCK, 0, ctx->stream,
+    hipLaunchKernelGGL((gravityWalkKernel<T, Tm, ORDER, LET, SOFT>), gridFor(numGroups, GW_WAVES), GW_BLOCK, 0, ctx->stream,
                        (const T*)x, (const T*)y, (const T*)z, (const Tm*)m, first, last, groups, numGroups, childOffsets,
                        internalToLeaf, layout, (const T*)centers, (const T*)multipoles, T(G), T(eps2), (T*)ax, (T*)ay,
-                       (T*)az, (T*)phi, p2p, m2p, letM2p, ctx->devScalars + 63, (const T*)h);
+                       (T*)az, (T*)phi, p2p, m2p, letM2p, ctx->devScalars + 63, (const T*)h, (const T*)octupoles);
 }
 
 template<class T, class Tm>
 int launchGravity(cstone_hip_ctx* ctx, const void* x, const void* y, const void* z, const void* m, const void* h,
                   uint32_t first, uint32_t last, const uint32_t* groups, uint32_t numGroups, const int32_t* childOffsets,
                   const int32_t* internalToLeaf, const uint32_t* layout, const void* centers, const void* multipoles,
-                  int order, bool let, double G, double eps2, void* ax, void* ay, void* az, void* phi, uint32_t* p2p,
-                  uint32_t* m2p, uint32_t* letM2p)
+                  const void* octupoles, int order, bool let, double G, double eps2, void* ax, void* ay, void* az,
+                  void* phi, uint32_t* p2p, uint32_t* m2p, uint32_t* letM2p)
 {
-#define CSTONE_WALK(QUAD, LET, SOFT)                                                                                   \
-    launchWalk<T, Tm, QUAD, LET, SOFT>(ctx, x, y, z, m, h, first, last, groups, numGroups, childOffsets, internalToLeaf, \
-                                       layout, centers, multipoles, G, eps2, ax, ay, az, phi, p2p, m2p, letM2p)
+#define CSTONE_WALK(ORDER, LET, SOFT)                                                                                  \
+    launchWalk<T, Tm, ORDER, LET, SOFT>(ctx, x, y, z, m, h, first, last, groups, numGroups, childOffsets,               \
+                                        internalToLeaf, layout, centers, multipoles, octupoles, G, eps2, ax, ay, az,   \
+                                        phi, p2p, m2p, letM2p)
     if (h)
     {
-        if (order == 2) { let ? CSTONE_WALK(true, true, true) : CSTONE_WALK(true, false, true); }
-        else { let ? CSTONE_WALK(false, true, true) : CSTONE_WALK(false, false, true); }
+        if (order == 3) { let ? CSTONE_WALK(3, true, true) : CSTONE_WALK(3, false, true); }
+        else if (order == 2) { let ? CSTONE_WALK(2, true, true) : CSTONE_WALK(2, false, true); }
+        else { let ? CSTONE_WALK(0, true, true) : CSTONE_WALK(0, false, true); }
     }
-    else if (order == 2) { let ? CSTONE_WALK(true, true, false) : CSTONE_WALK(true, false, false); }
-    else { let ? CSTONE_WALK(false, true, false) : CSTONE_WALK(false, false, false); }
+    else if (order == 3) { let ? CSTONE_WALK(3, true, false) : CSTONE_WALK(3, false, false); }
+    else if (order == 2) { let ? CSTONE_WALK(2, true, false) : CSTONE_WALK(2, false, false); }
+    else { let ? CSTONE_WALK(0, true, false) : CSTONE_WALK(0, false, false); }
 #undef CSTONE_WALK
     CS_HIP(ctx, hipGetLastError());
     return CSTONE_OK;
 }
 
-//! the checks and the dispatch behind cstone_hip_compute_gravity and cstone_hip_compute_gravity_let
+//! the checks and the dispatch behind cstone_hip_compute_gravity, cstone_hip_compute_gravity_let (octupoles == null,
+//! order 0 | 2) and cstone_hip_compute_gravity_o3 (order 3, which needs the octupoles)
 int computeGravity(cstone_hip_ctx* ctx, bool let, const char* name, int real_bits, int mass_bits, const void* x,
                    const void* y, const void* z, const void* m, const void* h, uint32_t first, uint32_t last,
                    const uint32_t* groups, uint32_t num_groups, const cstone_box* box_host, const int32_t* child_offsets,
                    const int32_t* internal_to_leaf, const uint32_t* layout, const void* expansion_centers,
-                   const void* multipoles, int order, double G, double eps2, void* ax, void* ay, void* az, void* phi,
-                   uint32_t* p2p_counts, uint32_t* m2p_counts, uint32_t* let_m2p_counts);
+                   const void* multipoles, const void* octupoles, int order, double G, double eps2, void* ax, void* ay,
+                   void* az, void* phi, uint32_t* p2p_counts, uint32_t* m2p_counts, uint32_t* let_m2p_counts);
 
 bool badBits(int bits) { return bits != 32 && bits != 64; }
 
@@ -486,10 +625,11 @@ int computeGravity(cstone_hip_ctx* ctx, bool let, const char* name, int real_bit
                    const void* y, const void* z, const void* m, const void* h, uint32_t first, uint32_t last,
                    const uint32_t* groups, uint32_t num_groups, const cstone_box* box_host, const int32_t* child_offsets,
                    const int32_t* internal_to_leaf, const uint32_t* layout, const void* expansion_centers,
-                   const void* multipoles, int order, double G, double eps2, void* ax, void* ay, void* az, void* phi,
-                   uint32_t* p2p_counts, uint32_t* m2p_counts, uint32_t* let_m2p_counts)
+                   const void* multipoles, const void* octupoles, int order, double G, double eps2, void* ax, void* ay,
+                   void* az, void* phi, uint32_t* p2p_counts, uint32_t* m2p_counts, uint32_t* let_m2p_counts)
 {
-    if (!ctx || badBits(real_bits) || badBits(mass_bits) || (order != 0 && order != 2) || !(eps2 >= 0.0) ||
+    const bool badOrder = order == 3 ? !octupoles : (order != 0 && order != 2);
+    if (!ctx || badBits(real_bits) || badBits(mass_bits) || badOrder || !(eps2 >= 0.0) ||
         last < first || !x || !y || !z || !m || (num_groups && !groups) || !box_host || !child_offsets ||
         !internal_to_leaf || !layout || !expansion_centers || !multipoles || !ax || !ay || !az)
         return fail(ctx, CSTONE_E_ARG, "%s: bad argument", name);
@@ -500,8 +640,8 @@ int computeGravity(cstone_hip_ctx* ctx, bool let, const char* name, int real_bit
         StageTimer timer(ctx, CSTONE_STAGE_GRAVITY);
 #define CSTONE_GRAVITY(T, Tm)                                                                                          \
     launchGravity<T, Tm>(ctx, x, y, z, m, h, first, last, groups, num_groups, child_offsets, internal_to_leaf, layout,     \
-                         expansion_centers, multipoles, order, let, G, eps2, ax, ay, az, phi, p2p_counts, m2p_counts,   \
-                         let_m2p_counts)
+                         expansion_centers, multipoles, octupoles, order, let, G, eps2, ax, ay, az, phi, p2p_counts,    \
+                         m2p_counts, let_m2p_counts)
         int rc;
         if (real_bits == 64) rc = mass_bits == 64 ? CSTONE_GRAVITY(double, double) : CSTONE_GRAVITY(double, float);
         else rc = mass_bits == 64 ? CSTONE_GRAVITY(float, double) : CSTONE_GRAVITY(float, float);
@@ -581,7 +721,7 @@ int cstone_hip_compute_gravity_h(cstone_hip_ctx* ctx, int real_bits, int mass_bi
 {
     return computeGravity(ctx, false, "compute_gravity", real_bits, mass_bits, x, y, z, m, h, first, last, groups,
                           num_groups, box_host, child_offsets, internal_to_leaf, layout, expansion_centers, multipoles,
-                          order, G, eps2, ax, ay, az, phi, p2p_counts, m2p_counts, nullptr);
+                          nullptr, order, G, eps2, ax, ay, az, phi, p2p_counts, m2p_counts, nullptr);
 }
 
 int cstone_hip_compute_gravity(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
@@ -606,7 +746,7 @@ int cstone_hip_compute_gravity_let_h(cstone_hip_ctx* ctx, int real_bits, int mas
 {
     return computeGravity(ctx, true, "compute_gravity_let", real_bits, mass_bits, x, y, z, m, h, first, last, groups,
                           num_groups, box_host, child_offsets, internal_to_leaf, layout, expansion_centers, multipoles,
-                          order, G, eps2, ax, ay, az, phi, p2p_counts, m2p_counts, let_m2p_counts);
+                          nullptr, order, G, eps2, ax, ay, az, phi, p2p_counts, m2p_counts, let_m2p_counts);
 }
 
 int cstone_hip_compute_gravity_let(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
@@ -685,6 +825,58 @@ int cstone_hip_upsweep_multipoles_nodes(cstone_hip_ctx* ctx, int real_bits, int 
     if (real_bits == 64)
         return upsweepLevels<double>(ctx, num_levels, level_range_host, child_offsets, expansion_centers, multipoles);
     return upsweepLevels<float>(ctx, num_levels, level_range_host, child_offsets, expansion_centers, multipoles);
+}
+
+int cstone_hip_upsweep_octupoles(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
+                                 const void* z, const void* m, const int32_t* leaf_to_internal, int num_leaves,
+                                 const uint32_t* layout, int num_levels, const int32_t* level_range_host,
+                                 const int32_t* child_offsets, int num_nodes, const void* expansion_centers,
+                                 const void* multipoles, void* octupoles)
+{
+    if (!ctx || badBits(real_bits) || badBits(mass_bits) || num_leaves < 1 || num_nodes < num_leaves || num_levels < 0 ||
+        !x || !y || !z || !m || !leaf_to_internal || !layout || !level_range_host || !child_offsets ||
+        !expansion_centers || !multipoles || !octupoles)
+        return fail(ctx, CSTONE_E_ARG, "upsweep_octupoles: bad argument");
+    if (badLevelRanges(num_levels, level_range_host, num_nodes))
+        return fail(ctx, CSTONE_E_ARG, "upsweep_octupoles: level_range_host is not a range of [0, num_nodes)");
+    StageTimer timer(ctx, CSTONE_STAGE_MULTIPOLES);
+#define CSTONE_UPSWEEP(T, Tm)                                                                                          \
+    upsweepOctupoles<T, Tm>(ctx, x, y, z, m, leaf_to_internal, num_leaves, layout, num_levels, level_range_host,       \
+                            child_offsets, expansion_centers, multipoles, octupoles)
+    if (real_bits == 64) return mass_bits == 64 ? CSTONE_UPSWEEP(double, double) : CSTONE_UPSWEEP(double, float);
+    return mass_bits == 64 ? CSTONE_UPSWEEP(float, double) : CSTONE_UPSWEEP(float, float);
+#undef CSTONE_UPSWEEP
+}
+
+int cstone_hip_upsweep_octupoles_nodes(cstone_hip_ctx* ctx, int real_bits, int num_levels,
+                                       const int32_t* level_range_host, const int32_t* child_offsets, int num_nodes,
+                                       const void* expansion_centers, const void* multipoles, void* octupoles)
+{
+    if (!ctx || badBits(real_bits) || num_levels < 0 || num_nodes < 1 || !level_range_host || !child_offsets ||
+        !expansion_centers || !multipoles || !octupoles)
+        return fail(ctx, CSTONE_E_ARG, "upsweep_octupoles_nodes: bad argument");
+    if (badLevelRanges(num_levels, level_range_host, num_nodes))
+        return fail(ctx, CSTONE_E_ARG, "upsweep_octupoles_nodes: level_range_host is not a range of [0, num_nodes)");
+    StageTimer timer(ctx, CSTONE_STAGE_MULTIPOLES);
+    if (real_bits == 64)
+        return upsweepOctupoleLevels<double>(ctx, num_levels, level_range_host, child_offsets, expansion_centers,
+                                             multipoles, octupoles);
+    return upsweepOctupoleLevels<float>(ctx, num_levels, level_range_host, child_offsets, expansion_centers, multipoles,
+                                        octupoles);
+}
+
+int cstone_hip_compute_gravity_o3(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
+                                  const void* z, const void* m, const void* h, uint32_t first, uint32_t last,
+                                  const uint32_t* groups, uint32_t num_groups, const cstone_box* box_host,
+                                  const int32_t* child_offsets, const int32_t* internal_to_leaf, const uint32_t* layout,
+                                  const void* expansion_centers, const void* multipoles, const void* octupoles, int let,
+                                  double G, double eps2, void* ax, void* ay, void* az, void* phi, uint32_t* p2p_counts,
+                                  uint32_t* m2p_counts, uint32_t* let_m2p_counts)
+{
+    return computeGravity(ctx, let != 0, "compute_gravity_o3", real_bits, mass_bits, x, y, z, m, h, first, last, groups,
+                          num_groups, box_host, child_offsets, internal_to_leaf, layout, expansion_centers, multipoles,
+                          octupoles, 3, G, eps2, ax, ay, az, phi, p2p_counts, m2p_counts,
+                          let ? let_m2p_counts : nullptr);
 }
 
 } // extern "C"

@@ -238,19 +238,29 @@ public:
      *  sum); the peers' regions from the peers; upsweep.  A multipole that arrives from another rank is about that
      *  rank's centre of the node, which is the centre this rank holds for it, because the same routes delivered it.  So
      *  the result is valid for the centres of the last updateGrav / updateExpansionCenters and must follow either.
-     *  Collective.  (Not instantiated by clients of this header that have no gravity entry points.) */
+     *  Collective.  (Not instantiated by clients of this header that have no gravity entry points.)
+     *  order 3: every stage runs a second time for the octupoles (csrc/gravity.hip), right after its multipole half, whose
+     *  result the octupole shift reads -- one more global and one more peer exchange.  Any other order touches no
+     *  octupole buffer and runs no extra collective. */
     int updateMultipoles(const T* x, const T* y, const T* z, const void* m, int massBits, const K* globalLeaves,
-                         const K* globalLeavesHost, int numGlobalLeaves)
+                         const K* globalLeavesHost, int numGlobalLeaves, int order = 2)
     {
         const int L = L_, M = numNodesOf(L), I = numInternalOf(L);
         const int e = int(8 * sizeof(T));
+        const bool o3 = order == 3; // every stage then runs for the octupoles too, after the multipoles it reads
         haveMultipoles_ = false;
+        haveOctupoles_  = false;
         LET_TRY(multipoles_.ensure(size_t(M) * e));
+        if (o3) LET_TRY(octupoles_.ensure(size_t(M) * e));
         uint32_t* lay = nullptr;
         LET_TRY(ownLayout(&lay));
         LET_TRY(readBack(levelRange_.as<int32_t>(), levelHost_, size_t(maxLevel) + 2));
         LET_TRY(cstone_hip_upsweep_multipoles(ctx_, rb, massBits, x, y, z, m, lti_.as<int32_t>() + I, L, lay, maxLevel,
                                               levelHost_, child_.as<int32_t>(), M, centers_.p, multipoles_.p));
+        if (o3)
+            LET_TRY(cstone_hip_upsweep_octupoles(ctx_, rb, massBits, x, y, z, m, lti_.as<int32_t>() + I, L, lay, maxLevel,
+                                                 levelHost_, child_.as<int32_t>(), M, centers_.p, multipoles_.p,
+                                                 octupoles_.p));
         if (P_ > 1)
         {
             const int GL = numGlobalLeaves;
@@ -265,15 +275,34 @@ public:
                                                                                       gChild_.as<int32_t>(), numNodesOf(GL),
                                                                                       gNodeCenters, nodeMp);
                                        }));
+            if (o3)
+            {
+                // the global nodes' multipoles of the exchange above, still in gMultipoles_ behind its [GL + 1] leaf values
+                const void* gNodeMp = gMultipoles_.as<char>() + size_t(GL + 1) * e;
+                LET_TRY(globalNodeExchange(globalLeaves, globalLeavesHost, GL, e, gOctupoles_, octupoles_.p,
+                                           [&](void* nodeOc)
+                                           {
+                                               return cstone_hip_upsweep_octupoles_nodes(
+                                                   ctx_, rb, maxLevel, gLevelHost_, gChild_.as<int32_t>(), numNodesOf(GL),
+                                                   gNodeCenters, gNodeMp, nodeOc);
+                                           }));
+            }
             LET_TRY(peerNodeExchange(e, multipoles_.p));
+            if (o3) LET_TRY(peerNodeExchange(e, octupoles_.p));
             LET_TRY(cstone_hip_upsweep_multipoles_nodes(ctx_, rb, maxLevel, levelHost_, child_.as<int32_t>(), M,
                                                         centers_.p, multipoles_.p));
+            if (o3)
+                LET_TRY(cstone_hip_upsweep_octupoles_nodes(ctx_, rb, maxLevel, levelHost_, child_.as<int32_t>(), M,
+                                                           centers_.p, multipoles_.p, octupoles_.p));
         }
         haveMultipoles_ = true;
+        haveOctupoles_  = o3;
         return CSTONE_OK;
     }
     //! T[numNodes()][8] of the last updateMultipoles, or null
     const T* multipoles() const { return haveMultipoles_ ? multipoles_.as<T>() : nullptr; }
+    //! T[numNodes()][8] octupoles of the last updateMultipoles if that was at order 3, else null
+    const T* octupoles() const { return haveMultipoles_ && haveOctupoles_ ? octupoles_.as<T>() : nullptr; }
 
     //! (centre of mass, MAC radius^2) of every node of the focus tree: Vec4<T>[numNodes()], after updateGrav
     const T* expansionCenters() const { return centers_.as<T>(); }
@@ -391,7 +420,8 @@ private:
                 &macs_, &centers_, &geoCenters_, &geoSizes_, &opsAll_, &ops_, &scratchKeys_, &scratchKeys2_, &scratchIdx_,
                 &scratchIdx2_, &scratchU64_, &gPrefixes_, &gChild_, &gParents_, &gLevelRange_, &gItl_, &gLti_, &treelets_,
                 &treeletIdx_, &tlFlags_, &tlScan_, &sendBuf_, &recvBuf_, &layout_, &flags_, &radii_, &rangeOffsets_,
-                &rangeScan_, &haloSend_, &haloRecv_, &rowBuf_, &gSeg_, &gCenters_, &multipoles_, &gMultipoles_};
+                &rangeScan_, &haloSend_, &haloRecv_, &rowBuf_, &gSeg_, &gCenters_, &multipoles_, &gMultipoles_,
+                &octupoles_, &gOctupoles_};
     }
 
     int fail(int code, const char* fmt, ...)
@@ -903,7 +933,7 @@ private:
         *done = true;
         if (oldStart == focusStart && oldEnd == focusEnd) return CSTONE_OK;
         const int L = L_, M = numNodesOf(L), I = numInternalOf(L);
-        haveMultipoles_ = false; // (they are about the centres this call replaces)
+        haveMultipoles_ = haveOctupoles_ = false; // (they are about the centres this call replaces)
         LET_TRY(centers_.ensure(size_t(M) * 4 * sizeof(T)));
         LET_TRY(cstone_hip_geo_mac_spheres(ctx_, curve_, kb, rb, prefixes_.p, M, centers_.p, invTheta, &box));
         LET_TRY(macs_.ensure(size_t(M)));
@@ -1282,7 +1312,7 @@ private:
                       const K* globalLeavesHost, int numGlobalLeaves)
     {
         const int L = L_, M = numNodesOf(L), I = numInternalOf(L);
-        haveMultipoles_ = false; // (they are about the centres this call replaces)
+        haveMultipoles_ = haveOctupoles_ = false; // (they are about the centres this call replaces)
         LET_TRY(centers_.ensure(size_t(M) * 4 * sizeof(T)));
         uint32_t* lay = nullptr;
         LET_TRY(ownLayout(&lay));
@@ -1607,7 +1637,8 @@ private:
     LetBuf gSeg_, gCenters_;                  // global centre exchange: my segment + everybody's, leaf and node centres
     int gCentersLeaves_ = -1;                 // global leaves of the last global centre exchange (gCenters_ is laid out for)
     LetBuf multipoles_, gMultipoles_;         // updateMultipoles: T[numNodes()][8], and the global exchange's store
-    bool haveMultipoles_ = false;
+    LetBuf octupoles_, gOctupoles_;           // the same two at order 3: (Oxxx, Oxxy, Oxxz, Oxyy, Oxyz, Oyyy, Oyyz, 0)
+    bool haveMultipoles_ = false, haveOctupoles_ = false;
     int32_t levelHost_[maxLevel + 2]  = {0};  // level ranges of the focus tree / the global tree on the host (upsweeps)
     int32_t gLevelHost_[maxLevel + 2] = {0};
 

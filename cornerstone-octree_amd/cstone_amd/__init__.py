@@ -65,6 +65,9 @@ EXPORTS = [
     # ... with per-particle softening lengths, and the all-pairs direct sum
     "cstone_hip_compute_gravity_h", "cstone_hip_compute_gravity_let_h", "cstone_hip_direct_gravity",
     "cstone_hip_domain_compute_gravity_h", "cstone_hip_domain_mr_compute_gravity_h",
+    # ... at order 3: the octupoles beside the multipoles
+    "cstone_hip_upsweep_octupoles", "cstone_hip_upsweep_octupoles_nodes", "cstone_hip_compute_gravity_o3",
+    "cstone_hip_domain_mr_octupoles_get",
 ]
 
 GRAVITY_GROUP_TOL = 2.0  # CSTONE_GRAVITY_GROUP_TOL: tol_factor of the target groups of cstone_hip_domain_compute_gravity
@@ -629,6 +632,65 @@ class Context:
             self._check_h(x, h)
             self._chk(self.lib.cstone_hip_compute_gravity_let_h(*head, _ptr(h), *tail), "compute_gravity_let_h")
         return ax, ay, az, phi, p2p, m2p, let
+
+    @staticmethod
+    def _host_levels(level_range):
+        return np.ascontiguousarray(np.asarray(level_range.cpu() if hasattr(level_range, "cpu") else level_range,
+                                               dtype=np.int32))
+
+    def upsweep_octupoles(self, x, y, z, m, leaf_to_internal, layout, level_range, child_offsets, expansion_centers,
+                          multipoles, octupoles=None):
+        """octupoles (num_nodes, 8) = (Oxxx, Oxxy, Oxxz, Oxyy, Oxyz, Oyyy, Oyyz, 0) about the expansion centres
+        (cstone_hip_upsweep_octupoles); multipoles: the result of upsweep_multipoles for the same tree and centres (read,
+        not written); the other arguments as for upsweep_multipoles"""
+        torch = _torch()
+        nn = expansion_centers.numel() // 4
+        levels = self._host_levels(level_range)
+        if octupoles is None:
+            octupoles = torch.zeros((nn, 8), dtype=x.dtype, device=x.device)
+        self._chk(self.lib.cstone_hip_upsweep_octupoles(
+            self.h, C.c_int(x.element_size() * 8), C.c_int(m.element_size() * 8), _ptr(x), _ptr(y), _ptr(z), _ptr(m),
+            _ptr(leaf_to_internal), C.c_int(layout.numel() - 1), _ptr(layout), C.c_int(levels.size - 1),
+            levels.ctypes.data_as(C.c_void_p), _ptr(child_offsets), C.c_int(nn), _ptr(expansion_centers),
+            _ptr(multipoles), _ptr(octupoles)), "upsweep_octupoles")
+        return octupoles
+
+    def upsweep_octupoles_nodes(self, level_range, child_offsets, expansion_centers, multipoles, octupoles):
+        """the internal-node part of upsweep_octupoles alone (cstone_hip_upsweep_octupoles_nodes): octupoles, whose leaf
+        rows are filled, gets its internal rows in place and is returned"""
+        nn = expansion_centers.numel() // 4
+        levels = self._host_levels(level_range)
+        self._chk(self.lib.cstone_hip_upsweep_octupoles_nodes(
+            self.h, C.c_int(octupoles.element_size() * 8), C.c_int(levels.size - 1), levels.ctypes.data_as(C.c_void_p),
+            _ptr(child_offsets), C.c_int(nn), _ptr(expansion_centers), _ptr(multipoles), _ptr(octupoles)),
+            "upsweep_octupoles_nodes")
+        return octupoles
+
+    def compute_gravity_o3(self, x, y, z, m, first, last, groups, box, child_offsets, internal_to_leaf, layout,
+                           expansion_centers, multipoles, octupoles, let=False, G=1.0, eps2=0.0, potential=True,
+                           counts=False, h=None):
+        """the walk at order 3 (cstone_hip_compute_gravity_o3): compute_gravity (let False) or compute_gravity_let (let
+        True) with the octupole term.  Returns (ax, ay, az, phi, p2p_counts, m2p_counts), and let_m2p_counts as a seventh
+        if let; h: as in compute_gravity"""
+        torch = _torch()
+        nt = last - first
+
+        def out(dt):
+            return torch.zeros(nt, dtype=dt, device=x.device)
+
+        ax, ay, az = out(x.dtype), out(x.dtype), out(x.dtype)
+        phi = out(x.dtype) if potential else None
+        p2p, m2p = (out(torch.int32), out(torch.int32)) if counts else (None, None)
+        letc = out(torch.int32) if counts and let else None
+        if h is not None:
+            self._check_h(x, h)
+        self._chk(self.lib.cstone_hip_compute_gravity_o3(
+            self.h, C.c_int(x.element_size() * 8), C.c_int(m.element_size() * 8), _ptr(x), _ptr(y), _ptr(z), _ptr(m),
+            _ptr(h), C.c_uint32(first), C.c_uint32(last), _ptr(groups), C.c_uint32(groups.numel() - 1), C.byref(box),
+            _ptr(child_offsets), _ptr(internal_to_leaf), _ptr(layout), _ptr(expansion_centers), _ptr(multipoles),
+            _ptr(octupoles), C.c_int(1 if let else 0), C.c_double(G), C.c_double(eps2), _ptr(ax), _ptr(ay), _ptr(az),
+            _ptr(phi), _ptr(p2p), _ptr(m2p), _ptr(letc)), "compute_gravity_o3")
+        return (ax, ay, az, phi, p2p, m2p, letc) if let else (ax, ay, az, phi, p2p, m2p)
 
     def direct_gravity(self, x, y, z, m, h=None, first=0, last=None, targets=None, num_segments=0, G=1.0, eps2=0.0,
                        potential=True):

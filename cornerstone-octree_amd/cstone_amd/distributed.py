@@ -315,7 +315,8 @@ class NativeDistributedDomain:
         coordinates but not those of the masses, so the masses' halos are exchanged first (in place) unless
         exchange_masses is False, in which case the caller has done that.  h: per-particle softening lengths laid out
         like x and read on the halo ranges too (cstone_hip_domain_mr_compute_gravity_h); the sync's h has its halo
-        ranges filled already, they travel with x, y, z, so nothing is exchanged for it.  Collective"""
+        ranges filled already, they travel with x, y, z, so nothing is exchanged for it.  order: 0, 2 or 3 (octupoles: one
+        more global and one more peer exchange).  Collective"""
         torch = _torch()
         if exchange_masses:
             self.exchange_halos(m)
@@ -341,10 +342,17 @@ class NativeDistributedDomain:
     def multipoles(self):
         """(num_nodes, 8) multipoles of the focus tree as the last gravity() built them (a tensor that aliases the
         domain's array), or None"""
+        return self._node_moments(self.ctx.lib.cstone_hip_domain_mr_multipoles_get, "domain_mr_multipoles_get")
+
+    def octupoles(self):
+        """(num_nodes, 8) octupoles (Oxxx, Oxxy, Oxxz, Oxyy, Oxyz, Oyyy, Oyyz, 0) beside them, or None unless the last
+        gravity() was at order 3"""
+        return self._node_moments(self.ctx.lib.cstone_hip_domain_mr_octupoles_get, "domain_mr_octupoles_get")
+
+    def _node_moments(self, getter, what):
         torch = _torch()
         ptr, nn = C.c_void_p(), C.c_int32(0)
-        self.ctx._chk(self.ctx.lib.cstone_hip_domain_mr_multipoles_get(self.h, C.byref(ptr), C.byref(nn)),
-                      "domain_mr_multipoles_get")
+        self.ctx._chk(getter(self.h, C.byref(ptr), C.byref(nn)), what)
         if not ptr.value:
             return None
         rdt = torch.float64 if self.rb == 64 else torch.float32

@@ -135,7 +135,7 @@ class Domain:
         """Barnes-Hut gravity on the focus tree (cstone_hip_domain_compute_gravity) after sync_grav /
         update_expansion_centers: (ax, ay, az, phi) of the end_index particles, phi None unless potential; x, y, z, m laid
         out like the last sync's results.  h: per-particle softening lengths laid out like x (the sync's h), None: Plummer
-        softening with eps alone"""
+        softening with eps alone.  order: 0 monopoles, 2 + quadrupoles, 3 + octupoles"""
         import torch
 
         ne = self.view().end_index

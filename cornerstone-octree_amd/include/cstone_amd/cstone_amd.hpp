@@ -699,6 +699,56 @@ void directGravity(const T* x, const T* y, const T* z, const Tm* m, const T* h, 
                    "directGravity");
 }
 
+/*! Octupoles of a linked octree with expansion centres (cstone_hip_upsweep_octupoles): 8 values of T per node,
+ *  (Oxxx, Oxxy, Oxxz, Oxyy, Oxyz, Oyyy, Oyyz, 0), a second array beside the multipoles, which are an INPUT here and must
+ *  be swept up already for the same centres.  levelRangeHost: numLevels + 1 host entries.  All other pointers: device. */
+template<class T, class Tm>
+void upsweepOctupoles(const T* x, const T* y, const T* z, const Tm* m, const TreeNodeIndex* leafToInternal,
+                      TreeNodeIndex numLeaves, const LocalIndex* layout, int numLevels,
+                      const TreeNodeIndex* levelRangeHost, const TreeNodeIndex* childOffsets, TreeNodeIndex numNodes,
+                      const T* expansionCenters, const T* multipoles, T* octupoles)
+{
+    static_assert(std::is_same_v<T, float> || std::is_same_v<T, double>);
+    static_assert(std::is_same_v<Tm, float> || std::is_same_v<Tm, double>);
+    Context::check(cstone_hip_upsweep_octupoles(Context::get(), int(sizeof(T)) * 8, int(sizeof(Tm)) * 8, x, y, z, m,
+                                                leafToInternal, numLeaves, layout, numLevels, levelRangeHost, childOffsets,
+                                                numNodes, expansionCenters, multipoles, octupoles),
+                   "upsweepOctupoles");
+}
+
+//! the internal-node part of upsweepOctupoles alone, for octupoles whose leaf entries are filled already
+template<class T>
+void upsweepOctupolesNodes(int numLevels, const TreeNodeIndex* levelRangeHost, const TreeNodeIndex* childOffsets,
+                           TreeNodeIndex numNodes, const T* expansionCenters, const T* multipoles, T* octupoles)
+{
+    static_assert(std::is_same_v<T, float> || std::is_same_v<T, double>);
+    Context::check(cstone_hip_upsweep_octupoles_nodes(Context::get(), int(sizeof(T)) * 8, numLevels, levelRangeHost,
+                                                      childOffsets, numNodes, expansionCenters, multipoles, octupoles),
+                   "upsweepOctupolesNodes");
+}
+
+/*! The group walk at order 3 (cstone_hip_compute_gravity_o3): monopole + quadrupole + octupole for the targets of the
+ *  groups (numGroups + 1 device offsets) clipped to [first, last); outputs indexed by i - first.  h, phi and the counts
+ *  are nullable; let: the rule of a locally essential tree (an opened leaf without particles is applied as a multipole,
+ *  counted in letM2pCounts).  eps: Plummer softening length.  Synchronises the stream. */
+template<class T, class Tm>
+void computeGravityO3(const T* x, const T* y, const T* z, const Tm* m, const T* h, LocalIndex first, LocalIndex last,
+                      const LocalIndex* groups, LocalIndex numGroups, const Box<T>& box,
+                      const TreeNodeIndex* childOffsets, const TreeNodeIndex* internalToLeaf, const LocalIndex* layout,
+                      const T* expansionCenters, const T* multipoles, const T* octupoles, bool let, T G, T eps, T* ax,
+                      T* ay, T* az, T* phi, unsigned* p2pCounts = nullptr, unsigned* m2pCounts = nullptr,
+                      unsigned* letM2pCounts = nullptr)
+{
+    static_assert(std::is_same_v<T, float> || std::is_same_v<T, double>);
+    static_assert(std::is_same_v<Tm, float> || std::is_same_v<Tm, double>);
+    Context::check(cstone_hip_compute_gravity_o3(Context::get(), int(sizeof(T)) * 8, int(sizeof(Tm)) * 8, x, y, z, m, h,
+                                                 first, last, groups, numGroups, &box.pod(), childOffsets, internalToLeaf,
+                                                 layout, expansionCenters, multipoles, octupoles, let ? 1 : 0, double(G),
+                                                 double(eps) * double(eps), ax, ay, az, phi, p2pCounts, m2pCounts,
+                                                 letM2pCounts),
+                   "computeGravityO3");
+}
+
 class RcclComm
 {
 public:
@@ -823,7 +873,8 @@ public:
      *  null, potentials of the assigned particles, written to [startIndex(), endIndex()) of arrays laid out like the
      *  result arrays (nParticlesWithHalos() elements).  x, y, z, m are laid out the same way and read on the halo ranges
      *  too; the sync does not fill the halo ranges of the masses, so they are exchanged here first (in place) unless
-     *  exchangeMasses is false.  eps: Plummer softening length; order 0: monopoles, 2: + quadrupoles.  Collective. */
+     *  exchangeMasses is false.  eps: Plummer softening length; order 0: monopoles, 2: + quadrupoles, 3: + octupoles
+     *  (one more global and one more peer exchange).  Collective. */
     template<class Tm>
     void computeGravity(const T* x, const T* y, const T* z, Tm* m, T* ax, T* ay, T* az, T* phi, T G, T eps, int order = 2,
                         bool exchangeMasses = true)
@@ -853,6 +904,14 @@ public:
         const void* p = nullptr;
         std::int32_t n = 0;
         Context::check(cstone_hip_domain_mr_multipoles_get(dom_, &p, &n), "MultiRankDomain::multipoles");
+        return static_cast<const T*>(p);
+    }
+    //! the octupoles beside them, 8 values of T per node (device); null unless the last computeGravity was at order 3
+    const T* octupoles() const
+    {
+        const void* p = nullptr;
+        std::int32_t n = 0;
+        Context::check(cstone_hip_domain_mr_octupoles_get(dom_, &p, &n), "MultiRankDomain::octupoles");
         return static_cast<const T*>(p);
     }
     template<class V>
@@ -1154,7 +1213,7 @@ public:
     /*! Barnes-Hut gravity on the focus tree (cstone_hip_domain_compute_gravity): accelerations and, if phi is not null,
      *  potentials of the endIndex() particles (the vectors are resized to that), from the expansion centres of
      *  updateExpansionCenters after the last sync; x, y, z, m laid out like the result arrays of that sync.  eps: Plummer
-     *  softening length; order 0: monopoles, 2: monopoles + quadrupoles.  Open boundaries.  On several ranks the
+     *  softening length; order 0: monopoles, 2: + quadrupoles, 3: + octupoles.  Open boundaries.  On several ranks the
      *  vectors hold nParticlesWithHalos() elements, [startIndex(), endIndex()) is written and the halo ranges of m are
      *  exchanged first (MultiRankDomain::computeGravity). */
     template<class Tm>

@@ -227,6 +227,11 @@ void instantiateSoftGravity()
     [[maybe_unused]] auto multi  = static_cast<void (Mr::*)(const T*, const T*, const T*, Tm*, const T*, T*, T*, T*, T*, T,
                                                            T, int, bool)>(&Mr::template computeGravity<Tm>);
     [[maybe_unused]] auto direct = &directGravity<T, Tm>;
+    // order 3 (tests/test_gravity_o3.py runs the entry points behind them)
+    [[maybe_unused]] auto octLeaves = &upsweepOctupoles<T, Tm>;
+    [[maybe_unused]] auto octNodes  = &upsweepOctupolesNodes<T>;
+    [[maybe_unused]] auto walkO3    = &computeGravityO3<T, Tm>;
+    [[maybe_unused]] auto octGet    = &Mr::octupoles;
 }
 
 //! computeContinuumCsarray for the two concentration functions the oracle's reference build can name (oracle/ref_driver.cpp,

@@ -861,7 +861,8 @@ extern "C"
 
     /* ---------------------------------------------------------------------------------------------
      * Barnes-Hut gravity on a linked octree with expansion centres (the step the reference leaves to its client, Ryoanji):
-     * single rank, open boundaries, monopole + traceless Cartesian quadrupole, Plummer softening.  Coordinates, centres,
+     * single rank, open boundaries, monopole + traceless Cartesian quadrupole (+ octupole, the _o3 / order 3 entries at
+     * the end of this block), Plummer softening.  Coordinates, centres,
      * multipoles and results are real_bits (float | double), masses mass_bits (float | double); sums run in real_bits.
      * upsweep_multipoles : multipoles[n][8] = (M, Qxx, Qxy, Qxz, Qyy, Qyz, Qzz, 0) of every node n about its expansion
      *                 centre c_n = expansion_centers[n].xyz: M = sum m_j, Q_ab = sum m_j (3 d_a d_b - |d|^2 delta_ab),
@@ -879,6 +880,8 @@ extern "C"
      *                 are walked.  r^2 = |d|^2 + eps2;  P2P: a_i += G m_j d / r^3, phi_i -= G m_j / r (d = r_j - r_i);
      *                 M2P (d = r_i - c_n): a += G [-M d / r^3 + Q d / r^5 - 5/2 (d.Q.d) d / r^7],
      *                 phi -= G [M / r + 1/2 (d.Q.d) / r^5]; order 0 drops the Q terms (monopole), order 2 keeps them.
+     *                 Every other order is CSTONE_E_ARG here and in compute_gravity_let / _h / _let_h: these entries have
+     *                 no octupole pointer; order 3 is compute_gravity_o3.
      *                 ax, ay, az, phi (nullable) and the optional per-target interaction counts p2p_counts / m2p_counts
      *                 (u32) are indexed by i - first and OVERWRITTEN; particles outside every group are left untouched.
      *                 Periodic axes are refused (CSTONE_E_ARG: Ewald summation is not provided).  Synchronises the stream;
@@ -956,6 +959,32 @@ extern "C"
      *                 (csrc/domain_mr.hip, C5; R/domain/domain.hpp exchangeHalos(x, y, z, h)), so no exchange is needed
      *                 for the h that a sync returned; an h the caller recomputed afterwards on its assigned range needs
      *                 _exchange_halos(h) first, like any other field.
+     * upsweep_octupoles : octupoles[n][8] = (Oxxx, Oxxy, Oxxz, Oxyy, Oxyz, Oyyy, Oyyz, 0) of every node n, a SECOND array
+     *                 beside multipoles[n][8] (whose layout and bits do not change): the seven independent components
+     *                 of the symmetric traceless rank-3 tensor about c_n in the quadrupole's normalisation,
+     *                 O_abc = sum m_j (15 d_a d_b d_c - 3 |d|^2 (d_a delta_bc + d_b delta_ac + d_c delta_ab)), d = r_j - c_n;
+     *                 Oxzz = -(Oxxx + Oxyy), Oyzz = -(Oxxy + Oyyy), Ozzz = -(Oxxz + Oyyz) are not stored.  Leaves from
+     *                 their particles, internal nodes level by level from their children shifted by s = c_child - c_n
+     *                 with the child's M and Q, (Qs)_a = Q_ab s_b:
+     *                 O'_abc = O_abc + 5 (s_a Q_bc + s_b Q_ac + s_c Q_ab) - 2 (delta_ab (Qs)_c + delta_ac (Qs)_b +
+     *                 delta_bc (Qs)_a) + M (15 s_a s_b s_c - 3 |s|^2 (s_a delta_bc + s_b delta_ac + s_c delta_ab)).
+     *                 multipoles: INPUT, already swept up for the same tree and centres (upsweep_multipoles first);
+     *                 the other arguments as for upsweep_multipoles.
+     * upsweep_octupoles_nodes : the internal-node part alone, for octupoles whose leaf entries are filled already, like
+     *                 upsweep_multipoles_nodes.
+     * compute_gravity_o3 : the walk at order 3, everything else as compute_gravity_h (let == 0) or compute_gravity_let_h
+     *                 (let != 0; let_m2p_counts is read only then): the same MAC, groups, counts, pair rule, refusals,
+     *                 synchronisation and stack-overflow report, h nullable.  octupoles == NULL: CSTONE_E_ARG.  M2P
+     *                 adds, with u_a = O_abc d_b d_c and w = u.d (d = r_i - c_n, r^2 = |d|^2 + eps2):
+     *                 a += G [u / (2 r^7) - 7 w d / (6 r^9)], phi -= G w / (6 r^7).  The order changes no decision of
+     *                 the walk: all three counts equal those of orders 0 and 2 on the same tree.
+     * order 3 on the domains : domain_compute_gravity[_h] and domain_mr_compute_gravity[_h] accept order == 3 and build
+     *                 the octupoles after the multipoles.  On several ranks every stage of the multipole update runs
+     *                 for the second array too (own leaves, upsweep, global exchange, peer exchange, upsweep), so an
+     *                 order-3 call costs ONE MORE global exchange and ONE MORE peer exchange than order 0 or 2, whose
+     *                 collective sequence is unchanged.
+     * domain_mr_octupoles_get : like domain_mr_multipoles_get for the T[num_nodes][8] octupoles; NULL before the first
+     *                 order-3 domain_mr_compute_gravity and after a call at another order.
      * ------------------------------------------------------------------------------------------- */
 #define CSTONE_GRAVITY_GROUP_TOL 2.0f
     int cstone_hip_upsweep_multipoles(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
@@ -1010,6 +1039,24 @@ extern "C"
     int cstone_hip_domain_mr_compute_gravity_h(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z,
                                                const void* m, const void* h, int mass_bits, int order, double G,
                                                double eps2, void* ax, void* ay, void* az, void* phi);
+    int cstone_hip_upsweep_octupoles(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
+                                     const void* z, const void* m, const int32_t* leaf_to_internal, int num_leaves,
+                                     const uint32_t* layout, int num_levels, const int32_t* level_range_host,
+                                     const int32_t* child_offsets, int num_nodes, const void* expansion_centers,
+                                     const void* multipoles, void* octupoles);
+    int cstone_hip_upsweep_octupoles_nodes(cstone_hip_ctx* ctx, int real_bits, int num_levels,
+                                           const int32_t* level_range_host, const int32_t* child_offsets,
+                                           int num_nodes, const void* expansion_centers, const void* multipoles,
+                                           void* octupoles);
+    int cstone_hip_compute_gravity_o3(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
+                                      const void* z, const void* m, const void* h, uint32_t first, uint32_t last,
+                                      const uint32_t* groups, uint32_t num_groups, const cstone_box* box_host,
+                                      const int32_t* child_offsets, const int32_t* internal_to_leaf,
+                                      const uint32_t* layout, const void* expansion_centers, const void* multipoles,
+                                      const void* octupoles, int let, double G, double eps2, void* ax, void* ay,
+                                      void* az, void* phi, uint32_t* p2p_counts, uint32_t* m2p_counts,
+                                      uint32_t* let_m2p_counts);
+    int cstone_hip_domain_mr_octupoles_get(cstone_hip_domain_mr* dom, const void** octupoles, int32_t* num_nodes);
 
 #ifdef __cplusplus
 }
