@@ -132,6 +132,8 @@ struct DomainBase
     virtual int updateExpansionCenters(const void* x, const void* y, const void* z, const void* m, int massBits) = 0;
     virtual int computeGravity(const void* x, const void* y, const void* z, const void* m, const void* h, int massBits,
                                int order, double G, double eps2, void* ax, void* ay, void* az, void* phi) = 0;
+    virtual int adaptH(const void* x, const void* y, const void* z, void* h, uint32_t ng0, uint32_t tol, uint32_t maxIter,
+                       float growLimit, uint32_t* counts, uint32_t* status) = 0;
     virtual void stats(cstone_hip_domain_stats* out)     = 0;
 };
 
@@ -219,6 +221,19 @@ public:
         v->halo_radii            = radii_.as<float>();
         v->expansion_centers     = haveExpansion_ ? fExpansion_.p : nullptr;
         return CSTONE_OK;
+    }
+
+    /*! cstone_hip_adapt_smoothing_lengths for [start_index, end_index) of the last sync on the focus tree of the view.
+     *  On one rank every particle is here, so h may grow without limit: growLimit == 0 means INFINITY */
+    int adaptH(const void* x, const void* y, const void* z, void* h, uint32_t ng0, uint32_t tol, uint32_t maxIter,
+               float growLimit, uint32_t* counts, uint32_t* status) override
+    {
+        if (firstCall_ || fLeaves_ < 1) return fail(ctx_, CSTONE_E_ARG, "domain_adapt_h: no sync yet");
+        if (growLimit == 0.0f) growLimit = INFINITY;
+        return cstone_hip_adapt_smoothing_lengths(ctx_, rb, x, y, z, h, startIndex_, endIndex_, &box_,
+                                                  fChild_.as<int32_t>(), fItl_.as<int32_t>(), layout_.as<uint32_t>(),
+                                                  fCenters_.p, fSizes_.p, ng0, tol, maxIter, growLimit, 0, nullptr, counts,
+                                                  status);
     }
 
     /*! Domain::updateExpansionCenters (R/domain/domain.hpp:415-421) on one rank = FocusedOctree::updateCenters without its
@@ -1018,6 +1033,13 @@ int cstone_hip_domain_compute_gravity_h(cstone_hip_domain* dom, const void* x, c
 {
     if (!dom) return CSTONE_E_ARG;
     return dom->impl->computeGravity(x, y, z, m, h, mass_bits, order, G, eps2, ax, ay, az, phi);
+}
+
+int cstone_hip_domain_adapt_h(cstone_hip_domain* dom, const void* x, const void* y, const void* z, void* h, uint32_t ng0,
+                              uint32_t tol, uint32_t max_iter, float grow_limit, uint32_t* counts, uint32_t* status)
+{
+    if (!dom) return CSTONE_E_ARG;
+    return dom->impl->adaptH(x, y, z, h, ng0, tol, max_iter, grow_limit, counts, status);
 }
 
 int cstone_hip_domain_view_get(cstone_hip_domain* dom, cstone_hip_domain_view* out)

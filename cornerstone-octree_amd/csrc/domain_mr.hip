@@ -363,6 +363,8 @@ struct MrBase
     virtual int updateExpansionCenters(const void* x, const void* y, const void* z, const void* m, int massBits) = 0;
     virtual int computeGravity(const void* x, const void* y, const void* z, const void* m, const void* h, int massBits,
                                int order, double G, double eps2, void* ax, void* ay, void* az, void* phi) = 0;
+    virtual int adaptH(const void* x, const void* y, const void* z, void* h, uint32_t ng0, uint32_t tol, uint32_t maxIter,
+                       float growLimit, uint32_t* counts, uint32_t* status)                = 0;
     virtual int multipoles(const void** out, int32_t* numNodes)                           = 0;
     virtual int octupoles(const void** out, int32_t* numNodes)                            = 0;
     virtual int view(cstone_hip_domain_mr_view* out)                                     = 0;
@@ -596,6 +598,41 @@ public:
             phi ? static_cast<char*>(phi) + off : nullptr, nullptr, nullptr, nullptr);
     }
 
+    /*! cstone_hip_adapt_smoothing_lengths for the assigned particles on the tree octree() returns (both halo modes serve
+     *  it: the LET's focus tree has empty layout ranges where the particles are elsewhere).  LOCAL, no collective.  The
+     *  halos of the last sync cover 2 h x haloExt_ of every assigned particle, so h may grow by haloExt_ at most:
+     *  growLimit == 0 means haloExt_, a larger one is refused, and so is a second call before the next sync (the cap is
+     *  relative to the h it is handed, it would compound).  x, y, z, h laid out like the result arrays; counts and status
+     *  are indexed from start_index; the halo ranges of h are stale afterwards (exchangeHalos). */
+    int adaptH(const void* x, const void* y, const void* z, void* h, uint32_t ng0, uint32_t tol, uint32_t maxIter,
+               float growLimit, uint32_t* counts, uint32_t* status) override
+    {
+        if (firstCall_) return fail(ctx_, CSTONE_E_ARG, "domain_mr_adapt_h: no sync yet");
+        if (growLimit == 0.0f) growLimit = haloExt_;
+        if (!(growLimit >= 1.0f) || growLimit > haloExt_)
+            return fail(ctx_, CSTONE_E_ARG,
+                        "domain_mr_adapt_h: grow_limit %g outside [1, halo factor %g]: neighbours beyond the halos are not "
+                        "on this rank",
+                        double(growLimit), double(haloExt_));
+        if (adapted_)
+            return fail(ctx_, CSTONE_E_ARG, "domain_mr_adapt_h: called twice since the last sync (the cap on h would compound)");
+        const uint32_t si = view_.start_index, ei = view_.end_index;
+        // (a rank without particles may pass null arrays, like an empty rank of a sync)
+        if (ei > si && (!x || !y || !z || !h || !counts || !status))
+            return fail(ctx_, CSTONE_E_ARG, "domain_mr_adapt_h: bad argument");
+        if (ng0 == 0) return fail(ctx_, CSTONE_E_ARG, "domain_mr_adapt_h: ng0 must be at least 1");
+        if (ei > si)
+        {
+            cstone_hip_domain_mr_octree t;
+            CS_TRY(octree(&t));
+            CS_TRY(cstone_hip_adapt_smoothing_lengths(ctx_, rb, x, y, z, h, si, ei, &view_.box, t.child_offsets,
+                                                      t.internal_to_leaf, t.layout, t.centers, t.sizes, ng0, tol, maxIter,
+                                                      growLimit, 0, nullptr, counts, status));
+        }
+        adapted_ = true;
+        return CSTONE_OK;
+    }
+
     int multipoles(const void** out, int32_t* numNodes) override
     {
         const bool have = useLet_ && let_ && !firstCall_ && haveExpansionCenters_;
@@ -779,6 +816,7 @@ private:
         s.hsCounts.assign(P_, 0), s.hmatrix.assign(size_t(P_) * P_, 0);
         CS_TRY(scal_.ensure(ctx_, 4096 + size_t(P_) * (P_ + 1) * 8 + size_t(P_ + 1) * 16));
         ++syncs_;
+        adapted_ = false;
         return CSTONE_OK;
     }
 
@@ -1899,6 +1937,7 @@ private:
     bool noMargin_  = std::getenv("CSTONE_MR_NO_MARGIN") != nullptr; // tests: no room left for halos, the block is moved
     bool peerLoop_  = std::getenv("CSTONE_MR_PEER_LOOP") != nullptr; // tests: take the > 32 ranks path (one traversal per peer)
     int syncs_      = 0;
+    bool adapted_   = false; // adaptH ran since the last sync (one call per sync; every sync clears it)
     std::map<std::string, double> phase_;
     std::chrono::steady_clock::time_point t0_;
     std::vector<K> assignment_;
@@ -2069,6 +2108,14 @@ int cstone_hip_domain_mr_compute_gravity_h(cstone_hip_domain_mr* dom, const void
 {
     if (!dom) return CSTONE_E_ARG;
     return dom->impl->computeGravity(x, y, z, m, h, mass_bits, order, G, eps2, ax, ay, az, phi);
+}
+
+int cstone_hip_domain_mr_adapt_h(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z, void* h,
+                                 uint32_t ng0, uint32_t tol, uint32_t max_iter, float grow_limit, uint32_t* counts,
+                                 uint32_t* status)
+{
+    if (!dom) return CSTONE_E_ARG;
+    return dom->impl->adaptH(x, y, z, h, ng0, tol, max_iter, grow_limit, counts, status);
 }
 
 int cstone_hip_domain_mr_multipoles_get(cstone_hip_domain_mr* dom, const void** multipoles, int32_t* num_nodes)

@@ -20,7 +20,7 @@ MORTON, HILBERT = 0, 1
 STAGES = {
     "encode": 0, "sort_hist": 1, "sort_pass": 2, "gather": 3, "node_counts": 4, "rebalance": 5, "link_octree": 6,
     "halos": 7, "neighbors": 8, "minmax": 9, "sort_pass_iota": 10, "resort_bins": 11, "resort_leaves": 12, "gather_h": 13, "place": 14,
-    "multipoles": 15, "gravity": 16,
+    "multipoles": 15, "gravity": 16, "adapt_h": 17,
 }
 
 EXPORTS = [
@@ -68,7 +68,12 @@ EXPORTS = [
     # ... at order 3: the octupoles beside the multipoles
     "cstone_hip_upsweep_octupoles", "cstone_hip_upsweep_octupoles_nodes", "cstone_hip_compute_gravity_o3",
     "cstone_hip_domain_mr_octupoles_get",
+    # adaptive smoothing lengths: h iterated to a neighbour count inside one kernel (csrc/adapt_h.hip)
+    "cstone_hip_adapt_smoothing_lengths", "cstone_hip_domain_adapt_h", "cstone_hip_domain_mr_adapt_h",
 ]
+
+# status word of the adapt calls: number of walks in bits 0-7, then the CSTONE_ADAPT_H_* flags
+ADAPT_H_WALKS_MASK, ADAPT_H_NOT_CONVERGED, ADAPT_H_CAPPED, ADAPT_H_STALLED = 0xFF, 0x100, 0x200, 0x400
 
 GRAVITY_GROUP_TOL = 2.0  # CSTONE_GRAVITY_GROUP_TOL: tol_factor of the target groups of cstone_hip_domain_compute_gravity
 
@@ -518,6 +523,25 @@ class Context:
                                                      _ptr(layout), _ptr(centers), _ptr(sizes), C.c_float(ext),
                                                      C.c_uint32(ngmax), _ptr(nidx), _ptr(nc)), "find_neighbors")
         return nidx, nc
+
+    def adapt_smoothing_lengths(self, x, y, z, h, first, last, box, octree, layout, centers, sizes, ng0, tol, max_iter,
+                                grow_limit=float("inf"), ngmax=0):
+        """cstone_hip_adapt_smoothing_lengths: h[first:last] iterated IN PLACE to ng0 +- tol neighbours (the rule: include/
+        cstone_hip.h).  Returns (neighbors [last - first, ngmax] or None if ngmax == 0, counts, status), status = walks |
+        ADAPT_H_* flags.  Rows of neighbors beyond min(count, ngmax) are not written (they are zero here)"""
+        torch = _torch()
+        if h.dtype != x.dtype:
+            raise ValueError("h must have the coordinates' type")
+        nw = last - first
+        nidx = torch.zeros((nw, ngmax), dtype=torch.int32, device=x.device) if ngmax else None
+        nc = torch.zeros(nw, dtype=torch.int32, device=x.device)
+        st = torch.zeros(nw, dtype=torch.int32, device=x.device)
+        self._chk(self.lib.cstone_hip_adapt_smoothing_lengths(
+            self.h, C.c_int(x.element_size() * 8), _ptr(x), _ptr(y), _ptr(z), _ptr(h), C.c_uint32(first),
+            C.c_uint32(last), C.byref(box), _ptr(octree["child_offsets"]), _ptr(octree["internal_to_leaf"]), _ptr(layout),
+            _ptr(centers), _ptr(sizes), C.c_uint32(ng0), C.c_uint32(tol), C.c_uint32(max_iter), C.c_float(grow_limit),
+            C.c_uint32(ngmax), _ptr(nidx), _ptr(nc), _ptr(st)), "adapt_smoothing_lengths")
+        return nidx, nc, st
 
     def compute_fixed_groups(self, first, last, group_size):
         torch = _torch()

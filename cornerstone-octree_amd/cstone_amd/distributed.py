@@ -339,6 +339,35 @@ class NativeDistributedDomain:
         self.ctx._chk(rc, "domain_mr_compute_gravity")
         return ax, ay, az, phi
 
+    def set_halo_factor(self, factor):
+        """Domain::setHaloFactor: the next syncs collect halos for 2 h x factor (cstone_hip_domain_mr_set_halo_factor)"""
+        self.ctx._chk(self.ctx.lib.cstone_hip_domain_mr_set_halo_factor(self.h, C.c_float(factor)),
+                      "domain_mr_set_halo_factor")
+
+    def adapt_h(self, x, y, z, h, ng0, tol, max_iter, grow_limit=0.0, exchange=True):
+        """cstone_hip_domain_mr_adapt_h: h of the assigned particles iterated IN PLACE to ng0 +- tol neighbours on
+        octree(); x, y, z, h laid out like the result arrays of the last sync and read on the halo ranges too (h is not:
+        a walk reads only its own target's h).  grow_limit 0: the domain's halo factor, the most h may grow with every
+        neighbour still among the halos; a larger value and a second call before the next sync are refused.  Returns
+        (counts, status) of the assigned particles.  The call itself is local; afterwards the halo ranges of h are stale,
+        so they are exchanged (collective) unless exchange is False"""
+        torch = _torch()
+        if h.dtype != x.dtype or h.numel() != x.numel():
+            raise ValueError("h must be laid out like x")
+        v = self.view()
+        nw = v.end_index - v.start_index
+        nc = torch.zeros(nw, dtype=torch.int32, device=x.device)
+        st = torch.zeros(nw, dtype=torch.int32, device=x.device)
+        rc = self.ctx.lib.cstone_hip_domain_mr_adapt_h(self.h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()),
+                                                       C.c_void_p(z.data_ptr()), C.c_void_p(h.data_ptr()),
+                                                       C.c_uint32(ng0), C.c_uint32(tol), C.c_uint32(max_iter),
+                                                       C.c_float(grow_limit), C.c_void_p(nc.data_ptr()),
+                                                       C.c_void_p(st.data_ptr()))
+        self.ctx._chk(rc, "domain_mr_adapt_h")
+        if exchange:
+            self.exchange_halos(h)
+        return nc, st
+
     def multipoles(self):
         """(num_nodes, 8) multipoles of the focus tree as the last gravity() built them (a tensor that aliases the
         domain's array), or None"""

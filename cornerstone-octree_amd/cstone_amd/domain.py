@@ -154,6 +154,24 @@ class Domain:
         self.ctx._chk(rc, "domain_compute_gravity")
         return ax, ay, az, phi
 
+    def adapt_h(self, x, y, z, h, ng0, tol, max_iter, grow_limit=0.0, exchange=True):
+        """cstone_hip_domain_adapt_h: h of the particles [start_index, end_index) of the last sync iterated IN PLACE to
+        ng0 +- tol neighbours on the view's octree; x, y, z, h laid out like the sync's results.  grow_limit 0: no limit.
+        Returns (counts, status) of those particles.  exchange: nothing to do on one rank (every particle is assigned);
+        the argument is that of NativeDistributedDomain.adapt_h"""
+        import torch
+
+        v = self.view()
+        nw = v.end_index - v.start_index
+        nc = torch.zeros(nw, dtype=torch.int32, device=x.device)
+        st = torch.zeros(nw, dtype=torch.int32, device=x.device)
+        rc = self.ctx.lib.cstone_hip_domain_adapt_h(self.h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()),
+                                                    C.c_void_p(z.data_ptr()), C.c_void_p(h.data_ptr()), C.c_uint32(ng0),
+                                                    C.c_uint32(tol), C.c_uint32(max_iter), C.c_float(grow_limit),
+                                                    C.c_void_p(nc.data_ptr()), C.c_void_p(st.data_ptr()))
+        self.ctx._chk(rc, "domain_adapt_h")
+        return nc, st
+
     def reapply_sync(self, field):
         """Domain::reapplySync: field (n rows of the last sync's input, 1..32 bytes each) in the order of the result"""
         import torch

@@ -676,6 +676,34 @@ void findNeighborsGpu(const T* x, const T* y, const T* z, const T* h, const Grou
                    "findNeighborsGpu");
 }
 
+//! status word of adaptSmoothingLengthsGpu: number of walks in the low byte, then the reason a target stopped unconverged
+struct AdaptStatus
+{
+    static constexpr unsigned walksMask    = 0xFFu;
+    static constexpr unsigned notConverged = CSTONE_ADAPT_H_NOT_CONVERGED;
+    static constexpr unsigned capped       = CSTONE_ADAPT_H_CAPPED;
+    static constexpr unsigned stalled      = CSTONE_ADAPT_H_STALLED;
+};
+
+/*! Adaptive smoothing lengths (cstone_hip_adapt_smoothing_lengths; the rule is stated in include/cstone_hip.h): h of the
+ *  particles [first, last) is iterated IN PLACE, inside one kernel, until each has ng0 +- tol neighbours, for at most
+ *  maxIter corrections and never beyond growLimit x its input (INFINITY: no limit).  neighborsCount[i - first]: the
+ *  count at the final h; status[i - first]: walks made | AdaptStatus flags (none: converged).  ngmax > 0: the first
+ *  ngmax neighbours at the final h in neighbors[(i - first) * ngmax + k], as findNeighborsGpu would store them.  The
+ *  search extension of the tree view is not used: the walk of a target covers exactly its current radius. */
+template<class T, class KeyType>
+void adaptSmoothingLengthsGpu(const T* x, const T* y, const T* z, T* h, LocalIndex first, LocalIndex last,
+                              const Box<T>& box, const OctreeNsView<T, KeyType>& tree, unsigned ng0, unsigned tol,
+                              unsigned maxIter, float growLimit, unsigned* neighborsCount, unsigned* status,
+                              unsigned ngmax = 0, LocalIndex* neighbors = nullptr)
+{
+    Context::check(cstone_hip_adapt_smoothing_lengths(Context::get(), detail::realBits<T>(), x, y, z, h, first, last,
+                                                      &box.pod(), tree.childOffsets, tree.internalToLeaf, tree.layout,
+                                                      tree.centers, tree.sizes, ng0, tol, maxIter, growLimit, ngmax,
+                                                      neighbors, neighborsCount, status),
+                   "adaptSmoothingLengthsGpu");
+}
+
 /*! The transport of the multi-rank Domain on a node of MI355X: RCCL, served from C++ inside libcstone_hip on the context's
  *  stream (csrc/comm_rccl.hip) -- replaces the MPI point-to-point exchanges of the reference
  *  (R/domain/domaindecomp_mpi_gpu.cuh:86-185, R/halos/exchange_halos_gpu.cuh:35-119).  One rank obtains the id
@@ -897,6 +925,19 @@ public:
         Context::check(cstone_hip_domain_mr_compute_gravity_h(dom_, x, y, z, m, h, int(sizeof(Tm)) * 8, order, double(G),
                                                               double(eps) * double(eps), ax, ay, az, phi),
                        "MultiRankDomain::computeGravity");
+    }
+    /*! Adaptive smoothing lengths on several ranks (cstone_hip_domain_mr_adapt_h): h of the assigned particles iterated in
+     *  place to ng0 +- tol neighbours on octreeProperties(); x, y, z, h laid out like the result arrays, counts and
+     *  status hold nParticles() elements (indexed from startIndex()).  The kernel call is local.  growLimit 0: the halo
+     *  factor, the most h may grow with all neighbours still among the halos; more is refused, and so is a second call
+     *  before the next sync.  Afterwards the halo ranges of h are stale: they are exchanged (collective) unless exchange
+     *  is false. */
+    void adaptSmoothingLengths(const T* x, const T* y, const T* z, T* h, unsigned ng0, unsigned tol, unsigned maxIter,
+                               float growLimit, unsigned* counts, unsigned* status, bool exchange = true)
+    {
+        Context::check(cstone_hip_domain_mr_adapt_h(dom_, x, y, z, h, ng0, tol, maxIter, growLimit, counts, status),
+                       "MultiRankDomain::adaptSmoothingLengths");
+        if (exchange) exchangeHalos(h);
     }
     //! the multipoles of the focus tree that the last computeGravity built: 8 values of T per node (device), or null
     const T* multipoles() const
@@ -1274,6 +1315,29 @@ public:
                                                            double(eps) * double(eps), ax.data(), ay.data(), az.data(),
                                                            phi ? phi->data() : nullptr),
                        "Domain::computeGravity");
+    }
+    /*! Adaptive smoothing lengths (cstone_hip_domain_adapt_h): h of the particles [startIndex(), endIndex()) of the last
+     *  sync iterated IN PLACE, inside one kernel, to ng0 +- tol neighbours (the rule: include/cstone_hip.h); x, y, z, h laid
+     *  out like the result arrays.  counts and status are resized to nParticles(): the count at the final h, and the walks
+     *  made | AdaptStatus flags (none: converged).  growLimit: the most h may grow relative to its input; 0 means no limit
+     *  on one rank and the halo factor on several (MultiRankDomain::adaptSmoothingLengths, which also exchanges the halos
+     *  of h afterwards). */
+    void adaptSmoothingLengths(const DeviceVector<T>& x, const DeviceVector<T>& y, const DeviceVector<T>& z,
+                               DeviceVector<T>& h, unsigned ng0, unsigned tol, unsigned maxIter, float growLimit,
+                               DeviceVector<unsigned>& counts, DeviceVector<unsigned>& status)
+    {
+        if (h.size() != x.size()) throw std::runtime_error("Domain adaptSmoothingLengths: h is not laid out like x\n");
+        counts.resize(nParticles());
+        status.resize(nParticles());
+        if (mr_)
+        {
+            mr_->adaptSmoothingLengths(x.data(), y.data(), z.data(), h.data(), ng0, tol, maxIter, growLimit, counts.data(),
+                                       status.data());
+            return;
+        }
+        Context::check(cstone_hip_domain_adapt_h(dom_, x.data(), y.data(), z.data(), h.data(), ng0, tol, maxIter, growLimit,
+                                                 counts.data(), status.data()),
+                       "Domain::adaptSmoothingLengths");
     }
     //! R/domain/domain.hpp:411: stores the flag like the reference does (its member convergeTrees, :661, has no reader
     //! there either: the trees converge on the first sync and take one update step per sync afterwards)

@@ -96,8 +96,9 @@ extern "C"
                                         pass (placeColumnsKernel): 4 + 2 K + 8 T bytes per particle (+ 4 with a merge) */
 #define CSTONE_STAGE_MULTIPOLES 15    /* cstone_hip_upsweep_multipoles: leaf multipoles + one launch per tree level */
 #define CSTONE_STAGE_GRAVITY 16       /* cstone_hip_compute_gravity: the Barnes-Hut group walk */
-#define CSTONE_NUM_STAGES 17
-    /* on: 0 off, 1 every stage, 2 only ENCODE, SORT_PASS(_IOTA), RESORT_LEAVES, GATHER(_H), HALOS, NEIGHBORS (the kernels that
+#define CSTONE_STAGE_ADAPT_H 17       /* cstone_hip_adapt_smoothing_lengths: the in-kernel iteration of h, one launch */
+#define CSTONE_NUM_STAGES 18
+    /* on: 0 off, 1 every stage, 2 only ENCODE, SORT_PASS(_IOTA), RESORT_LEAVES, GATHER(_H), HALOS, NEIGHBORS, ADAPT_H (the kernels that
      * move the particle arrays: eight brackets per sync instead of forty) */
     int cstone_hip_profile_enable(cstone_hip_ctx* ctx, int on);
     /* on != 0: every stage of every call is also wrapped in a roctx range "cstone:<stage>" (roctxRangePushA / Pop of
@@ -1057,6 +1058,66 @@ extern "C"
                                       void* az, void* phi, uint32_t* p2p_counts, uint32_t* m2p_counts,
                                       uint32_t* let_m2p_counts);
     int cstone_hip_domain_mr_octupoles_get(cstone_hip_domain_mr* dom, const void** octupoles, int32_t* num_nodes);
+
+    /* ---------------------------------------------------------------------------------------------
+     * Adaptive smoothing lengths (csrc/adapt_h.hip): every target's h iterated to a neighbour count of ng0 +- tol inside
+     * ONE kernel -- the loop "count neighbours, correct h, count again" that SPH clients run after a sync.  The reference
+     * has no such call; the rule below is this library's.  All arithmetic is in the coordinate type T with + - * / and
+     * comparisons only, products not fused, min(a, b) = b < a ? b : a, so a restatement in the same type reproduces h,
+     * counts and status bit for bit.  The same parameters for every target; per target i of [first, last):
+     *
+     *     h = h0 = h[i];  lo = 0;  hi = +inf;  hcap = h0 * T(grow_limit)
+     *     for it = 0 .. max_iter:
+     *         nn = number of j != i with |r_j - r_i|^2 < (2h)^2     -- the count of cstone_hip_find_neighbors at ext = 1
+     *                                                                  for this h (periodic fold decided from THIS h)
+     *         if nn + tol >= ng0 and nn <= ng0 + tol: stop (converged)
+     *         if it == max_iter:                      stop, NOT_CONVERGED
+     *         if nn + tol < ng0: lo = h; if h >= hcap: stop, CAPPED
+     *         else:              hi = h
+     *         q  = T(ng0) / T(max(nn, 1));  q = min(max(q, T(0.125)), T(8))
+     *         t  = (T(2) + q) / T(3);  t = (T(2) * t + q / (t * t)) / T(3)      -- two Newton steps towards cbrt(q)
+     *         hp = min(h * t, hcap)
+     *         if hi < +inf and not (lo < hp and hp < hi): hp = T(0.5) * (lo + hi)   -- bisect once both sides are known
+     *         if hp == h: stop, STALLED
+     *         h = hp
+     *
+     * h[i] is overwritten with the final h (in place: a walk reads only its own target's h); counts[i - first] = nn of the
+     * last walk; status[i - first] = number of walks done (bits 0-7, saturating at 255) | CSTONE_ADAPT_H_* flags.  No flag
+     * set: the final count lies within ng0 +- tol.  The loop ends for every input (at most max_iter + 1 walks): a NaN in h
+     * ends NOT_CONVERGED; h <= 0 finds nothing and stops after one walk, CAPPED (h >= hcap holds) or, where hcap is a NaN
+     * (0 * inf), STALLED.  ngmax > 0: the first ngmax neighbours of the final h, row-major
+     * neighbors[(i - first) * ngmax + k] exactly as cstone_hip_find_neighbors stores them for the output h, nothing written
+     * beyond min(count, ngmax) (one more walk of all targets).  ngmax == 0: neighbors may be NULL.
+     * Argument conventions of cstone_hip_find_neighbors; grow_limit >= 1, INFINITY allowed.  CSTONE_E_ARG with nothing
+     * written for: a null pointer, last < first, real_bits not 32 or 64, ng0 == 0, grow_limit < 1 or NaN, ngmax > 0 without
+     * neighbors.  Asynchronous on the context's stream; a traversal stack overflow ORs 4 into the sticky error word.
+     *
+     * domain_adapt_h    : the call for the particles [start_index, end_index) of the last sync on the view's octree;
+     *                     x, y, z, h laid out like the sync's results, counts / status indexed from start_index.
+     *                     grow_limit == 0: no limit (INFINITY).
+     * domain_mr_adapt_h : the same on several ranks, for the assigned particles, on the tree cstone_hip_domain_mr_octree_get
+     *                     returns (both halo modes serve it).  LOCAL: no collective.  Neighbours beyond the halos are not
+     *                     on the rank, and the halos of a sync cover 2 h_sync x the halo factor (set_halo_factor), so
+     *                     grow_limit == 0 means the domain's halo factor and a larger value is CSTONE_E_ARG (the counts
+     *                     would be silently wrong).  A second call before the next sync is CSTONE_E_ARG too: the cap would
+     *                     compound.  Afterwards the halo ranges of h are stale: cstone_hip_domain_mr_exchange_halos(h).
+     * ------------------------------------------------------------------------------------------- */
+#define CSTONE_ADAPT_H_NOT_CONVERGED 0x100u /* max_iter corrections made, the count is still outside ng0 +- tol */
+#define CSTONE_ADAPT_H_CAPPED 0x200u        /* too few neighbours at h == h0 * grow_limit */
+#define CSTONE_ADAPT_H_STALLED 0x400u       /* the next h equals the current one */
+    int cstone_hip_adapt_smoothing_lengths(cstone_hip_ctx* ctx, int real_bits, const void* x, const void* y,
+                                           const void* z, void* h, uint32_t first, uint32_t last,
+                                           const cstone_box* box_host, const int32_t* child_offsets,
+                                           const int32_t* internal_to_leaf, const uint32_t* layout, const void* centers,
+                                           const void* sizes, uint32_t ng0, uint32_t tol, uint32_t max_iter,
+                                           float grow_limit, uint32_t ngmax, uint32_t* neighbors, uint32_t* counts,
+                                           uint32_t* status);
+    int cstone_hip_domain_adapt_h(cstone_hip_domain* dom, const void* x, const void* y, const void* z, void* h,
+                                  uint32_t ng0, uint32_t tol, uint32_t max_iter, float grow_limit, uint32_t* counts,
+                                  uint32_t* status);
+    int cstone_hip_domain_mr_adapt_h(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z, void* h,
+                                     uint32_t ng0, uint32_t tol, uint32_t max_iter, float grow_limit, uint32_t* counts,
+                                     uint32_t* status);
 
 #ifdef __cplusplus
 }

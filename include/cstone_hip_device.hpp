@@ -140,13 +140,17 @@ struct NoStats
  *                  (dx = x_j - x_i after the periodic fold ...), by the lane of target i, in the order of the reference's
  *                  walk
  *  stats           optional observer (detail::NoStats: none)
- *  returns         the number of neighbours of this lane's target */
+ *  returns         the number of neighbours of this lane's target
+ *
+ *  traverseNeighborsH is the walk itself with the target's smoothing length handed in as a VALUE (hi): a kernel that
+ *  changes h between walks (csrc/adapt_h.hip) keeps it in a register and never reads the h array inside the walk.
+ *  traverseNeighbors(..., h, ...) below is traverseNeighborsH(..., h[i], ...). */
 template<class T, class F, class Stats = detail::NoStats>
-__device__ __forceinline__ uint32_t traverseNeighbors(bool valid, uint32_t i, const T* __restrict__ x,
-                                                      const T* __restrict__ y, const T* __restrict__ z,
-                                                      const T* __restrict__ h, const OctreeNsView<T>& tree,
-                                                      const DeviceBox<T>& box, float ext, TraversalStack& stack,
-                                                      int* errors, F&& onNeighbor, Stats&& stats = Stats{})
+__device__ __forceinline__ uint32_t traverseNeighborsH(bool valid, uint32_t i, const T* __restrict__ x,
+                                                       const T* __restrict__ y, const T* __restrict__ z, const T hi,
+                                                       const OctreeNsView<T>& tree, const DeviceBox<T>& box, float ext,
+                                                       TraversalStack& stack, int* errors, F&& onNeighbor,
+                                                       Stats&& stats = Stats{})
 {
     using detail::uniform;
     const unsigned lane = threadIdx.x & 63u;
@@ -154,7 +158,6 @@ __device__ __forceinline__ uint32_t traverseNeighbors(bool valid, uint32_t i, co
     uint64_t* sMask     = stack.mask;
 
     const T xi = x[i], yi = y[i], zi = z[i];
-    const T hi = h[i];
     const T radSq  = T(4.0) * hi * hi;
     const T cellSq = radSq * ext * ext;
     const bool px = box.bc[0] == 1, py = box.bc[1] == 1, pz = box.bc[2] == 1;
@@ -283,6 +286,18 @@ __device__ __forceinline__ uint32_t traverseNeighbors(bool valid, uint32_t i, co
         }
     }
     return nn;
+}
+
+//! the walk with the search radius 2 h[i] read from the particle array: see above
+template<class T, class F, class Stats = detail::NoStats>
+__device__ __forceinline__ uint32_t traverseNeighbors(bool valid, uint32_t i, const T* __restrict__ x,
+                                                      const T* __restrict__ y, const T* __restrict__ z,
+                                                      const T* __restrict__ h, const OctreeNsView<T>& tree,
+                                                      const DeviceBox<T>& box, float ext, TraversalStack& stack,
+                                                      int* errors, F&& onNeighbor, Stats&& stats = Stats{})
+{
+    return traverseNeighborsH(valid, i, x, y, z, h[i], tree, box, ext, stack, errors, static_cast<F&&>(onNeighbor),
+                              static_cast<Stats&&>(stats));
 }
 
 } // namespace cstone_hip
