@@ -81,11 +81,26 @@ int ensureAuxStream(cstone_hip_ctx* ctx)
     return CSTONE_OK;
 }
 
+int ensureTreeStream(cstone_hip_ctx* ctx)
+{
+    if (ctx->tree) return CSTONE_OK;
+    // highest priority: its kernels are tiny and are to be dispatched ahead of the remaining workgroups of whatever bulk
+    // kernel the other streams have in flight
+    int least = 0, greatest = 0;
+    CS_HIP(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
+    CS_HIP(ctx, hipStreamCreateWithPriority(&ctx->tree, hipStreamNonBlocking, greatest));
+    CS_HIP(ctx, hipEventCreateWithFlags(&ctx->evTreeFork, hipEventDisableTiming));
+    CS_HIP(ctx, hipEventCreateWithFlags(&ctx->evTreeJoin, hipEventDisableTiming));
+    return CSTONE_OK;
+}
+
 int arenaReserve(cstone_hip_ctx* ctx, size_t totalBytes)
 {
     totalBytes = alignUp(totalBytes) + 4096;
     if (totalBytes <= ctx->arenaBytes) return CSTONE_OK;
     if (ctx->arenaUsed != 0) return fail(ctx, CSTONE_E_INTERNAL, "arena grow while slices are live");
+    // (the block is used in the order of ctx->stream alone -- inside a StreamScope with its own arena that is the
+    //  scope's stream and the scope's block: nothing another stream reads is freed here)
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->arena) CS_HIP(ctx, hipFree(ctx->arena));
     ctx->arena      = nullptr;
@@ -247,7 +262,15 @@ int cstone_hip_ctx_destroy(cstone_hip_ctx* ctx)
         (void)hipEventDestroy(ctx->evJoin);
         (void)hipStreamDestroy(ctx->aux);
     }
+    if (ctx->tree)
+    {
+        (void)hipStreamSynchronize(ctx->tree);
+        (void)hipEventDestroy(ctx->evTreeFork);
+        (void)hipEventDestroy(ctx->evTreeJoin);
+        (void)hipStreamDestroy(ctx->tree);
+    }
     if (ctx->arena) (void)hipFree(ctx->arena);
+    if (ctx->sideArena) (void)hipFree(ctx->sideArena);
     if (ctx->devScalars) (void)hipFree(ctx->devScalars);
     if (ctx->hilbertTables) (void)hipFree(ctx->hilbertTables);
     if (ctx->hostScalars) (void)hipHostFree(ctx->hostScalars);

@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "cstone_hip.h"
@@ -23,6 +24,12 @@ struct cstone_hip_ctx
     char* arena       = nullptr;
     size_t arenaBytes = 0;
     size_t arenaUsed  = 0;
+    // the workspace of the OTHER chain while two chains of one call are being queued (StreamScope with ownArena swaps the
+    // two): a block is handed out, reused and grown in the order of ONE stream only -- the main stream's or the tree
+    // stream's --, so no slice is ever live on two streams and growing one block never frees what the other stream reads
+    char* sideArena       = nullptr;
+    size_t sideArenaBytes = 0;
+    size_t sideArenaUsed  = 0;
 
     // pinned host block for scalar results (one sync per read-back instead of symbol copies)
     int* hostScalars = nullptr; // [64]
@@ -38,10 +45,16 @@ struct cstone_hip_ctx
     // it -- Domain::sync gathers x, y, z there while the trees are updated on `stream` --, and the events that order the
     // two; whatever runs there is joined back into `stream` before the call returns
     hipStream_t aux    = nullptr;
-    bool auxBusy       = false; // between a fork onto the second stream and its join: a bandwidth kernel may be running
-                                // there, and workgroups of 1024 lanes would not find a CU until it has drained (sort.hip)
+    unsigned sideBusy  = 0; // SIDE_AUX | SIDE_TREE: between a fork onto another stream of the context and its join, two
+                            // chains share the CUs -- one of them a bandwidth kernel --, and workgroups of 1024 lanes
+                            // would not find a CU until that kernel has drained (sort.hip)
     hipEvent_t evFork  = nullptr;
     hipEvent_t evJoin  = nullptr;
+    // a third stream (ensureTreeStream), of the highest priority: the structural half of the focus-tree update of a
+    // re-sorted Domain::sync -- chains of tiny kernels -- runs there beside the mover bins and the leaf pass
+    hipStream_t tree       = nullptr;
+    hipEvent_t evTreeFork  = nullptr;
+    hipEvent_t evTreeJoin  = nullptr;
 
     // -1 unknown, else result of the one-time LDS atomic ordering probe of the radix sort (sort.hip)
     int ldsOrderOk = -1;
@@ -100,8 +113,16 @@ inline int fail(cstone_hip_ctx* ctx, int code, const char* fmt, ...)
         if (rc_ != CSTONE_OK) return rc_;                                                                              \
     } while (0)
 
+//! bits of ctx->sideBusy
+constexpr unsigned SIDE_AUX = 1, SIDE_TREE = 2;
+//! slots of devScalars / hostScalars the focus-tree update reports {changed, new leaf count} in.  Its own: the chain may
+//! run on the tree stream while the main stream uses [2..3] (global tree) and [16..31] (re-sort)
+constexpr int FOCUS_SCALARS = 32;
+
 //! creates ctx->aux and its events on first use
 int ensureAuxStream(cstone_hip_ctx* ctx);
+//! creates ctx->tree and its events on first use
+int ensureTreeStream(cstone_hip_ctx* ctx);
 
 /*! a few bytes from the device to PINNED host memory (hipHostMalloc: the context's hostScalars, a PinnedBlock ...) on the
  *  context's stream, by an ordinary kernel that stores through the mapped host pointer; the host reads them behind the
@@ -111,18 +132,32 @@ int ensureAuxStream(cstone_hip_ctx* ctx);
 int copyToPinned(cstone_hip_ctx* ctx, void* pinnedDst, const void* devSrc, size_t bytes);
 //! the same into ANY host memory (through a pinned block of the context) -- synchronises the stream
 int copyToHost(cstone_hip_ctx* ctx, void* dst, const void* devSrc, size_t bytes);
-//! the launches (and stage timers) of a scope go to another stream of the context
+//! the launches (and stage timers) of a scope go to another stream of the context; ownArena: and the arena calls of the
+//! scope to the context's second block (a chain with scans or sorts that is queued beside the main stream's)
 struct StreamScope
 {
     cstone_hip_ctx* ctx;
     hipStream_t saved;
-    StreamScope(cstone_hip_ctx* c, hipStream_t s)
+    bool ownArena;
+    StreamScope(cstone_hip_ctx* c, hipStream_t s, bool ownArena_ = false)
         : ctx(c)
         , saved(c->stream)
+        , ownArena(ownArena_)
     {
         ctx->stream = s;
+        if (ownArena) swapArenas();
     }
-    ~StreamScope() { ctx->stream = saved; }
+    ~StreamScope()
+    {
+        if (ownArena) swapArenas();
+        ctx->stream = saved;
+    }
+    void swapArenas()
+    {
+        std::swap(ctx->arena, ctx->sideArena);
+        std::swap(ctx->arenaBytes, ctx->sideArenaBytes);
+        std::swap(ctx->arenaUsed, ctx->sideArenaUsed);
+    }
 };
 
 //! reserve bytes from the arena; grows (with a stream sync) when too small. Pointers stay valid until arenaReset.

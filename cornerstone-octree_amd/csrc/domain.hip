@@ -162,6 +162,32 @@ public:
         if (!firstCall_ && n != bufSize_)
             return fail(ctx_, CSTONE_E_ARG, "Domain sync: input array sizes are inconsistent (%zu != %u)", n, bufSize_);
         SyncState s{xPP, yPP, zPP, hPP, static_cast<K*>(*keysPP), n, scratchAll, numScratch, props, propBytes, numProps};
+        const int rc = runStages(s);
+        // a sync that failed behind a fork onto the tree stream joins it: nothing of this sync is in flight afterwards
+        if (rc != CSTONE_OK && treeInFlight_)
+        {
+            (void)hipStreamSynchronize(ctx_->tree);
+            treeInFlight_ = false;
+        }
+        // ... and one that failed between focusRebuild and the end of focusCounts (all particles removed, found at the
+        // read-back of the re-sort; any CS_TRY of tryResort's tail, stepGlobalTree, joinTreeStream or focusCounts) holds
+        // the new tree with the counts and the layout of the old one: the next sync starts both trees from the root, as
+        // the first did
+        if (rc != CSTONE_OK && s.rebuilt && !s.converged && !s.treeDone)
+        {
+            firstCall_    = true;
+            layoutLeaves_ = -1;
+            deepestBound_ = int(maxLevel<K>());
+            levelRangeHost_.clear();
+        }
+        if (rc != CSTONE_OK) ctx_->sideBusy &= ~SIDE_TREE;
+        return rc;
+    }
+
+private:
+    struct SyncState;
+    int runStages(SyncState& s)
+    {
         CS_TRY(takeLevelRanges());
         // ---- GlobalAssignment::assign (assignment.hpp:57-103): box, keys, sort, one global-tree step
         CS_TRY(measureBoxFirst(s));
@@ -169,8 +195,12 @@ public:
         // The gather of x, y, z has no consumer inside a sync: with three or more scratch arrays it runs on the context's
         // second stream, next to the tree updates (chains of small, latency-bound kernels with two read-backs in between)
         // and the gather of h, and is joined before the call returns.
-        s.noOverlap   = std::getenv("CSTONE_NO_GATHER_OVERLAP") != nullptr; // tuning / tests
-        ctx_->auxBusy = false; // (a sync that failed behind its fork may have left it set)
+        s.noOverlap    = std::getenv("CSTONE_NO_GATHER_OVERLAP") != nullptr; // tuning / tests
+        // (tuning / tests: the order on one stream.  A tree that the last sync left as it was is expected to stay: then
+        //  there is nothing to hoist but the node ops, and those cost the encode more than they save -- the gather of
+        //  x, y, z bounds such a sync, not the tree: extras.zero_motion)
+        s.noHoist      = std::getenv("CSTONE_NO_TREE_HOIST") != nullptr || !treeChanged_;
+        ctx_->sideBusy = 0; // (a sync that failed behind a fork may have left a bit set)
         CS_TRY(tryResort(s));
         resortedThisSync_ = s.sorted;
         CS_TRY(encodeSortCheckBox(s));
@@ -181,12 +211,13 @@ public:
         // ---- h goes into SFC order for the halo radii (domain.hpp:213-215): gathered further down, in the pass that
         //      takes the maximum per leaf
         CS_TRY(updateFocusTree(s));
-        gHost_.takeReadBack(); // (updateFocus has synchronised the stream: the global counts are here)
+        s.treeDone = true;
         CS_TRY(layoutAndHalos(s));
         CS_TRY(gatherFields(s));
-        return finishSync(s);
+        return finishSync(s); // (its synchronisation brings the global counts: a hoisted sync has none before it)
     }
 
+public:
     void setHaloFactor(float factor) override { haloSearchExt_ = factor; }
     void setSortMode(int mode) override { sortMode_ = mode; }
     void setSpeculativeBox(bool on) override { speculativeBox_ = on; }
@@ -361,6 +392,14 @@ private:
         bool fieldsMoved    = false; // x, y, z, h are in their new order already (and radii follow from hmax)
         bool noOverlap      = false; // CSTONE_NO_GATHER_OVERLAP
         bool xyzForked = false, xyzJoined = false; // the gather of x, y, z on the second stream
+        bool noHoist        = false; // CSTONE_NO_TREE_HOIST
+        bool opsOnTree      = false; // focusOps of this sync was queued on the tree stream ...
+        bool opsTaken       = false; // ... and the host has read what it found:
+        int converged       = 0;     //     every node op is "keep"
+        NodeIdx newL        = 0;     //     leaves of the rebalanced tree
+        bool treeDone       = false; // the focus tree, its links and its counts are those of this sync
+        bool hoistLate      = false; // CSTONE_TREE_HOIST_LATE
+        bool rebuilt        = false; // focusRebuild is done or on its way on the tree stream: focusCounts is what is left
         uint32_t numAssigned = 0;    // particles without the remove marker
     };
 
@@ -465,7 +504,7 @@ private:
         }
         CS_TRY(rc);
         CS_HIP(ctx_, hipEventRecord(ctx_->evJoin, ctx_->aux));
-        ctx_->auxBusy = true;
+        ctx_->sideBusy |= SIDE_AUX;
         swapFieldsWithScratch(s, false);
         s.xyzForked = true;
         return CSTONE_OK;
@@ -474,8 +513,8 @@ private:
     int joinXyzGather(SyncState& s)
     {
         if (s.xyzForked && !s.xyzJoined) CS_HIP(ctx_, hipStreamWaitEvent(ctx_->stream, ctx_->evJoin, 0));
-        s.xyzJoined   = true;
-        ctx_->auxBusy = false;
+        s.xyzJoined = true;
+        ctx_->sideBusy &= ~SIDE_AUX;
         return CSTONE_OK;
     }
 
@@ -504,13 +543,37 @@ private:
                                carryFields ? rb : 0));
         const ResortArgs<K> ra = resort_.args();
         bool done              = false;
+        if (!s.noHoist)
+        {
+            // (fillCompactLeavesKernel was the last reader of the old tree on this stream: the tree stream starts here)
+            CS_TRY(ensureTreeStream(ctx_));
+            CS_HIP(ctx_, hipEventRecord(ctx_->evTreeFork, ctx_->stream));
+        }
         CS_TRY(computeKeysResort(ctx_, curve_, kb, rb, *s.xPP, *s.yPP, *s.zPP, s.keys, s.n, box_, &ra,
                                  s.speculate ? extentsDev() : nullptr, &done));
         if (!done) return CSTONE_OK;
         CS_TRY(resort_.binMovers(ctx_, tileLeaves));
         // one read-back: the extents (slots 16..27) and what the re-sort found (28..31)
         CS_TRY(copyToPinned(ctx_, ctx_->hostScalars + 16, ctx_->devScalars + 16, 16 * sizeof(int)));
+        // The device is busy with the encode and the mover bins from here on, and the host has nothing more to queue
+        // before it has seen what they found.  The structural half of the focus-tree update follows from the tree and the counts of
+        // the previous sync alone, and whatever becomes of the re-sort, this sync needs it: the node ops go to the tree
+        // stream now (not before the encode is queued: the idle device would wait for the host), the host takes their result
+        // and queues the rebalance and the linked octree behind them -- all of it beside the encode.
+        // CSTONE_TREE_HOIST_LATE=1 (tuning): the rebuild beside the leaf pass instead, once the re-sort is accepted
+        if (!s.noHoist)
+        {
+            s.hoistLate = std::getenv("CSTONE_TREE_HOIST_LATE") != nullptr;
+            CS_TRY(forkFocusOps(s));
+            if (!s.hoistLate)
+            {
+                CS_TRY(takeFocusOps(s));
+                CS_TRY(forkFocusRebuild(s));
+            }
+        }
         CS_HIP(ctx_, hipStreamSynchronize(ctx_->stream));
+        // (CSTONE_TREE_HOIST_LATE: the node ops on the tree stream have long finished, no wait of its own)
+        if (s.opsOnTree && !s.opsTaken) CS_TRY(takeFocusOps(s));
         cstone_box next = box_;
         if (s.speculate)
         {
@@ -526,6 +589,9 @@ private:
         s.resortMarkers        = markers;
         if (!boxChanged && resortAccepted(flags, movers, s.n))
         {
+            // (stepGlobalTree would find this too, further down: no leaf pass, gather or tree step for nothing.  With
+            //  the rebuild on its way already, sync() puts the domain back to its first-call state)
+            if (s.opsTaken && markers >= s.n) return fail(ctx_, CSTONE_E_ARG, "domain_sync: all particles removed");
             if (carryFields)
             {
                 ResortFields rf{rb, {*s.xPP, *s.yPP, *s.zPP, *s.hPP}, {s.scratch[0], s.scratch[1], s.scratch[2], s.scratch[3]}};
@@ -540,6 +606,9 @@ private:
                                           tileLeaves, (flags & RESORT_LARGE_QUIET_TILES) != 0));
                 CS_TRY(forkXyzGather(s, s.n - markers)); // (the ordering is final: x, y, z follow on the second stream)
             }
+            // placeMovers and the leaf pass are queued: the rebalance and the linked octree run beside them.  Everything
+            // that read the old tree (prepare's fillCompactLeavesKernel; `attempt` above) lies before the read-back
+            if (s.opsTaken && !s.rebuilt) CS_TRY(forkFocusRebuild(s));
             CS_HIP(ctx_, hipMemsetAsync(ctx_->devScalars + 3, 0, sizeof(int), ctx_->stream));
             s.sorted    = true;
             lastMovers_ = movers;
@@ -548,6 +617,8 @@ private:
         }
         // the caller's key array has not been touched: the regular path starts from scratch, with the box this sync
         // needs (the extents are known by now)
+        // (the radix sort is next: it takes its large tiles again once the tree stream is joined -- it finished long ago)
+        if (s.rebuilt) CS_TRY(joinTreeStream());
         if (boxChanged) { adoptChangedBox(next); }
         else
         {
@@ -678,7 +749,72 @@ private:
                 if (++guard > 64) return fail(ctx_, CSTONE_E_INTERNAL, "focus tree does not converge");
             }
         }
+        if (s.rebuilt)
+        {
+            // the re-sorted sync: the structure is on its way on the tree stream, the counts follow it on this one
+            CS_TRY(joinTreeStream());
+            return focusCounts(s.keys, s.numAssigned, s.converged);
+        }
+        if (s.opsOnTree)
+        {
+            // the re-sort fell back (or never started) behind the fork of the node ops: they are not made again, the
+            // rest keeps its place and its stream.  The radix passes saturate the memory system as the gather does
+            // here, so there is no better place for the rebuild on this path
+            if (!s.opsTaken) CS_TRY(takeFocusOps(s));
+            CS_TRY(focusRebuild(s.converged, s.newL));
+            return focusCounts(s.keys, s.numAssigned, s.converged);
+        }
         return updateFocus(s.keys, s.numAssigned, &conv);
+    }
+
+    //! focusOps of this sync on the tree stream, behind the leaf-table prepare of the main stream (evTreeFork stands
+    //! behind its fillCompactLeavesKernel, the last reader of the old tree)
+    int forkFocusOps(SyncState& s)
+    {
+        CS_HIP(ctx_, hipStreamWaitEvent(ctx_->tree, ctx_->evTreeFork, 0));
+        int rc;
+        {
+            StreamScope scope(ctx_, ctx_->tree, true);
+            treeInFlight_ = true;
+            rc            = focusOps();
+        }
+        CS_TRY(rc);
+        CS_HIP(ctx_, hipEventRecord(ctx_->evTreeJoin, ctx_->tree));
+        s.opsOnTree = true;
+        return CSTONE_OK;
+    }
+    //! the host waits for the node ops on the tree stream and reads {changed, new leaf count}
+    int takeFocusOps(SyncState& s)
+    {
+        CS_HIP(ctx_, hipEventSynchronize(ctx_->evTreeJoin));
+        treeInFlight_ = false;
+        s.opsTaken    = true;
+        return readFocusOps(&s.converged, &s.newL);
+    }
+    //! focusRebuild on the tree stream (the host knows the new leaf count), behind the node ops and with them behind the
+    //! last reader of the old tree on the main stream.  An unchanged tree has nothing to rebuild
+    int forkFocusRebuild(SyncState& s)
+    {
+        s.rebuilt = true;
+        if (s.converged) return CSTONE_OK;
+        ctx_->sideBusy |= SIDE_TREE; // (the node-key sort takes its 256-lane tiles beside the encode or the leaf pass)
+        int rc;
+        {
+            StreamScope scope(ctx_, ctx_->tree, true);
+            treeInFlight_ = true;
+            rc            = focusRebuild(s.converged, s.newL);
+        }
+        CS_TRY(rc);
+        CS_HIP(ctx_, hipEventRecord(ctx_->evTreeJoin, ctx_->tree));
+        return CSTONE_OK;
+    }
+    //! the main stream waits for the tree stream (the pinned level ranges included: they are written there)
+    int joinTreeStream()
+    {
+        if (treeInFlight_) CS_HIP(ctx_, hipStreamWaitEvent(ctx_->stream, ctx_->evTreeJoin, 0));
+        treeInFlight_ = false;
+        ctx_->sideBusy &= ~SIDE_TREE;
+        return CSTONE_OK;
     }
 
     //! Halos::discover + computeLayout (halos.hpp:128-222) for the assignment [0, L); h goes into SFC order on the way
@@ -774,7 +910,10 @@ private:
 #ifdef CSTONE_TEST_HOOKS // (tests: CSTONE_FORCE_DEVICE_ERROR raises the error word)
         if (std::getenv("CSTONE_FORCE_DEVICE_ERROR")) CS_HIP(ctx_, hipMemsetAsync(ctx_->devScalars + 63, 1, 1, ctx_->stream));
 #endif
-        return cstone_hip_ctx_sync(ctx_);
+        const int rc = cstone_hip_ctx_sync(ctx_);
+        // (the stream has been synchronised: the global counts stepGlobalTree queued are here)
+        if (rc != CSTONE_E_HIP) gHost_.takeReadBack();
+        return rc;
     }
     int buildFocusOctree()
     {
@@ -802,14 +941,27 @@ private:
     }
 
     /*! one FocusedOctree::updateTree + updateCounts + updateGeoCenters step on one rank
-     *  (octree_focus_mpi.hpp:108-187,205-273; octree_focus.hpp:83-137; rebalance.hpp:50-184) */
+     *  (octree_focus_mpi.hpp:108-187,205-273; octree_focus.hpp:83-137; rebalance.hpp:50-184), cut where the data
+     *  dependencies are: focusOps and focusRebuild need the tree, its links and its counts as the previous sync left
+     *  them, only focusCounts needs this sync's keys (and box).  All three queue on ctx_->stream. */
     int updateFocus(const K* keys, size_t n, int* converged)
+    {
+        CS_TRY(focusOps());
+        CS_HIP(ctx_, hipStreamSynchronize(ctx_->stream));
+        NodeIdx newL = 0;
+        CS_TRY(readFocusOps(converged, &newL));
+        CS_TRY(focusRebuild(*converged, newL));
+        return focusCounts(keys, n, *converged);
+    }
+
+    //! node ops from the counts at hand, their scan over the leaves, {changed, new leaf count} on the way to the host; no wait
+    int focusOps()
     {
         const NodeIdx L = fLeaves_, I = (L - 1) / 7, M = L + I;
         CS_TRY(ops_.ensure(ctx_, size_t(M + 1) * sizeof(NodeIdx)));
         CS_TRY(ops2_.ensure(ctx_, size_t(M + 1) * sizeof(NodeIdx)));
         CS_TRY(leafOps_.ensure(ctx_, size_t(L + 1) * sizeof(uint32_t)));
-        int* scalars = ctx_->devScalars;
+        int* scalars = ctx_->devScalars + FOCUS_SCALARS;
         CS_HIP(ctx_, hipMemsetAsync(scalars, 0, 2 * sizeof(int), ctx_->stream));
         hipLaunchKernelGGL(focusOpsKernel<K>, gridFor(M, 256), 256, 0, ctx_->stream, fPrefixes_.as<K>(),
                            fChild_.as<NodeIdx>(), fParents_.as<NodeIdx>(), fCounts_.as<uint32_t>(), M, bucketFocus_,
@@ -824,35 +976,47 @@ private:
                          (uint32_t*)scalars + 1);
         arenaReset(ctx_);
         CS_TRY(rc);
-        CS_TRY(copyToPinned(ctx_, ctx_->hostScalars, scalars, 2 * sizeof(int)));
-        CS_HIP(ctx_, hipStreamSynchronize(ctx_->stream));
-        *converged           = ctx_->hostScalars[0] == 0;
-        const NodeIdx newL   = ctx_->hostScalars[1];
-        if (newL < 1) return fail(ctx_, CSTONE_E_INTERNAL, "focus rebalance produced %d leaves", newL);
+        return copyToPinned(ctx_, ctx_->hostScalars + FOCUS_SCALARS, scalars, 2 * sizeof(int));
+    }
 
-        if (!*converged)
-        {
-            CS_TRY(newTree_.ensure(ctx_, size_t(newL + 1) * sizeof(K)));
-            CS_TRY(cstone_hip_rebalance_tree(ctx_, 8 * sizeof(K), fTree_.p, L, newL, leafOps_.as<int32_t>(),
-                                             newTree_.p));
-            // the new leaf array BECOMES the tree (the two buffers change places; the counts are made anew below).  It
-            // used to be copied back: 18 MB at 10^8 particles, a blit with a handful of waves that got next to nothing
-            // of the memory system while the gather of x, y, z ran on the second stream -- 0.62 ms during which the
-            // rest of the tree update waited (profiles/r04: the copy ended with the gather)
-            std::swap(fTree_.p, newTree_.p);
-            std::swap(fTree_.bytes, newTree_.bytes);
-            CS_TRY(fLeafCounts_.ensure(ctx_, size_t(newL) * sizeof(uint32_t)));
-            fCap_    = int(std::min(fTree_.bytes / sizeof(K) - 1, fLeafCounts_.bytes / sizeof(uint32_t)));
-            fLeaves_ = newL;
-            CS_TRY(buildFocusOctree());
-        }
-        // else: every node op is "keep" -- the leaf array and with it the linked octree are what they were; the reference
+    //! behind a wait for focusOps
+    int readFocusOps(int* converged, NodeIdx* newL)
+    {
+        *converged = ctx_->hostScalars[FOCUS_SCALARS] == 0;
+        *newL      = ctx_->hostScalars[FOCUS_SCALARS + 1];
+        if (*newL < 1) return fail(ctx_, CSTONE_E_INTERNAL, "focus rebalance produced %d leaves", *newL);
+        return CSTONE_OK;
+    }
+
+    //! a tree that changed: the rebalanced leaf array and its linked octree; fLeaves_ = newL from here on
+    int focusRebuild(int converged, NodeIdx newL)
+    {
+        // every node op is "keep" -- the leaf array and with it the linked octree are what they were; the reference
         // rebuilds them regardless (octree_focus.hpp:121-134) because it parks its temporaries in the tree's own arrays
+        if (converged) return CSTONE_OK;
+        const NodeIdx L = fLeaves_;
+        CS_TRY(newTree_.ensure(ctx_, size_t(newL + 1) * sizeof(K)));
+        CS_TRY(cstone_hip_rebalance_tree(ctx_, 8 * sizeof(K), fTree_.p, L, newL, leafOps_.as<int32_t>(), newTree_.p));
+        // the new leaf array BECOMES the tree (the two buffers change places; the counts are made anew in focusCounts).
+        // It used to be copied back: 18 MB at 10^8 particles, a blit with a handful of waves that got next to nothing
+        // of the memory system while the gather of x, y, z ran on the second stream -- 0.62 ms during which the
+        // rest of the tree update waited (profiles/r04: the copy ended with the gather)
+        std::swap(fTree_.p, newTree_.p);
+        std::swap(fTree_.bytes, newTree_.bytes);
+        CS_TRY(fLeafCounts_.ensure(ctx_, size_t(newL) * sizeof(uint32_t)));
+        fCap_    = int(std::min(fTree_.bytes / sizeof(K) - 1, fLeafCounts_.bytes / sizeof(uint32_t)));
+        fLeaves_ = newL;
+        return buildFocusOctree();
+    }
 
-        // updateCounts: leaf counts from the particle keys, scattered to the linked layout, summed bottom-up
-        const NodeIdx newI = (newL - 1) / 7, newM = newL + newI;
+    //! updateCounts: leaf counts from the particle keys, scattered to the linked layout, summed bottom-up; then the
+    //! geometric centres, which need the box this sync ends with
+    int focusCounts(const K* keys, size_t n, int converged)
+    {
+        const NodeIdx newL = fLeaves_, newI = (newL - 1) / 7, newM = newL + newI;
+        treeChanged_       = !converged;
         // the leaf boundaries of an unchanged tree are searched from where they were at the previous sync (layout_)
-        const uint32_t* guess = (*converged && layoutLeaves_ == newL) ? layout_.as<uint32_t>() : nullptr;
+        const uint32_t* guess = (converged && layoutLeaves_ == newL) ? layout_.as<uint32_t>() : nullptr;
         // a sync that was re-sorted knows where the particles of every old leaf went: a boundary that an old leaf had
         // already is looked up, any other is searched inside one old leaf (resort.hip, countLeaves)
         if (resortedThisSync_)
@@ -868,7 +1032,7 @@ private:
         // updateGeoCenters: the geometry of the nodes follows from the tree and the box alone -- nothing to do for an
         // unchanged tree inside an unchanged box (the reference recomputes it in every sync, octree_focus_mpi.hpp:259-273)
         const bool sameBox = centersNodes_ == newM && sameLimits(centersBox_, box_);
-        if (!(*converged && sameBox))
+        if (!(converged && sameBox))
         {
             CS_TRY(fCenters_.ensure(ctx_, size_t(newM) * 3 * sizeof(T)));
             CS_TRY(fSizes_.ensure(ctx_, size_t(newM) * 3 * sizeof(T)));
@@ -905,6 +1069,8 @@ private:
     std::vector<NodeIdx> levelRangeHost_; // of the tree the LAST sync left behind (exact)
     NodeIdx* pinnedLevels_ = nullptr;     // where the level ranges of a rebuilt tree arrive
     bool levelsPending_    = false;
+    bool treeChanged_      = true;  // the last focus update rebuilt the tree
+    bool treeInFlight_     = false; // work of this sync is queued on the tree stream and not joined yet
     int deepestBound_      = int(maxLevel<K>()); // no leaf of the current focus tree is deeper
     int fullSortFallbacks_ = 0;
     DevBuf fPrefixes_, fChild_, fParents_, fLevelRange_, fItl_, fLti_, fCenters_, fSizes_;

@@ -801,7 +801,7 @@ private:
         }
         pending_ = 0, toggled_ = false;
         CS_TRY(joinPlace()); // (a sync that was abandoned behind its fork: whatever it left on the second stream comes first)
-        ctx_->auxBusy = false;
+        ctx_->sideBusy &= ~SIDE_AUX;
         if (s.numProps < 0 || s.numProps > MAX_PROPS) setPending(CSTONE_E_ARG, "domain_mr_sync: at most %d properties", MAX_PROPS);
         for (int q = 0; q < s.numProps && !pending_; ++q)
             if ((s.n && !s.props[q]) || !gatherableElement(s.propBytes[q])) // an empty rank may pass null arrays
@@ -1149,7 +1149,7 @@ private:
             CS_TRY(rc);
             CS_HIP(ctx_, hipEventRecord(ctx_->evJoin, ctx_->aux));
             placeForked_  = true;
-            ctx_->auxBusy = true;
+            ctx_->sideBusy |= SIDE_AUX;
         }
         for (int c = 0; c < 3 && nb && !overlap; ++c)
             CS_TRY(cstone_hip_scatter(ctx_, sizeof(T), posB_.as<uint32_t>(), nb, rcolS_[c].p, dst[c]));
@@ -1384,7 +1384,7 @@ private:
         if (!placeForked_) return CSTONE_OK;
         CS_HIP(ctx_, hipStreamWaitEvent(ctx_->stream, ctx_->evJoin, 0));
         placeForked_  = false;
-        ctx_->auxBusy = false;
+        ctx_->sideBusy &= ~SIDE_AUX;
         return CSTONE_OK;
     }
 

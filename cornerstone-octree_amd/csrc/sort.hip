@@ -1115,8 +1115,9 @@ int sortPairs(cstone_hip_ctx* ctx, K* keys, uint32_t* vals, size_t n, K* keysAlt
     // (16 Ki-pair tiles are workgroups of 1024 lanes: while a bandwidth kernel of the same context fills the CUs from the
     //  second stream -- the gather of x, y, z, placeColumnsKernel -- four of its workgroups never finish on one CU at the
     //  same moment, and the first digit pass of the tree's node sort sat there until that kernel had drained: 0.28 ms
-    //  (single-rank sync) and 0.73 ms (multi-rank) instead of 0.02 ms at 2.6 million node keys)
-    bool large       = n >= largeTileThreshold() && !ctx->auxBusy;
+    //  (single-rank sync) and 0.73 ms (multi-rank) instead of 0.02 ms at 2.6 million node keys.  The same holds for the
+    //  node sort on the tree stream beside the leaf pass: any fork of the context that is not joined yet)
+    bool large       = n >= largeTileThreshold() && ctx->sideBusy == 0;
     size_t tile      = large ? SortCfg<K, LARGE_BLOCK>::TILE : SortCfg<K, SMALL_BLOCK>::TILE;
     size_t usedBytes = (headerWords(P) + size_t(P) * (n / tile) * RADIX) * sizeof(uint32_t);
     if (histogramState != 2) CS_HIP(ctx, hipMemsetAsync(temp, 0, usedBytes, ctx->stream));

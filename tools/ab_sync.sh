@@ -10,6 +10,7 @@ for rep in 1 2; do
 run A=0
 run CSTONE_DEVICE_GLOBAL_STEP=1
 run CSTONE_NO_GATHER_OVERLAP=1
+run CSTONE_NO_TREE_HOIST=1
 run CSTONE_DEVICE_GLOBAL_STEP=1 CSTONE_NO_GATHER_OVERLAP=1
 done
 mr A=0
