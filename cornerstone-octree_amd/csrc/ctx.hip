@@ -56,7 +56,7 @@ const char* stageName(int stage)
                                                    "cstone:link_octree", "cstone:halos",       "cstone:neighbors",
                                                    "cstone:minmax",      "cstone:sort_pass_iota", "cstone:resort_bins",
                                                    "cstone:resort_leaves", "cstone:gather_h",  "cstone:place",
-                                                   "cstone:multipoles", "cstone:gravity", "cstone:adapt_h"};
+                                                   "cstone:multipoles", "cstone:gravity", "cstone:adapt_h", "cstone:fof"};
     return stage >= 0 && stage < CSTONE_NUM_STAGES ? names[stage] : "cstone:?";
 }
 } // namespace
@@ -143,7 +143,7 @@ StageTimer::StageTimer(cstone_hip_ctx* c, int stage)
     const bool heavy = stage == CSTONE_STAGE_ENCODE || stage == CSTONE_STAGE_SORT_PASS ||
                        stage == CSTONE_STAGE_SORT_PASS_IOTA || stage == CSTONE_STAGE_GATHER ||
                        stage == CSTONE_STAGE_RESORT_LEAVES || stage == CSTONE_STAGE_HALOS || stage == CSTONE_STAGE_GATHER_H || stage == CSTONE_STAGE_PLACE ||
-                       stage == CSTONE_STAGE_NEIGHBORS || stage == CSTONE_STAGE_ADAPT_H;
+                       stage == CSTONE_STAGE_NEIGHBORS || stage == CSTONE_STAGE_ADAPT_H || stage == CSTONE_STAGE_FOF;
     if (ctx->profiling == 2 && !heavy) return;
     cstone_hip_ctx::Bracket b{stage, takeEvent(ctx), takeEvent(ctx)};
     (void)hipEventRecord(b.a, ctx->stream);

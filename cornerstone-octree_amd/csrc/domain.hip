@@ -134,6 +134,8 @@ struct DomainBase
                                int order, double G, double eps2, void* ax, void* ay, void* az, void* phi) = 0;
     virtual int adaptH(const void* x, const void* y, const void* z, void* h, uint32_t ng0, uint32_t tol, uint32_t maxIter,
                        float growLimit, uint32_t* counts, uint32_t* status) = 0;
+    virtual int fof(const void* x, const void* y, const void* z, double linkingLength, uint32_t* labels,
+                    uint32_t* groupSizes, uint32_t* numGroups) = 0;
     virtual void stats(cstone_hip_domain_stats* out)     = 0;
 };
 
@@ -265,6 +267,16 @@ public:
                                                   fChild_.as<int32_t>(), fItl_.as<int32_t>(), layout_.as<uint32_t>(),
                                                   fCenters_.p, fSizes_.p, ng0, tol, maxIter, growLimit, 0, nullptr, counts,
                                                   status);
+    }
+
+    //! cstone_hip_friends_of_friends for [start_index, end_index) of the last sync on the focus tree of the view
+    int fof(const void* x, const void* y, const void* z, double linkingLength, uint32_t* labels, uint32_t* groupSizes,
+            uint32_t* numGroups) override
+    {
+        if (firstCall_ || fLeaves_ < 1) return fail(ctx_, CSTONE_E_ARG, "domain_fof: no sync yet");
+        return cstone_hip_friends_of_friends(ctx_, rb, x, y, z, startIndex_, endIndex_, &box_, fChild_.as<int32_t>(),
+                                             fItl_.as<int32_t>(), layout_.as<uint32_t>(), fCenters_.p, fSizes_.p,
+                                             linkingLength, labels, groupSizes, numGroups);
     }
 
     /*! Domain::updateExpansionCenters (R/domain/domain.hpp:415-421) on one rank = FocusedOctree::updateCenters without its
@@ -1206,6 +1218,13 @@ int cstone_hip_domain_adapt_h(cstone_hip_domain* dom, const void* x, const void*
 {
     if (!dom) return CSTONE_E_ARG;
     return dom->impl->adaptH(x, y, z, h, ng0, tol, max_iter, grow_limit, counts, status);
+}
+
+int cstone_hip_domain_fof(cstone_hip_domain* dom, const void* x, const void* y, const void* z, double linking_length,
+                          uint32_t* labels, uint32_t* group_sizes, uint32_t* num_groups)
+{
+    if (!dom) return CSTONE_E_ARG;
+    return dom->impl->fof(x, y, z, linking_length, labels, group_sizes, num_groups);
 }
 
 int cstone_hip_domain_view_get(cstone_hip_domain* dom, cstone_hip_domain_view* out)

@@ -20,7 +20,7 @@ MORTON, HILBERT = 0, 1
 STAGES = {
     "encode": 0, "sort_hist": 1, "sort_pass": 2, "gather": 3, "node_counts": 4, "rebalance": 5, "link_octree": 6,
     "halos": 7, "neighbors": 8, "minmax": 9, "sort_pass_iota": 10, "resort_bins": 11, "resort_leaves": 12, "gather_h": 13, "place": 14,
-    "multipoles": 15, "gravity": 16, "adapt_h": 17,
+    "multipoles": 15, "gravity": 16, "adapt_h": 17, "fof": 18,
 }
 
 EXPORTS = [
@@ -70,6 +70,8 @@ EXPORTS = [
     "cstone_hip_domain_mr_octupoles_get",
     # adaptive smoothing lengths: h iterated to a neighbour count inside one kernel (csrc/adapt_h.hip)
     "cstone_hip_adapt_smoothing_lengths", "cstone_hip_domain_adapt_h", "cstone_hip_domain_mr_adapt_h",
+    # friends-of-friends groups: lock-free union-find on the neighbour walk (csrc/fof.hip)
+    "cstone_hip_friends_of_friends", "cstone_hip_fof_catalog", "cstone_hip_domain_fof",
 ]
 
 # status word of the adapt calls: number of walks in bits 0-7, then the CSTONE_ADAPT_H_* flags
@@ -542,6 +544,38 @@ class Context:
             _ptr(centers), _ptr(sizes), C.c_uint32(ng0), C.c_uint32(tol), C.c_uint32(max_iter), C.c_float(grow_limit),
             C.c_uint32(ngmax), _ptr(nidx), _ptr(nc), _ptr(st)), "adapt_smoothing_lengths")
         return nidx, nc, st
+
+    def friends_of_friends(self, x, y, z, first, last, box, octree, layout, centers, sizes, linking_length,
+                           want_sizes=True, want_num_groups=True):
+        """cstone_hip_friends_of_friends: (labels [last - first], group sizes or None, number of groups or None); labels hold
+        the lowest particle index of each particle's group (the rule: include/cstone_hip.h).  Asking for the number of
+        groups synchronises the stream"""
+        torch = _torch()
+        nw = last - first
+        labels = torch.zeros(nw, dtype=torch.int32, device=x.device)
+        gs = torch.zeros(nw, dtype=torch.int32, device=x.device) if want_sizes else None
+        ng = C.c_uint32(0)
+        self._chk(self.lib.cstone_hip_friends_of_friends(
+            self.h, C.c_int(x.element_size() * 8), _ptr(x), _ptr(y), _ptr(z), C.c_uint32(first), C.c_uint32(last),
+            C.byref(box), _ptr(octree["child_offsets"]), _ptr(octree["internal_to_leaf"]), _ptr(layout), _ptr(centers),
+            _ptr(sizes), C.c_double(linking_length), _ptr(labels), _ptr(gs),
+            C.byref(ng) if want_num_groups else None), "friends_of_friends")
+        return labels, gs, (ng.value if want_num_groups else None)
+
+    def fof_catalog(self, labels, first, last, min_members=1, capacity=None):
+        """cstone_hip_fof_catalog: (group_offsets [num_groups + 1], members [number of particles listed]) of the groups with
+        at least min_members members, by ascending label, members ascending"""
+        torch = _torch()
+        nw = last - first
+        cap = nw + 1 if capacity is None else capacity
+        offsets = torch.zeros(max(cap, 1), dtype=torch.int32, device=labels.device)
+        members = torch.zeros(max(nw, 1), dtype=torch.int32, device=labels.device)
+        ng = C.c_uint32(0)
+        self._chk(self.lib.cstone_hip_fof_catalog(self.h, _ptr(labels), C.c_uint32(first), C.c_uint32(last),
+                                                  C.c_uint32(min_members), _ptr(offsets), C.c_size_t(cap), _ptr(members),
+                                                  C.byref(ng)), "fof_catalog")
+        offsets = offsets[:ng.value + 1]
+        return offsets, members[:int(offsets[-1].item())]
 
     def compute_fixed_groups(self, first, last, group_size):
         torch = _torch()

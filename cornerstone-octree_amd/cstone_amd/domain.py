@@ -172,6 +172,25 @@ class Domain:
         self.ctx._chk(rc, "domain_adapt_h")
         return nc, st
 
+    def fof(self, x, y, z, linking_length, want_sizes=True):
+        """cstone_hip_domain_fof: friends-of-friends groups of the particles [start_index, end_index) of the last sync at
+        the given linking length on the view's octree; x, y, z laid out like the sync's results.  Returns (labels, group
+        sizes or None, number of groups), indexed from start_index; a label is the lowest index (into the synced arrays)
+        among the members of the particle's group"""
+        import torch
+
+        v = self.view()
+        nw = v.end_index - v.start_index
+        labels = torch.zeros(nw, dtype=torch.int32, device=x.device)
+        gs = torch.zeros(nw, dtype=torch.int32, device=x.device) if want_sizes else None
+        ng = C.c_uint32(0)
+        rc = self.ctx.lib.cstone_hip_domain_fof(self.h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()),
+                                                C.c_void_p(z.data_ptr()), C.c_double(linking_length),
+                                                C.c_void_p(labels.data_ptr()),
+                                                C.c_void_p(gs.data_ptr() if want_sizes else None), C.byref(ng))
+        self.ctx._chk(rc, "domain_fof")
+        return labels, gs, ng.value
+
     def reapply_sync(self, field):
         """Domain::reapplySync: field (n rows of the last sync's input, 1..32 bytes each) in the order of the result"""
         import torch

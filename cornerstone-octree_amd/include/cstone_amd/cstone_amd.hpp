@@ -704,6 +704,50 @@ void adaptSmoothingLengthsGpu(const T* x, const T* y, const T* z, T* h, LocalInd
                    "adaptSmoothingLengthsGpu");
 }
 
+/*! Friends-of-friends groups (cstone_hip_friends_of_friends; the rule is stated in include/cstone_hip.h): particles of
+ *  [first, last) closer than linkingLength are friends, groups are the connected components.  labels[i - first]: the lowest
+ *  particle index of i's group (a canonical value: identical in every run); groupSizes[i - first] (nullable): the number
+ *  of members of i's group.  Returns the number of groups (which synchronises the stream), or 0 without a synchronisation
+ *  when countGroups is false.  linkingLength must be below half of every periodic box edge. */
+template<class T, class KeyType>
+unsigned friendsOfFriendsGpu(const T* x, const T* y, const T* z, LocalIndex first, LocalIndex last, const Box<T>& box,
+                             const OctreeNsView<T, KeyType>& tree, double linkingLength, LocalIndex* labels,
+                             unsigned* groupSizes = nullptr, bool countGroups = true)
+{
+    unsigned numGroups = 0;
+    Context::check(cstone_hip_friends_of_friends(Context::get(), detail::realBits<T>(), x, y, z, first, last, &box.pod(),
+                                                 tree.childOffsets, tree.internalToLeaf, tree.layout, tree.centers,
+                                                 tree.sizes, linkingLength, labels, groupSizes,
+                                                 countGroups ? &numGroups : nullptr),
+                   "friendsOfFriendsGpu");
+    return numGroups;
+}
+
+/*! The catalogue of the groups with at least minMembers members (cstone_hip_fof_catalog), ordered by ascending label:
+ *  members[groupOffsets[g] .. groupOffsets[g + 1]) are the particle indices of group g, ascending.  Both vectors are
+ *  resized to fit (groupOffsets: number of groups + 1).  Returns the number of groups. */
+inline unsigned fofCatalogGpu(const LocalIndex* labels, LocalIndex first, LocalIndex last, unsigned minMembers,
+                              DeviceVector<LocalIndex>& groupOffsets, DeviceVector<LocalIndex>& members)
+{
+    unsigned numGroups = 0;
+    if (groupOffsets.size() < 1) groupOffsets.resize(1);
+    members.resize(last - first);
+    int rc = cstone_hip_fof_catalog(Context::get(), labels, first, last, minMembers, groupOffsets.data(), groupOffsets.size(),
+                                    members.data(), &numGroups);
+    if (rc == CSTONE_E_CAPACITY)
+    {
+        groupOffsets = DeviceVector<LocalIndex>(std::size_t(numGroups) + 1);
+        rc = cstone_hip_fof_catalog(Context::get(), labels, first, last, minMembers, groupOffsets.data(),
+                                    groupOffsets.size(), members.data(), &numGroups);
+    }
+    Context::check(rc, "fofCatalogGpu");
+    groupOffsets.resize(std::size_t(numGroups) + 1);
+    LocalIndex listed = 0;
+    memcpyD2H(groupOffsets.data() + numGroups, 1, &listed);
+    members.resize(listed);
+    return numGroups;
+}
+
 /*! The transport of the multi-rank Domain on a node of MI355X: RCCL, served from C++ inside libcstone_hip on the context's
  *  stream (csrc/comm_rccl.hip) -- replaces the MPI point-to-point exchanges of the reference
  *  (R/domain/domaindecomp_mpi_gpu.cuh:86-185, R/halos/exchange_halos_gpu.cuh:35-119).  One rank obtains the id
@@ -1338,6 +1382,23 @@ public:
         Context::check(cstone_hip_domain_adapt_h(dom_, x.data(), y.data(), z.data(), h.data(), ng0, tol, maxIter, growLimit,
                                                  counts.data(), status.data()),
                        "Domain::adaptSmoothingLengths");
+    }
+    /*! Friends-of-friends groups (cstone_hip_domain_fof) of the particles [startIndex(), endIndex()) of the last sync at the
+     *  given linking length; x, y, z laid out like the result arrays.  labels (and groupSizes, if given) are resized to
+     *  nParticles() and indexed from startIndex(); a label is the lowest index into the synced arrays among the members of
+     *  the particle's group.  Returns the number of groups.  One rank: groups are not joined across ranks. */
+    unsigned friendsOfFriends(const DeviceVector<T>& x, const DeviceVector<T>& y, const DeviceVector<T>& z,
+                              double linkingLength, DeviceVector<LocalIndex>& labels,
+                              DeviceVector<unsigned>* groupSizes = nullptr)
+    {
+        if (mr_) throw std::runtime_error("Domain friendsOfFriends: not provided on several ranks\n");
+        labels.resize(nParticles());
+        if (groupSizes) groupSizes->resize(nParticles());
+        unsigned numGroups = 0;
+        Context::check(cstone_hip_domain_fof(dom_, x.data(), y.data(), z.data(), linkingLength, labels.data(),
+                                             groupSizes ? groupSizes->data() : nullptr, &numGroups),
+                       "Domain::friendsOfFriends");
+        return numGroups;
     }
     //! R/domain/domain.hpp:411: stores the flag like the reference does (its member convergeTrees, :661, has no reader
     //! there either: the trees converge on the first sync and take one update step per sync afterwards)

@@ -97,8 +97,9 @@ extern "C"
 #define CSTONE_STAGE_MULTIPOLES 15    /* cstone_hip_upsweep_multipoles: leaf multipoles + one launch per tree level */
 #define CSTONE_STAGE_GRAVITY 16       /* cstone_hip_compute_gravity: the Barnes-Hut group walk */
 #define CSTONE_STAGE_ADAPT_H 17       /* cstone_hip_adapt_smoothing_lengths: the in-kernel iteration of h, one launch */
-#define CSTONE_NUM_STAGES 18
-    /* on: 0 off, 1 every stage, 2 only ENCODE, SORT_PASS(_IOTA), RESORT_LEAVES, GATHER(_H), HALOS, NEIGHBORS, ADAPT_H (the kernels that
+#define CSTONE_STAGE_FOF 18           /* cstone_hip_friends_of_friends: the link pass (the walk with the unions), one launch */
+#define CSTONE_NUM_STAGES 19
+    /* on: 0 off, 1 every stage, 2 only ENCODE, SORT_PASS(_IOTA), RESORT_LEAVES, GATHER(_H), HALOS, NEIGHBORS, ADAPT_H, FOF (the kernels that
      * move the particle arrays: eight brackets per sync instead of forty) */
     int cstone_hip_profile_enable(cstone_hip_ctx* ctx, int on);
     /* on != 0: every stage of every call is also wrapped in a roctx range "cstone:<stage>" (roctxRangePushA / Pop of
@@ -1118,6 +1119,60 @@ extern "C"
     int cstone_hip_domain_mr_adapt_h(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z, void* h,
                                      uint32_t ng0, uint32_t tol, uint32_t max_iter, float grow_limit, uint32_t* counts,
                                      uint32_t* status);
+
+    /* ---------------------------------------------------------------------------------------------
+     * Friends-of-friends groups (csrc/fof.hip): two particles closer than a linking length b are friends, the groups are
+     * the connected components of that relation -- the halo / clump finder a clustering client runs after gravity.  The
+     * reference has no such call; the rule below is this library's, stated so that a restatement reproduces it bit for bit.
+     *
+     *     T = coordinate type, hi = T(0.5) * T(linking_length).  Particles i != j of [first, last) are LINKED iff
+     *     cstone_hip_find_neighbors at ext = 1 reports j as a neighbour of i when h[i] = hi:
+     *         d2 = dx*dx + dy*dy + dz*dz      -- left fold, products not fused, dx = x_j - x_i after the walk's periodic fold
+     *         linked iff d2 < T(4) * hi * hi  -- strict
+     *     A particle outside [first, last) (a halo, say) links nothing and bridges nothing.
+     *
+     * The relation is symmetric while b is below half of every periodic box edge (a target whose sphere lies inside the box
+     * skips the fold, and for such a pair the fold is the identity), so  linking_length >= 0.5 * (lim[2d+1] - lim[2d])  on a
+     * periodic axis d is CSTONE_E_ARG, as are linking_length <= 0 and a NaN.  The kernel then unites a pair once, from the
+     * lane of the larger index.
+     *
+     * labels[i - first]      the LOWEST particle index (absolute, in [first, last)) among the members of i's group; a particle
+     *                        without a friend labels itself.  The array doubles as the parent array of a lock-free
+     *                        union-find (csrc/union_find.hpp: the larger root is hooked under the smaller by one
+     *                        compare-and-swap, so every root is the minimum of its component); no per-particle workspace.
+     *                        The value is canonical: the same input gives the same bits in every run, on every stream, in
+     *                        whatever order the atomics land.
+     * group_sizes[i - first] (nullable) the number of members of i's group; every member gets it (integer atomics on n words
+     *                        of the context's workspace).
+     * *num_groups            (host, nullable) the number of k with labels[k] == first + k.  Asking for it is the only
+     *                        synchronisation of the stream; without it the call is asynchronous.
+     *
+     * Argument conventions and refusals of cstone_hip_find_neighbors: CSTONE_E_ARG with nothing written for a null pointer
+     * (the two nullable outputs excepted), last < first, real_bits not 32 or 64, a linking length as above.  last == first:
+     * CSTONE_OK, nothing written.  A traversal stack overflow ORs 4 into the sticky error word; a union that gives up at its
+     * retry cap (it cannot, unless memory breaks the forest's invariant) ORs 16: cstone_hip_ctx_sync then fails.
+     *
+     * fof_catalog : the groups with at least min_members members (0 is taken as 1), ordered by ascending label, from the
+     *               labels of a friends_of_friends call on [first, last): members[group_offsets[g] .. group_offsets[g + 1])
+     *               are the particle indices of group g in ascending order.  group_offsets: *num_groups + 1 <= capacity
+     *               entries; members: room for last - first entries.  CSTONE_E_CAPACITY with *num_groups set and nothing
+     *               written when capacity is too small (the contract of compute_group_splits).  A stable sort of (label,
+     *               index), head flags, two scans, a compaction; last - first < 2^30; synchronises the stream.
+     * domain_fof  : friends_of_friends for the particles [start_index, end_index) of the last sync on the view's octree;
+     *               x, y, z laid out like the sync's results, labels / group_sizes indexed from start_index, labels hold
+     *               indices into the synced arrays.  One rank only: joining groups across ranks is not provided.
+     * ------------------------------------------------------------------------------------------- */
+    int cstone_hip_friends_of_friends(cstone_hip_ctx* ctx, int real_bits, const void* x, const void* y, const void* z,
+                                      uint32_t first, uint32_t last, const cstone_box* box_host,
+                                      const int32_t* child_offsets, const int32_t* internal_to_leaf,
+                                      const uint32_t* layout, const void* centers, const void* sizes,
+                                      double linking_length, uint32_t* labels, uint32_t* group_sizes,
+                                      uint32_t* num_groups);
+    int cstone_hip_fof_catalog(cstone_hip_ctx* ctx, const uint32_t* labels, uint32_t first, uint32_t last,
+                               uint32_t min_members, uint32_t* group_offsets, size_t capacity, uint32_t* members,
+                               uint32_t* num_groups);
+    int cstone_hip_domain_fof(cstone_hip_domain* dom, const void* x, const void* y, const void* z, double linking_length,
+                              uint32_t* labels, uint32_t* group_sizes, uint32_t* num_groups);
 
 #ifdef __cplusplus
 }

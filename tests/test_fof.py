@@ -1,0 +1,419 @@
+"""Friends-of-friends groups (csrc/fof.hip: cstone_hip_friends_of_friends, cstone_hip_fof_catalog, cstone_hip_domain_fof):
+particles closer than a linking length b are friends, groups are the connected components, the label of a particle is the
+lowest index of its group.
+
+The reference is the brute force of tests/fof_support.py: all pairs in the coordinate type with the d2 expression and the
+fold of tests/neighbors_support.py at h = T(0.5) * T(b), then a plain sequential union-find.  The CPU tests establish that
+it may serve -- the link matrix is symmetric, and the labels built from the oracle's WALK at that h (the walk the kernel
+makes) are the same -- and that every shape has the property it is here for.  The GPU tests compare labels, sizes, the
+number of groups and the catalogue with ==, on outputs pre-filled with a sentinel; the sticky error word must be 0 (a
+union that gave up at its retry cap sets it).  The union-find itself (csrc/union_find.hpp) runs under threads and
+sanitizers in a stand-alone host program, tests/union_find_check.cpp."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import fof_support as fs
+from fof_support import SENT
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RBS = [32, 64]
+NEW_SYMBOLS = ("cstone_hip_friends_of_friends", "cstone_hip_fof_catalog", "cstone_hip_domain_fof")
+E_ARG, E_CAPACITY = -1, -2
+
+
+def octants_of(case, idx):
+    """the set of octants (about the centre of the box) that the particles idx lie in"""
+    lim = case.box.lim
+    mid = [(lim[2 * d] + lim[2 * d + 1]) / 2 for d in range(3)]
+    return set((4 * (case.x[idx] > mid[0]) + 2 * (case.y[idx] > mid[1]) + (case.z[idx] > mid[2])).tolist())
+
+
+def check_premise(oracle, name, rb):
+    """what makes the shape exercise the code it is here for, from the brute force"""
+    s, r = fs.shape(oracle, name, rb), fs.reference(oracle, name, rb)
+    case, kind = s.case, name.split("-")[0]
+    sizes_by_group = np.bincount(r.labels - s.first)
+    if name == "n1":
+        assert case.n == 1 and r.labels.tolist() == [0]
+    elif name == "n2-exact":
+        assert case.n == 2 and sorted(case.x.tolist()) == [0.0, 0.25] and s.b == 0.25 and r.labels.tolist() == [0, 1]
+    elif name == "n2-inside":
+        assert case.n == 2 and 0.2499 < case.x.max() < 0.25 and r.labels.tolist() == [0, 0]
+    elif name == "oneleaf65":
+        assert case.o["num_nodes"] == 1 and case.n == 65 and 1 < r.num_groups < 65
+    elif name == "chain":
+        assert r.num_groups == 2 and sorted(sizes_by_group[sizes_by_group > 0].tolist()) == sorted(
+            [fs.CHAIN_GAP, fs.N_CHAIN - fs.CHAIN_GAP])
+        assert case.o["num_nodes"] > 100
+    elif name == "uniform-0.9":
+        assert (r.sizes == 1).any() and r.sizes.max() > 64
+    elif name == "uniform-0.5":
+        assert (r.sizes == 1).sum() > case.n // 2
+    elif name == "uniform-1.3":
+        assert r.sizes.max() > case.n // 2  # one percolating group
+    elif name == "blobs":
+        assert (sizes_by_group >= 20).sum() == 8
+    elif kind == "corner":
+        big = np.flatnonzero(r.labels == r.labels[np.argmax(r.sizes)]) + s.first
+        if name == "corner-100":  # open in y and z: the blob around the corner falls apart there
+            assert all(len(octants_of(case, np.flatnonzero(r.labels == lab) + s.first)) <= 2
+                       for lab in np.unique(r.labels[r.sizes >= 20]))
+            assert (sizes_by_group >= 20).sum() >= 4 and len(octants_of(case, big)) == 2
+        else:
+            assert len(octants_of(case, big)) == 8
+            if name == "corner-aniso":
+                assert len(set(np.diff(case.box.lim)[0::2].tolist())) == 3
+    elif name == "clump300":
+        assert case.leaf_counts.max() > 128 and r.sizes.max() >= 300
+    elif kind == "range":
+        pb, ia, ib = s.info["bridge"], s.info["clump_a"], s.info["clump_b"]
+        assert case.n == 600 and s.first % 64 != 0 and s.last % 64 != 0 and s.last - s.first > 256
+        assert pb < ia.min() and pb < ib.min() and max(ia.max(), ib.max()) < s.last
+        la, lb = set(r.labels[ia - s.first].tolist()), set(r.labels[ib - s.first].tolist())
+        assert len(la) == 1 and len(lb) == 1
+        if name == "range-out":  # the bridge is no target: it links nothing
+            assert s.first == pb + 1 and la != lb
+            assert case.pair_table()[pb, ia].all() and case.pair_table()[pb, ib].all()
+        else:
+            assert s.first == pb and la == lb == {pb}
+    elif name == "dense":
+        assert r.link.sum(1).max() > 100
+    elif name == "nolink":
+        assert s.b < s.info["dmin"] and r.num_groups == case.n and not r.link.any()
+
+
+# ---- CPU -------------------------------------------------------------------------------------------------------------
+
+def test_header_declares_and_the_bindings_export_the_three_calls():
+    import cstone_amd
+
+    text = open(os.path.join(ROOT, "include", "cstone_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    declared = set(re.findall(r"\b(cstone_hip_\w+)\s*\(", text))
+    lib = cstone_amd.load_library()
+    for name in NEW_SYMBOLS:
+        assert name in declared and name in cstone_amd.EXPORTS and hasattr(lib, name), name
+    assert cstone_amd.STAGES["fof"] == int(re.search(r"#define CSTONE_STAGE_FOF (\d+)", text).group(1)) == 18
+    assert int(re.search(r"#define CSTONE_NUM_STAGES (\d+)", text).group(1)) == 19 == len(cstone_amd.STAGES)
+
+
+@pytest.mark.parametrize("rb", RBS)
+@pytest.mark.parametrize("name", fs.NAMES)
+def test_brute_force_is_symmetric_and_equals_the_oracles_walk(oracle, name, rb):
+    """the link matrix is symmetric; labels from the oracle's walk lists at h = b / 2 equal the brute-force labels; the
+    shape's premise holds"""
+    s, r = fs.shape(oracle, name, rb), fs.reference(oracle, name, rb)
+    case = s.case
+    assert np.array_equal(r.link, r.link.T)
+    for d in range(3):  # the linking length is admissible
+        assert case.box.bc[d] != 1 or s.b < 0.5 * (case.box.lim[2 * d + 1] - case.box.lim[2 * d])
+    ngmax = int(case.pair_table()[s.first:s.last].sum(1).max()) + 1
+    lists, counts = case.find(oracle, s.first, s.last, ngmax)
+    assert counts.max(initial=0) < ngmax
+    edges = [(s.first + t, int(j)) for t in range(s.last - s.first) for j in lists[t, :counts[t]]
+             if s.first <= j < s.last]
+    assert np.array_equal(fs.min_labels(s.first, s.last, edges), r.labels)
+    assert (r.labels <= np.arange(s.first, s.last)).all() and (r.labels[r.labels - s.first] == r.labels).all()
+    check_premise(oracle, name, rb)
+
+
+def _build_check(tmp_path, flags, name):
+    exe = tmp_path / name
+    p = subprocess.run(["g++", "-std=c++20", "-O1", "-g", "-Wall", "-Wextra", "-pthread", *flags, "-I",
+                        os.path.join(ROOT, "cornerstone-octree_amd", "csrc"),
+                        os.path.join(ROOT, "tests", "union_find_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    return exe, p
+
+
+def _tsan_links(tmp_path):
+    src = tmp_path / "probe.cpp"
+    src.write_text("int main() { return 0; }\n")
+    p = subprocess.run(["g++", "-fsanitize=thread", str(src), "-o", str(tmp_path / "probe")], capture_output=True)
+    return p.returncode == 0 and subprocess.run([str(tmp_path / "probe")], capture_output=True).returncode == 0
+
+
+@pytest.mark.parametrize("build", ["plain", "asan_ubsan", "tsan"])
+def test_union_find_on_host_threads(tmp_path, build):
+    """csrc/union_find.hpp with std::atomic: 8 threads unite the edges of a path, a star, two cliques with and without a
+    bridge and random graphs in shuffled order; every vertex ends at the minimum of its component, no union gives up, and
+    a compare-and-swap that always fails ends at the retry cap and is reported"""
+    flags = {"plain": [], "asan_ubsan": ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"],
+             "tsan": ["-fsanitize=thread"]}[build]
+    if build == "tsan" and not _tsan_links(tmp_path):
+        pytest.skip("the toolchain here does not link or start a -fsanitize=thread program")
+    exe, p = _build_check(tmp_path, flags, "union_find_check_" + build)
+    assert p.returncode == 0, p.stderr[-3000:]
+    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
+    out = p.stdout + p.stderr
+    assert p.returncode == 0 and re.search(r"UNION_FIND OK: 48 graphs, 8 threads, retry cap checked", out), out[-3000:]
+    for needle in ("ERROR: AddressSanitizer", "runtime error", "WARNING: ThreadSanitizer", "UNION_FIND FAIL"):
+        assert needle not in out, out[-3000:]
+
+
+def _compile_example(exe):
+    libdir = os.path.join(ROOT, "cornerstone-octree_amd", "lib")
+    subprocess.run(["g++", "-std=c++20", "-O1", "-Wall", "-Wno-comment", "-I", os.path.join(ROOT, "include"), "-I",
+                    os.path.join(ROOT, "cornerstone-octree_amd", "include"),
+                    os.path.join(ROOT, "examples", "fof_example.cpp"), "-L", libdir, "-lcstone_hip",
+                    f"-Wl,-rpath,{libdir}", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib", "-o", str(exe)], check=True)
+
+
+def test_cpp_example_compiles_with_a_host_compiler(tmp_path):
+    """examples/fof_example.cpp (friendsOfFriendsGpu, fofCatalogGpu, Domain::friendsOfFriends) against the C++ host layer"""
+    _compile_example(tmp_path / "fof_example")
+
+
+# ---- GPU -------------------------------------------------------------------------------------------------------------
+
+def _dev(a):
+    import torch
+
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.uint32:
+        a = a.view(np.int32)
+    return torch.from_numpy(a.copy()).cuda()
+
+
+def _u32(t):
+    return t.cpu().numpy().view(np.uint32)
+
+
+class DevCase:
+    """the arrays of a case on the device"""
+
+    PAD = 70  # rows of labels and sizes behind the last target, to see that they stay untouched
+
+    def __init__(self, hip, case):
+        import cstone_amd
+
+        self.hip, self.case = hip, case
+        self.x, self.y, self.z = (_dev(a) for a in (case.x, case.y, case.z))
+        self.co, self.i2l = _dev(case.o["child_offsets"]), _dev(case.o["internal_to_leaf"])
+        self.layout, self.cen, self.siz = _dev(case.layout), _dev(case.cen), _dev(case.siz)
+        self.cbox = cstone_amd.make_cbox(case.box.lim, case.box.bc)
+
+    def call(self, first, last, b, null=(), real_bits=None, expect=0, sizes=True, count=True):
+        """one cstone_hip_friends_of_friends on outputs pre-filled with the sentinel: (labels, sizes, num_groups) with PAD
+        more rows than targets; num_groups starts as the sentinel too"""
+        import torch
+
+        hip, P = self.hip, lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        rows = max(last - first, 0) + self.PAD
+        lab = torch.full((rows,), -1, dtype=torch.int32, device="cuda")
+        gs = torch.full((rows,), -1, dtype=torch.int32, device="cuda")
+        ng = C.c_uint32(int(SENT))
+        args = dict(ctx=hip.h, real_bits=C.c_int(self.case.rb if real_bits is None else real_bits), x=P(self.x),
+                    y=P(self.y), z=P(self.z), first=C.c_uint32(first), last=C.c_uint32(last), box=C.byref(self.cbox),
+                    co=P(self.co), i2l=P(self.i2l), layout=P(self.layout), cen=P(self.cen), siz=P(self.siz),
+                    b=C.c_double(b), labels=P(lab), sizes=P(gs) if sizes else None, ng=C.byref(ng) if count else None)
+        for k in null:
+            args[k] = None
+        rc = hip.lib.cstone_hip_friends_of_friends(*args.values())
+        assert rc == expect, (rc, hip.lib.cstone_hip_last_error(hip.h))
+        hip.sync()  # raises if the sticky device-side error word is set (stack overflow: 4, a union that gave up: 16)
+        return _u32(lab), _u32(gs), ng.value
+
+    def catalog(self, labels, first, last, min_members, capacity=None, expect=0):
+        """one cstone_hip_fof_catalog on sentinel-filled outputs: (offsets [capacity + PAD], members [rows + PAD], num)"""
+        import torch
+
+        hip, P = self.hip, lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        nt = last - first
+        cap = nt + 1 if capacity is None else capacity
+        off = torch.full((cap + self.PAD,), -1, dtype=torch.int32, device="cuda")
+        mem = torch.full((nt + self.PAD,), -1, dtype=torch.int32, device="cuda")
+        ng = C.c_uint32(int(SENT))
+        rc = hip.lib.cstone_hip_fof_catalog(hip.h, P(_dev(labels)), C.c_uint32(first), C.c_uint32(last),
+                                            C.c_uint32(min_members), P(off), C.c_size_t(cap), P(mem), C.byref(ng))
+        assert rc == expect, (rc, hip.lib.cstone_hip_last_error(hip.h))
+        hip.sync()
+        return _u32(off), _u32(mem), ng.value
+
+
+class _Raw:
+    """a device pointer of a domain view where the bindings expect a tensor"""
+
+    def __init__(self, ptr):
+        self.ptr = ptr
+
+    def data_ptr(self):
+        return self.ptr
+
+
+def assert_equals_reference(got, s, r, what):
+    lab, gs, ng = got
+    nt = s.last - s.first
+    bad = np.flatnonzero(lab[:nt] != r.labels)
+    assert bad.size == 0, (what, "labels", bad.size, bad[:8].tolist(), lab[bad[:8]].tolist(), r.labels[bad[:8]].tolist())
+    bad = np.flatnonzero(gs[:nt] != r.sizes)
+    assert bad.size == 0, (what, "sizes", bad.size, bad[:8].tolist(), gs[bad[:8]].tolist(), r.sizes[bad[:8]].tolist())
+    assert ng == r.num_groups, (what, "number of groups", ng, r.num_groups)
+    assert (lab[nt:] == SENT).all() and (gs[nt:] == SENT).all(), (what, "written behind the last target")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rb", RBS)
+@pytest.mark.parametrize("name", fs.NAMES)
+def test_hip_equals_the_brute_force(hip, oracle, name, rb):
+    """labels, sizes and the number of groups with ==; the rows behind the last target keep the sentinel; the sticky error
+    word is 0.  Without the two nullable outputs the labels are the same"""
+    check_premise(oracle, name, rb)
+    s, r = fs.shape(oracle, name, rb), fs.reference(oracle, name, rb)
+    d = DevCase(hip, s.case)
+    got = d.call(s.first, s.last, s.b)
+    print(f"{name} f{rb}: n {s.last - s.first}, groups {got[2]}, largest {int(got[1][:s.last - s.first].max())}")
+    assert_equals_reference(got, s, r, name)
+    lab, gs, ng = d.call(s.first, s.last, s.b, sizes=False, count=False)
+    assert np.array_equal(lab, got[0]) and (gs == SENT).all() and ng == int(SENT)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rb", RBS)
+def test_hip_refuses_bad_arguments(hip, oracle, rb):
+    """every refusal is CSTONE_E_ARG with labels, sizes and the number of groups untouched; an empty range is accepted and
+    writes nothing"""
+    s = fs.shape(oracle, "uniform-0.9", rb)  # periodic unit box
+    d = DevCase(hip, s.case)
+    refusals = [dict(null=[k]) for k in ("ctx", "x", "y", "z", "box", "co", "i2l", "layout", "cen", "siz", "labels")]
+    refusals += [dict(b=0.0), dict(b=-0.05), dict(b=float("nan")), dict(b=0.5), dict(b=0.75), dict(real_bits=16),
+                 dict(first=s.last, last=s.first)]
+    for kw in refusals:
+        kw = dict(dict(first=s.first, last=s.last, b=s.b), **kw)
+        lab, gs, ng = d.call(kw.pop("first"), kw.pop("last"), kw.pop("b"), expect=E_ARG, **kw)
+        assert (lab == SENT).all() and (gs == SENT).all() and ng == int(SENT), kw
+    lab, gs, ng = d.call(100, 100, s.b)
+    assert (lab == SENT).all() and (gs == SENT).all() and ng == int(SENT)
+    # half an edge is refused on periodic axes only: the anisotropic box is open in no direction, its y edge is 0.7
+    a = fs.shape(oracle, "corner-aniso", rb)
+    lab, _, _ = DevCase(hip, a.case).call(0, a.case.n, 0.35, expect=E_ARG)
+    assert (lab == SENT).all()
+    o = fs.shape(oracle, "dense", rb)  # open: any positive length is taken
+    lab, _, ng = DevCase(hip, o.case).call(0, o.case.n, 2.0)
+    assert (lab[:o.case.n] == 0).all() and ng == 1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rb", RBS)
+@pytest.mark.parametrize("name", ["uniform-0.9", "chain"])
+def test_hip_is_repeatable(hip, oracle, name, rb):
+    """two calls on one context give identical arrays, and so does a third after an unrelated scan and sort on the same
+    context (they use the same workspace)"""
+    import torch
+
+    s = fs.shape(oracle, name, rb)
+    d = DevCase(hip, s.case)
+    a, b = d.call(s.first, s.last, s.b), d.call(s.first, s.last, s.b)
+    v = torch.arange(5000, dtype=torch.int32, device="cuda")
+    hip.exclusive_scan(v, torch.empty_like(v))
+    hip.sort_pairs(torch.flip(v, [0]).contiguous(), v.clone())
+    c = d.call(s.first, s.last, s.b)
+    for other in (b, c):
+        assert np.array_equal(a[0], other[0]) and np.array_equal(a[1], other[1]) and a[2] == other[2]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rb", RBS)
+@pytest.mark.parametrize("name", ["uniform-0.9", "blobs", "range-in"])
+def test_hip_catalog_equals_numpy(hip, oracle, name, rb):
+    """min_members in {0, 1, 2, largest, largest + 1}: offsets and members ==, nothing written behind them; a capacity one
+    short is CSTONE_E_CAPACITY with the number of groups set and nothing written"""
+    s, r = fs.shape(oracle, name, rb), fs.reference(oracle, name, rb)
+    d = DevCase(hip, s.case)
+    nt, largest = s.last - s.first, int(r.sizes.max())
+    for mm in (0, 1, 2, largest, largest + 1):
+        ref_off, ref_mem = fs.catalog_of(r.labels, s.first, mm)
+        ngroups = ref_off.size - 1
+        assert (mm == largest + 1) == (ngroups == 0)
+        off, mem, ng = d.catalog(r.labels, s.first, s.last, mm)
+        assert ng == ngroups, (mm, ng, ngroups)
+        assert np.array_equal(off[:ng + 1], ref_off) and (off[ng + 1:] == SENT).all(), mm
+        assert np.array_equal(mem[:ref_mem.size], ref_mem) and (mem[ref_mem.size:] == SENT).all(), mm
+        if mm <= 1:
+            assert ng == r.num_groups and ref_mem.size == nt
+        off, mem, ng = d.catalog(r.labels, s.first, s.last, mm, capacity=ngroups, expect=E_CAPACITY)
+        assert ng == ngroups and (off == SENT).all() and (mem == SENT).all(), mm
+        off, mem, ng = d.catalog(r.labels, s.first, s.last, mm, capacity=ngroups + 1)
+        assert ng == ngroups and np.array_equal(off[:ng + 1], ref_off) and (off[ng + 1:] == SENT).all(), mm
+    # the Python classes on the same labels
+    offsets, members = hip.fof_catalog(_dev(r.labels), s.first, s.last, 2)
+    ref_off, ref_mem = fs.catalog_of(r.labels, s.first, 2)
+    assert np.array_equal(_u32(offsets), ref_off) and np.array_equal(_u32(members), ref_mem)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rb", RBS)
+def test_hip_catalog_refuses_bad_arguments(hip, oracle, rb):
+    import torch
+
+    lab = torch.zeros(10, dtype=torch.int32, device="cuda")
+    P, ng = (lambda t: C.c_void_p(t.data_ptr())), C.c_uint32(7)
+    for args in ((None, 0, 10, 1, P(lab), 11, P(lab), C.byref(ng)), (P(lab), 0, 10, 1, None, 11, P(lab), C.byref(ng)),
+                 (P(lab), 0, 10, 1, P(lab), 11, None, C.byref(ng)), (P(lab), 0, 10, 1, P(lab), 11, P(lab), None),
+                 (P(lab), 10, 0, 1, P(lab), 11, P(lab), C.byref(ng))):
+        a = list(args)
+        rc = hip.lib.cstone_hip_fof_catalog(hip.h, a[0], C.c_uint32(a[1]), C.c_uint32(a[2]), C.c_uint32(a[3]), a[4],
+                                            C.c_size_t(a[5]), a[6], a[7])
+        assert rc == E_ARG and ng.value == 7
+    off = torch.full((4,), -1, dtype=torch.int32, device="cuda")
+    rc = hip.lib.cstone_hip_fof_catalog(hip.h, P(lab), C.c_uint32(5), C.c_uint32(5), C.c_uint32(1), P(off), C.c_size_t(4),
+                                        P(lab), C.byref(ng))
+    hip.sync()
+    assert rc == 0 and ng.value == 0 and _u32(off).tolist() == [0] + [int(SENT)] * 3
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kb", [32, 64])
+@pytest.mark.parametrize("rb", RBS)
+def test_hip_domain_fof_equals_the_brute_force_on_the_synced_arrays(hip, oracle, rb, kb):
+    """Domain.sync of the blob cloud, then Domain.fof == the brute force on the arrays as the sync left them, and ==
+    Context.friends_of_friends on the view; before the first sync the call is refused"""
+    import torch
+
+    import cstone_amd
+    from cstone_amd.domain import Domain
+    from helpers import Box
+
+    s = fs.shape(oracle, "blobs", rb)
+    case, n = s.case, s.case.n
+    tdt = torch.float32 if rb == 32 else torch.float64
+    perm = np.random.default_rng(5).permutation(n)
+    x, y, z = [torch.from_numpy(a[perm].copy()).cuda() for a in (case.x, case.y, case.z)]
+    h = torch.full((n,), 0.01, dtype=tdt, device="cuda")
+    dom = Domain(hip, cstone_amd.HILBERT, kb, rb, 64, 16, 0.5, cstone_amd.make_cbox(case.box.lim, case.box.bc))
+    with pytest.raises(cstone_amd.CstoneError):
+        dom.fof(x, y, z, s.b)
+    keys = torch.zeros(n, dtype=torch.int32 if kb == 32 else torch.int64, device="cuda")
+    scratch = [torch.empty(n, dtype=tdt, device="cuda") for _ in range(3)]
+    keys, x, y, z, h, _, _ = dom.sync(keys, x, y, z, h, scratch)
+    hip.sync()
+    v = dom.view()
+    assert (v.start_index, v.end_index) == (0, n)
+    labels, sizes, ng = dom.fof(x, y, z, s.b)
+    hip.sync()
+    synced = fs.stub_case(x.cpu().numpy(), y.cpu().numpy(), z.cpu().numpy(), s.b, Box(list(v.box.lim), tuple(v.box.bc)))
+    ref_labels = fs.labels_of(fs.links(synced, 0, n), 0, n)
+    assert np.array_equal(_u32(labels), ref_labels)
+    assert np.array_equal(_u32(sizes), fs.sizes_of(ref_labels, 0)) and ng == int((ref_labels == np.arange(n)).sum())
+    assert (np.bincount(ref_labels) >= 20).sum() == 8
+    tree = dict(child_offsets=_Raw(v.child_offsets), internal_to_leaf=_Raw(v.internal_to_leaf))
+    l2, s2, n2 = hip.friends_of_friends(x, y, z, 0, n, v.box, tree, _Raw(v.layout), _Raw(v.centers), _Raw(v.sizes), s.b)
+    hip.sync()
+    assert torch.equal(labels, l2) and torch.equal(sizes, s2) and ng == n2
+
+
+@pytest.mark.gpu
+def test_hip_cpp_example_runs(tmp_path):
+    """sync, Domain::friendsOfFriends, fofCatalogGpu, the host check of mutual reachability: exit status 0"""
+    exe = tmp_path / "fof_example"
+    _compile_example(exe)
+    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    print(p.stdout)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    m = re.search(r"groups (\d+), groups with at least 20 members (\d+)", p.stdout)
+    assert m and int(m.group(2)) >= 6 and int(m.group(1)) > int(m.group(2))
+    assert "not mutually reachable: 0" in p.stdout and "identical" in p.stdout
