@@ -1301,6 +1301,56 @@ int cstone_hip_sfc_keys_and_ordering(cstone_hip_ctx* ctx, int curve, int key_bit
     return run(fused ? 2 : 0);
 }
 
+static_assert(RUN_LIMIT == CSTONE_PARTIAL_SORT_RUN_LIMIT, "the header publishes the limit of fixupRunsKernel");
+
+int cstone_hip_sfc_keys_and_ordering_partial(cstone_hip_ctx* ctx, int curve, int key_bits, int real_bits, const void* x,
+                                             const void* y, const void* z, void* keys, uint32_t* ordering, size_t n,
+                                             const cstone_box* box_host, void* keys_alt, uint32_t* values_alt,
+                                             void* temp, size_t temp_bytes, int start_pass, int honour_markers,
+                                             int finish, cstone_hip_partial_sort_result* result_host)
+{
+    if (result_host) *result_host = cstone_hip_partial_sort_result{};
+    if (!ctx || !box_host || (key_bits != 32 && key_bits != 64) || (real_bits != 32 && real_bits != 64) ||
+        (curve != CSTONE_MORTON && curve != CSTONE_HILBERT))
+        return fail(ctx, CSTONE_E_ARG, "sfc_keys_and_ordering_partial: bad argument");
+    if (start_pass < 0 || start_pass % 2 != 0 || start_pass >= key_bits / 8)
+        return fail(ctx, CSTONE_E_ARG, "sfc_keys_and_ordering_partial: start_pass %d is not an even number in [0, %d)",
+                    start_pass, key_bits / 8);
+    if (n == 0) return CSTONE_OK;
+    if (!x || !y || !z || !keys || !ordering || !keys_alt || !values_alt || !temp)
+        return fail(ctx, CSTONE_E_ARG, "sfc_keys_and_ordering_partial: null array");
+    // the slots Domain::sync uses for the same purpose: the flag of the fix-up and the extents in the type of x, y, z
+    int* tooLongDev = ctx->devScalars + 3;
+    void* extDev    = ctx->devScalars + 16;
+    bool measured   = false;
+    CS_TRY(sfcKeysAndOrderingHint(ctx, curve, key_bits, real_bits, x, y, z, keys, ordering, n, *box_host, keys_alt,
+                                  values_alt, temp, temp_bytes, start_pass, tooLongDev, honour_markers != 0, extDev,
+                                  &measured));
+    if (start_pass == 0) CS_HIP(ctx, hipMemsetAsync(tooLongDev, 0, sizeof(int), ctx->stream)); // no fix-up ran
+    CS_TRY(copyToPinned(ctx, ctx->hostScalars + 3, tooLongDev, sizeof(int)));
+    if (measured) CS_TRY(copyToPinned(ctx, ctx->hostScalars + 16, extDev, 6 * (real_bits / 8)));
+    CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const bool tooLong = ctx->hostScalars[3] != 0;
+    if (result_host)
+    {
+        result_host->run_too_long     = tooLong;
+        result_host->finished         = tooLong && finish != 0;
+        result_host->extents_measured = measured;
+        for (int k = 0; k < 6 && measured; ++k)
+            result_host->extents[k] = real_bits == 32 ? double(reinterpret_cast<const float*>(ctx->hostScalars + 16)[k])
+                                                      : reinterpret_cast<const double*>(ctx->hostScalars + 16)[k];
+    }
+    if (tooLong && finish != 0)
+    {
+        // as Domain::sync completes it: the regular sort of (keys, ordering) over all digits
+        return key_bits == 32 ? sortPairs<uint32_t>(ctx, (uint32_t*)keys, ordering, n, (uint32_t*)keys_alt, values_alt,
+                                                    temp, temp_bytes)
+                              : sortPairs<uint64_t>(ctx, (uint64_t*)keys, ordering, n, (uint64_t*)keys_alt, values_alt,
+                                                    temp, temp_bytes);
+    }
+    return CSTONE_OK;
+}
+
 int cstone_hip_sequence_u32(cstone_hip_ctx* ctx, uint32_t* out, size_t n, uint32_t init)
 {
     if (!ctx || (n && !out)) return fail(ctx, CSTONE_E_ARG, "sequence_u32: bad argument");

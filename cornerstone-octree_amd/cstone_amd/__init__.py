@@ -28,7 +28,7 @@ EXPORTS = [
     "cstone_hip_device_info", "cstone_hip_malloc", "cstone_hip_free", "cstone_hip_memcpy_h2d",
     "cstone_hip_memcpy_d2h", "cstone_hip_memcpy_d2d", "cstone_hip_memset", "cstone_hip_profile_enable", "cstone_hip_profile_markers", "cstone_hip_domain_mr_sync_grav", "cstone_hip_domain_mr_update_expansion_centers", "cstone_hip_add_macs", "cstone_hip_halo_request_rows", "cstone_hip_peer_range_counts", "cstone_hip_adjacent_difference_u32", "cstone_hip_offsets_from_counts_u32", "cstone_hip_domain_sync_grav", "cstone_hip_domain_update_expansion_centers", "cstone_hip_gather_tables_u32",
     "cstone_hip_profile_reset", "cstone_hip_profile_get", "cstone_hip_profile_get_spread", "cstone_hip_compute_sfc_keys",
-    "cstone_hip_sort_pairs_temp_bytes", "cstone_hip_sort_pairs", "cstone_hip_sort_keys_ordering", "cstone_hip_sfc_keys_and_ordering", "cstone_hip_sequence_u32", "cstone_hip_gather",
+    "cstone_hip_sort_pairs_temp_bytes", "cstone_hip_sort_pairs", "cstone_hip_sort_keys_ordering", "cstone_hip_sfc_keys_and_ordering", "cstone_hip_sfc_keys_and_ordering_partial", "cstone_hip_sequence_u32", "cstone_hip_gather",
     "cstone_hip_scatter", "cstone_hip_gather_scatter", "cstone_hip_merge_positions", "cstone_hip_minmax", "cstone_hip_minmax_arrays", "cstone_hip_exclusive_scan_u32", "cstone_hip_inclusive_scan_u32", "cstone_hip_lower_bound",
     "cstone_hip_compute_node_counts", "cstone_hip_compute_node_counts_guided", "cstone_hip_compute_node_ops", "cstone_hip_rebalance_tree",
     "cstone_hip_update_octree", "cstone_hip_compute_octree", "cstone_hip_build_octree", "cstone_hip_upsweep_sum",
@@ -91,6 +91,14 @@ def make_cbox(lim, bc=(0, 0, 0)):
     for i in range(3):
         b.bc[i] = int(bc[i])
     return b
+
+
+PARTIAL_SORT_RUN_LIMIT = 192  # CSTONE_PARTIAL_SORT_RUN_LIMIT
+
+
+class PartialSortResult(C.Structure):
+    _fields_ = [("run_too_long", C.c_int32), ("finished", C.c_int32), ("extents_measured", C.c_int32),
+                ("pad_", C.c_int32), ("extents", C.c_double * 6)]
 
 
 class CstoneError(RuntimeError):
@@ -268,6 +276,28 @@ class Context:
                                                             _ptr(ka), _ptr(va), _ptr(tmp), C.c_size_t(tmp.numel())),
                   "sfc_keys_and_ordering")
         return keys, order
+
+    def sfc_keys_and_ordering_partial(self, curve, key_bits, x, y, z, box, start_pass, keys=None, honour_markers=True,
+                                      finish=True, temp=None):
+        """(keys, ordering, info): sfc_keys_and_ordering with the radix passes from digit start_pass upward and the
+        fix-up of the runs of equal high digits; info = dict(run_too_long, finished, extents (6 floats) or None)"""
+        torch = _torch()
+        n = x.numel()
+        if keys is None:
+            keys = torch.zeros(n, dtype=key_torch_dtype(key_bits), device=x.device)
+        order = torch.empty(n, dtype=torch.int32, device=x.device)
+        ka, va = torch.empty_like(keys), torch.empty_like(order)
+        if temp is None:
+            temp = torch.empty(max(1, self.sort_temp_bytes(key_bits, n)), dtype=torch.uint8, device=x.device)
+        res = PartialSortResult()
+        self._chk(self.lib.cstone_hip_sfc_keys_and_ordering_partial(
+            self.h, C.c_int(curve), C.c_int(key_bits), C.c_int(x.element_size() * 8), _ptr(x), _ptr(y), _ptr(z),
+            _ptr(keys), _ptr(order), C.c_size_t(n), C.byref(box), _ptr(ka), _ptr(va), _ptr(temp),
+            C.c_size_t(temp.numel()), C.c_int(start_pass), C.c_int(int(bool(honour_markers))),
+            C.c_int(int(bool(finish))), C.byref(res)), "sfc_keys_and_ordering_partial")
+        info = {"run_too_long": bool(res.run_too_long), "finished": bool(res.finished),
+                "extents": tuple(res.extents) if res.extents_measured else None}
+        return keys, order, info
 
     def sequence(self, out, init=0):
         self._chk(self.lib.cstone_hip_sequence_u32(self.h, _ptr(out), C.c_size_t(out.numel()), C.c_uint32(init)),

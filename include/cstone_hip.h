@@ -129,6 +129,35 @@ extern "C"
                                          const cstone_box* box_host, void* keys_alt, uint32_t* values_alt, void* temp,
                                          size_t temp_bytes);
 
+    /* The same with a hint on the structure of the keys, as Domain::sync calls it: only the digits from bit
+     * 8 * start_pass upward go through the radix passes; a fix-up kernel then orders the low bits inside every run of
+     * equal high bits (keys >> 8 * start_pass) in place, stably.  A client that knows the depth of its tree knows that
+     * such runs lie inside one leaf cell and are short.  A run of more than CSTONE_PARTIAL_SORT_RUN_LIMIT keys is not
+     * fixed up: it raises run_too_long, runs within the limit are finished all the same, longer ones stay in input order.
+     *   start_pass      even, 0 <= start_pass < key_bits / 8 (CSTONE_E_ARG otherwise); 0 sorts all digits
+     *   honour_markers  0: the previous content of keys is not read (no remove markers); otherwise as above
+     *   finish          != 0: after a run that was too long the call completes with the sort over all digits, the result
+     *                   is then that of cstone_hip_sfc_keys_and_ordering; 0 leaves the intermediate state
+     * The call synchronises the stream to fill *result_host (which may be NULL); a finishing sort is queued behind that.
+     * extents = {xmin, xmax, ymin, ymax, zmin, zmax} of all n particles, measured by the fused encode kernel; they are
+     * not measured (extents_measured = 0) when an array does not start on a 16-byte boundary: those take the plain
+     * encode.  n == 0 succeeds with nothing flagged. */
+#define CSTONE_PARTIAL_SORT_RUN_LIMIT 192
+    typedef struct cstone_hip_partial_sort_result
+    {
+        int32_t run_too_long;     /* a run of equal high digits exceeded CSTONE_PARTIAL_SORT_RUN_LIMIT */
+        int32_t finished;         /* the sort over all digits was queued because of that */
+        int32_t extents_measured; /* extents[] is valid */
+        int32_t pad_;
+        double extents[6];
+    } cstone_hip_partial_sort_result;
+    int cstone_hip_sfc_keys_and_ordering_partial(cstone_hip_ctx* ctx, int curve, int key_bits, int real_bits,
+                                                 const void* x, const void* y, const void* z, void* keys,
+                                                 uint32_t* ordering, size_t n, const cstone_box* box_host,
+                                                 void* keys_alt, uint32_t* values_alt, void* temp, size_t temp_bytes,
+                                                 int start_pass, int honour_markers, int finish,
+                                                 cstone_hip_partial_sort_result* result_host);
+
     /* ---------------------------------------------------------------------------------------------
      * sort: replaces sortByKeyGpu / sortByKeyTempStorage (R/primitives/primitives_gpu.h:93-100,
      * R/primitives/primitives_gpu.cu:328-369,383-386) and sequenceGpu (:286).

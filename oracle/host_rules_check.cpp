@@ -223,6 +223,42 @@ void checkResultMargins()
     expect(blockIs(blockWithHalos(0, 1000, 1000, 5, 2), true, 8, 1010, 3), "blockWithHalos: no margins, halos");
 }
 
+// ---- partialSortStartPass: which digit passes Domain::sync leaves to the fix-up of the runs (sort.hip)
+
+//! the rule restated: low bits below the deepest leaf level + margin, in whole digits, rounded down to an even count
+template<class K>
+void checkStartPassProperties()
+{
+    const int top = int(cship::hostMaxLevel<K>());
+    for (uint32_t bucket : {16u, 64u, 128u, 129u, 1024u, 1025u})
+    {
+        const int margin = bucket <= 128 ? 1 : bucket <= 1024 ? 2 : 3;
+        for (int L = 0; L <= top; ++L)
+        {
+            const int p  = cship::partialSortStartPass<K>(L, bucket);
+            auto holds   = [&](int q) { return 8 * q + 3 * (L + margin) <= 3 * top; };
+            auto inRange = [&](int q) { return q >= 0 && q <= int(sizeof(K)) - 2; };
+            expect(p % 2 == 0 && inRange(p), "partialSortStartPass: even and in [0, sizeof(K) - 2]");
+            expect(!holds(0) || holds(p), "partialSortStartPass: skipped digits lie below level L + margin");
+            expect(!holds(0) ? p == 0 : (!inRange(p + 2) || !holds(p + 2)), "partialSortStartPass: no two more digits fit");
+        }
+    }
+}
+
+void checkPartialSortStartPass()
+{
+    using cship::partialSortStartPass;
+    expect(partialSortStartPass<uint64_t>(4, 64) == 6, "partialSortStartPass<uint64_t>(4, 64)");
+    expect(partialSortStartPass<uint64_t>(9, 64) == 4, "partialSortStartPass<uint64_t>(9, 64)");
+    expect(partialSortStartPass<uint64_t>(10, 64) == 2, "partialSortStartPass<uint64_t>(10, 64)");
+    expect(partialSortStartPass<uint64_t>(15, 64) == 0, "partialSortStartPass<uint64_t>(15, 64)");
+    expect(partialSortStartPass<uint64_t>(9, 200) == 2, "partialSortStartPass<uint64_t>(9, 200)");
+    expect(partialSortStartPass<uint64_t>(21, 64) == 0, "partialSortStartPass<uint64_t>(21, 64)");
+    expect(partialSortStartPass<uint32_t>(3, 64) == 2, "partialSortStartPass<uint32_t>(3, 64)");
+    expect(partialSortStartPass<uint32_t>(4, 64) == 0, "partialSortStartPass<uint32_t>(4, 64)");
+    expect(partialSortStartPass<uint32_t>(2, 200) == 2, "partialSortStartPass<uint32_t>(2, 200)");
+}
+
 } // namespace
 
 int main()
@@ -230,6 +266,12 @@ int main()
     checkExchangePlan();
     checkResultMargins();
     std::printf("HOST_RULES exchangePlan and resultMargins: %d known answers\n", cases);
+    cases = 0;
+    checkPartialSortStartPass();
+    const int hand = cases;
+    checkStartPassProperties<uint32_t>();
+    checkStartPassProperties<uint64_t>();
+    std::printf("HOST_RULES partialSortStartPass: %d hand values, %d property checks\n", hand, cases - hand);
     // more than 64 x 512 keys: the root itself splits by 4096 at either bucket size
     check<uint32_t>(16, 40000, 1);
     check<uint32_t>(64, 40000, 2);

@@ -120,7 +120,9 @@ def test_sync_reports_the_device_side_error_word(hip, monkeypatch):
 def test_partial_sort_fallback_when_particles_collapse(hip, oracle):
     """Domain::sync radix-sorts only the key digits above the previous tree's depth and orders the rest inside runs of
     equal high digits; when the particles suddenly collapse into a tiny region those runs become too long and the
-    regular sort must take over.  Keys, ordering and attached fields must equal the oracle's full stable sort."""
+    regular sort must take over.  Keys, ordering and attached fields must equal the oracle's full stable sort, and the
+    domain's full_sort_fallbacks counter says that it did take over: 0 before the collapse, at least 1 from it on (in the
+    default sort mode: the re-sort gives up on the collapsed particles and hands over to the partial-digit sort)."""
     import torch
 
     import cstone_amd
@@ -152,6 +154,10 @@ def test_partial_sort_fallback_when_particles_collapse(hip, oracle):
         assert np.array_equal(keys.cpu().numpy().view(np.uint64), ks), step
         assert np.array_equal(ident.cpu().numpy(), idin[order]), step   # the same stable permutation
         assert np.array_equal(xd.cpu().numpy(), xin[order]), step
+        # ... and the regular sort did take over: never before the collapse, at least once from the collapse on
+        stats = dom.stats()
+        print(f"step {step}: {stats}")
+        assert stats["full_sort_fallbacks"] == 0 if step < 2 else stats["full_sort_fallbacks"] >= 1, (step, stats)
 
 
 @pytest.mark.gpu

@@ -3,7 +3,8 @@ stand-alone program against the oracle (oracle/host_rules_check.cpp): the update
 steady-state sync makes on the host must decide and rebalance like the oracle's update_octree, step by step from the
 root to convergence and on through a drift, a removal and a collapse, for 32- and 64-bit keys and buckets of 16 and 64,
 and must have taken every decision (merge, keep, split by 8, 64, 512, 4096) on the way; the exchange plan and the
-margins of the result arrays of the multi-rank sync give the answers worked out by hand.  Run as a plain build and as a
+margins of the result arrays of the multi-rank sync give the answers worked out by hand, and so does the start pass of
+the partial-digit sort, which also keeps its defining inequality at every level.  Run as a plain build and as a
 build of its own with -fsanitize=address,undefined."""
 import os
 import re
@@ -35,3 +36,7 @@ def test_global_tree_step_on_the_host_equals_the_oracle(built, exe):
         assert all(int(c) > 0 for c in r[3:]), r
     # exchangePlan and resultMargins / blockWithHalos of the multi-rank sync: every known answer was checked
     assert re.search(r"HOST_RULES exchangePlan and resultMargins: 19 known answers", out), out[-3000:]
+    # partialSortStartPass: the nine values worked out by hand, and three properties (even and in range, the skipped
+    # digits lie below the deepest leaf level + margin, two more would not) for every level of both key types at six
+    # bucket sizes: 6 x (11 + 22) x 3
+    assert re.search(r"HOST_RULES partialSortStartPass: 9 hand values, 594 property checks", out), out[-3000:]
