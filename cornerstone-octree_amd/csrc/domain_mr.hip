@@ -19,6 +19,7 @@
 #include <cstdarg>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <limits>
 #include <map>
 #include <string>
@@ -29,6 +30,7 @@
 #include "ctx.hpp"
 #include "devbuf.hpp"
 #include "device_keys.hpp"
+#include "fof_mr.hpp"
 #include "host_tree.hpp"
 #include "let.hpp"
 #include "resort.hpp"
@@ -365,6 +367,8 @@ struct MrBase
                                int order, double G, double eps2, void* ax, void* ay, void* az, void* phi) = 0;
     virtual int adaptH(const void* x, const void* y, const void* z, void* h, uint32_t ng0, uint32_t tol, uint32_t maxIter,
                        float growLimit, uint32_t* counts, uint32_t* status)                = 0;
+    virtual int friendsOfFriends(const void* x, const void* y, const void* z, double linkingLength, uint32_t maxRounds,
+                                 uint64_t* labels, uint64_t* groupSizes, uint64_t* numGroups, uint32_t* rounds) = 0;
     virtual int multipoles(const void** out, int32_t* numNodes)                           = 0;
     virtual int octupoles(const void** out, int32_t* numNodes)                            = 0;
     virtual int view(cstone_hip_domain_mr_view* out)                                     = 0;
@@ -630,6 +634,138 @@ public:
                                                       growLimit, 0, nullptr, counts, status));
         }
         adapted_ = true;
+        return CSTONE_OK;
+    }
+
+    /*! Friends-of-friends groups over the particles of ALL ranks (cstone_hip_domain_mr_fof, the definitions are in
+     *  include/cstone_hip.h, the method and its proof in DESIGN.md section 5f): global ids as initial labels, the local
+     *  components of everything present on the rank (halos included), then rounds of { lower the labels to the minimum of
+     *  their local component, exchange the halos of the labels, all-reduce "somebody changed an assigned label" } up to the
+     *  first quiet round; the group sizes through one exchange of (label, count) pairs with the owners of the labels.
+     *  Works on buffers of the domain and copies to the caller's arrays at the very end: a refused call writes nothing.
+     *  Whatever is the same on every rank is refused before the first collective; rank-local trouble rides in the status
+     *  word of the all-gather, so that everybody returns from the same point. */
+    int friendsOfFriends(const void* x, const void* y, const void* z, double b, uint32_t maxRounds, uint64_t* labels,
+                         uint64_t* groupSizes, uint64_t* numGroups, uint32_t* rounds) override
+    {
+        if (firstCall_) return fail(ctx_, CSTONE_E_ARG, "domain_mr_fof: no sync yet");
+        if (!(b > 0.0)) return fail(ctx_, CSTONE_E_ARG, "domain_mr_fof: linking length %g is not > 0", b); // (NaN too)
+        for (int d = 0; d < 3; ++d)
+        {
+            const double len = view_.box.lim[2 * d + 1] - view_.box.lim[2 * d];
+            if (view_.box.bc[d] == 1 && !(b < 0.5 * len))
+                return fail(ctx_, CSTONE_E_ARG, "domain_mr_fof: linking length %g is not below half the periodic edge %g", b, len);
+        }
+        if (maxRounds == 0) maxRounds = CSTONE_FOF_MR_DEFAULT_ROUNDS;
+        const uint32_t si = view_.start_index, ei = view_.end_index, nh = view_.num_particles_with_halos, na = ei - si;
+        const size_t nh1 = std::max<uint32_t>(nh, 1);
+
+        // ---- rank-local trouble: collected, not returned.  The local components are made here, in front of the
+        //      all-gather (they need nothing from the other ranks), so that their failure is part of the agreement too
+        enum : uint64_t { FINE = 0, NULL_ARRAY = 1, STALE_SYNC = 2, NO_MEMORY = 3, LOCAL_STEP = 4 };
+        uint64_t trouble = FINE;
+        if (nh && (!x || !y || !z || !labels)) trouble = NULL_ARRAY;
+        else if (viewSync_ != syncs_) trouble = STALE_SYNC; // the last sync was abandoned: tree and radii are not the view's
+        if (!trouble && (fofComp_.ensure(ctx_, nh1 * 4) || fofLabels_.ensure(ctx_, nh1 * 8) || fofScal_.ensure(ctx_, 4096) ||
+                         (groupSizes && (fofSizes_.ensure(ctx_, nh1 * 8) || fofWork_.ensure(ctx_, fofWorkBytes(nh, na))))))
+            trouble = NO_MEMORY;
+        uint32_t* comp = fofComp_.as<uint32_t>();
+        if (!trouble && nh)
+        {
+            cstone_hip_domain_mr_octree t;
+            if (octree(&t) ||
+                cstone_hip_friends_of_friends(ctx_, rb, x, y, z, 0, nh, &view_.box, t.child_offsets, t.internal_to_leaf, t.layout,
+                                              t.centers, t.sizes, b, comp, nullptr, nullptr))
+                trouble = LOCAL_STEP;
+        }
+
+        // ---- ONE all-gather: assigned count, smallest halo radius of a non-empty assigned leaf, status, sizes wanted
+        const uint64_t INF_BITS = 0x7f800000u;
+        std::vector<uint64_t> rows(4 * size_t(P_));
+        const uint64_t row[4] = {na, INF_BITS, trouble, groupSizes ? 1u : 0u};
+        if (P_ > 1)
+        {
+            CS_TRY(cstone_hip_upload(ctx_, gatherRow(), row, sizeof row));
+            if (!trouble) // (low word of the second entry: the radii are floats)
+                fofMinRadius(ctx_, useLet_ ? let_->haloRadii() : radii_.as<float>(), view_.focus_leaf_counts, view_.start_cell,
+                             view_.end_cell, reinterpret_cast<uint32_t*>(gatherRow() + 1));
+            CS_TRY(callComm(comm_.all_gather(comm_.user, gatherRow(), gatherRecv(), sizeof row), "all_gather (fof)"));
+            CS_TRY(copyToHost(ctx_, rows.data(), gatherRecv(), rows.size() * 8));
+        }
+        else { std::copy(row, row + 4, rows.begin()); }
+        for (int p = 0; p < P_; ++p)
+        {
+            const uint64_t st = rows[4 * size_t(p) + 2];
+            if (st == FINE) continue;
+            if (p != rank_) return fail(ctx_, CSTONE_E_INTERNAL, "domain_mr_fof: rank %d reported a failure (refused on every rank)", p);
+            static const char* const why[] = {"", "null array", "the last sync was abandoned", "out of device memory",
+                                              "the local group finder failed"};
+            return fail(ctx_, st == NO_MEMORY ? CSTONE_E_HIP : st == LOCAL_STEP ? CSTONE_E_INTERNAL : CSTONE_E_ARG,
+                        "domain_mr_fof: %s (refused on every rank)", why[st]);
+        }
+        std::vector<uint64_t> offset(size_t(P_) + 1, 0);
+        bool wantSizes = false;
+        for (int p = 0; p < P_; ++p)
+        {
+            // the cover condition, against the very f32 radii the halo discovery of the last sync used.  One rank: every
+            // particle is on the rank, there is nothing to cover
+            float radius;
+            const uint32_t bits = uint32_t(rows[4 * size_t(p) + 1]);
+            std::memcpy(&radius, &bits, sizeof radius);
+            if (P_ > 1 && !(b <= double(radius)))
+                return fail(ctx_, CSTONE_E_ARG,
+                            "domain_mr_fof: linking length %g exceeds the halo radius %g of a leaf of rank %d: a friend may "
+                            "be missing among the halos (refused on every rank)",
+                            b, double(radius), p);
+            offset[p + 1] = offset[p] + rows[4 * size_t(p)];
+            wantSizes     = wantSizes || rows[4 * size_t(p) + 3] != 0;
+        }
+        const uint64_t firstId = offset[rank_];
+
+        // ---- ids: the position in the global SFC order; halos carry their owner's
+        uint64_t* lab = fofLabels_.as<uint64_t>();
+        CS_TRY(cstone_hip_sequence_u64(ctx_, lab + si, na, firstId));
+        CS_TRY(exchangeHalos(lab, 8));
+
+        // ---- rounds
+        uint32_t* changedDev = fofScal_.as<uint32_t>(); // [0]: changed, [1]: groups owned, byte 8: their sum over the ranks
+        uint32_t made = 0, any = 1;
+        while (any && made < maxRounds)
+        {
+            CS_HIP(ctx_, hipMemsetAsync(changedDev, 0, 8, ctx_->stream));
+            CS_TRY(cstone_hip_fof_lower_labels(ctx_, comp, nh, si, ei, lab, changedDev));
+            ++made;
+            CS_TRY(exchangeHalos(lab, 8));
+            if (P_ > 1)
+            {
+                fofClampFlag(ctx_, changedDev); // (the sum of the counts themselves could wrap to 0)
+                CS_TRY(callComm(comm_.all_reduce(comm_.user, changedDev, 1, 1, 0), "all_reduce (fof round)"));
+            }
+            CS_TRY(copyToHost(ctx_, &any, changedDev, 4));
+        }
+        if (any)
+            return fail(ctx_, CSTONE_E_INTERNAL, "domain_mr_fof: labels still changing after %u rounds (max_rounds)", made);
+
+        // ---- number of groups: every group is counted by the owner of its lowest member.  Exact: an f64 sum below 2^53
+        fofCountOwn(ctx_, lab + si, na, firstId, changedDev + 1);
+        uint32_t own = 0;
+        CS_TRY(copyToHost(ctx_, &own, changedDev + 1, 4));
+        double groups = double(own);
+        if (P_ > 1)
+        {
+            double* sum = reinterpret_cast<double*>(fofScal_.as<char>() + 8);
+            CS_TRY(cstone_hip_upload(ctx_, sum, &groups, 8));
+            CS_TRY(callComm(comm_.all_reduce(comm_.user, sum, 1, 0, 0), "all_reduce (fof groups)"));
+            CS_TRY(copyToHost(ctx_, &groups, sum, 8));
+        }
+
+        if (wantSizes) CS_TRY(fofGroupSizes(offset, comp, lab));
+        CS_TRY(cstone_hip_ctx_sync(ctx_)); // the sticky device-side error word
+        if (nh) CS_HIP(ctx_, hipMemcpyAsync(labels, lab, size_t(nh) * 8, hipMemcpyDeviceToDevice, ctx_->stream));
+        if (nh && groupSizes)
+            CS_HIP(ctx_, hipMemcpyAsync(groupSizes, fofSizes_.p, size_t(nh) * 8, hipMemcpyDeviceToDevice, ctx_->stream));
+        if (numGroups) *numGroups = uint64_t(groups);
+        if (rounds) *rounds = made;
         return CSTONE_OK;
     }
 
@@ -1508,7 +1644,9 @@ private:
         view_.halo_boxes_exported = s.numMyBoxes;
         view_.resorts             = uint64_t(resorts_);
         // the sticky device-side error word: a sync that tripped a device-side check must not report success
-        return cstone_hip_ctx_sync(ctx_);
+        CS_TRY(cstone_hip_ctx_sync(ctx_));
+        viewSync_ = syncs_;
+        return CSTONE_OK;
     }
 
     //! CSTONE_MR_TIMING=1: synchronising wall clock per phase, printed by rank 0 when the domain is destroyed
@@ -1912,6 +2050,103 @@ private:
         return cstone_hip_node_centers(ctx_, curve_, kb, rb, nsPrefixes_.p, M, &box_, nsCenters_.p, nsSizes_.p);
     }
 
+    // ---- group sizes of friendsOfFriends().  The slices of fofWork_ for nh particles of which na are assigned:
+    struct FofSlices
+    {
+        size_t count, keys, keysAlt, values, valuesAlt, temp, tempBytes, pairs, answers, componentTotals, totals, end;
+    };
+    static FofSlices fofSlices(uint32_t nh, uint32_t na)
+    {
+        const size_t n = std::max<uint32_t>(nh, 1);
+        FofSlices s{};
+        size_t at   = 0;
+        auto take   = [&](size_t bytes) { const size_t here = at; at += alignUp(bytes); return here; };
+        s.count     = take(n * 4);
+        s.keys      = take(n * 8), s.keysAlt = take(n * 8);
+        s.values    = take(n * 4), s.valuesAlt = take(n * 4);
+        s.tempBytes = cstone_hip_sort_pairs_temp_bytes(64, n);
+        s.temp      = take(s.tempBytes + 256);
+        s.pairs     = take(n * sizeof(FofPair));
+        s.answers   = take(n * 8);
+        s.componentTotals = take(n * 8);
+        s.totals    = take(size_t(std::max<uint32_t>(na, 1)) * 8);
+        s.end       = at;
+        return s;
+    }
+    static size_t fofWorkBytes(uint32_t nh, uint32_t na) { return fofSlices(nh, na).end; }
+
+    //! what an all_to_all_v does, also on one rank (where the one segment is copied)
+    int fofAllToAll(const void* send, const std::vector<uint64_t>& sendCounts, void* recv, const std::vector<uint64_t>& recvCounts,
+                    size_t elem, const char* what)
+    {
+        if (P_ == 1)
+        {
+            if (sendCounts[0])
+                CS_HIP(ctx_, hipMemcpyAsync(recv, send, sendCounts[0] * elem, hipMemcpyDeviceToDevice, ctx_->stream));
+            return CSTONE_OK;
+        }
+        std::vector<size_t> sb(P_), rbv(P_);
+        for (int p = 0; p < P_; ++p)
+            sb[p] = sendCounts[p] * elem, rbv[p] = recvCounts[p] * elem;
+        return callComm(comm_.all_to_all_v(comm_.user, send, sb.data(), recv, rbv.data()), what);
+    }
+
+    /*! fofSizes_[k] = members of k's group over all ranks.  Every local component with an assigned member sends (label,
+     *  assigned members) to the owner of the label -- sorted by label the pairs of one owner are contiguous, owners hold
+     *  contiguous id ranges in rank order --, the owner adds them up per own particle and answers every pair with the
+     *  total; the halo ranges are the owners' values, by the domain's halo exchange.  offset: P + 1 id range bounds. */
+    int fofGroupSizes(const std::vector<uint64_t>& offset, const uint32_t* comp, const uint64_t* lab)
+    {
+        const uint32_t si = view_.start_index, ei = view_.end_index, nh = view_.num_particles_with_halos, na = ei - si;
+        CS_TRY(fofSizes_.ensure(ctx_, size_t(std::max<uint32_t>(nh, 1)) * 8));
+        CS_TRY(fofWork_.ensure(ctx_, fofWorkBytes(nh, na)));
+        const FofSlices s = fofSlices(nh, na);
+        char* w           = fofWork_.as<char>();
+        auto* count = reinterpret_cast<uint32_t*>(w + s.count);
+        auto* keys = reinterpret_cast<uint64_t*>(w + s.keys);
+        auto* values = reinterpret_cast<uint32_t*>(w + s.values);
+        auto* pairs = reinterpret_cast<FofPair*>(w + s.pairs);
+        auto* answers = reinterpret_cast<uint64_t*>(w + s.answers);
+        auto* componentTotals = reinterpret_cast<uint64_t*>(w + s.componentTotals);
+        auto* totals = reinterpret_cast<uint64_t*>(w + s.totals);
+
+        uint32_t numPairs = 0;
+        CS_TRY(fofComponentPairs(ctx_, comp, nh, si, ei, lab, count, keys, values, &numPairs));
+        if (numPairs)
+            CS_TRY(cstone_hip_sort_pairs(ctx_, 64, keys, values, numPairs, w + s.keysAlt, reinterpret_cast<uint32_t*>(w + s.valuesAlt),
+                                         w + s.temp, s.tempBytes));
+        fofPackPairs(ctx_, keys, values, count, numPairs, pairs);
+
+        // pairs per owner: the lower bounds of the owners' first ids in the sorted labels
+        std::vector<uint64_t> sendCounts(P_, 0), recvCounts(P_, 0), matrix;
+        sendCounts[0] = numPairs;
+        if (P_ > 1)
+        {
+            uint64_t* firstIds = reinterpret_cast<uint64_t*>(fofScal_.as<char>() + 256);
+            uint32_t* boundsDev = reinterpret_cast<uint32_t*>(fofScal_.as<char>() + 2048);
+            std::vector<uint32_t> bounds(size_t(P_) + 1, numPairs);
+            CS_TRY(cstone_hip_upload(ctx_, firstIds, offset.data(), size_t(P_) * 8));
+            CS_TRY(cstone_hip_lower_bound_u32(ctx_, 64, keys, numPairs, firstIds, P_, boundsDev));
+            CS_TRY(copyToHost(ctx_, bounds.data(), boundsDev, size_t(P_) * 4));
+            for (int p = 0; p < P_; ++p)
+                sendCounts[p] = bounds[p + 1] - bounds[p];
+        }
+        CS_TRY(countMatrix(sendCounts, matrix)); // the counts travel first
+        uint64_t numRecv = 0;
+        for (int p = 0; p < P_; ++p)
+            numRecv += recvCounts[p] = matrix[size_t(p) * P_ + rank_];
+        if (numRecv >= (uint64_t(1) << 32)) return fail(ctx_, CSTONE_E_CAPACITY, "domain_mr_fof: %llu pairs for one owner", (unsigned long long)numRecv);
+        CS_TRY(fofRecv_.ensure(ctx_, alignUp(std::max<uint64_t>(numRecv, 1) * sizeof(FofPair)) + std::max<uint64_t>(numRecv, 1) * 8));
+        auto* pairsRecv  = fofRecv_.as<FofPair>();
+        auto* answersOut = reinterpret_cast<uint64_t*>(fofRecv_.as<char>() + alignUp(std::max<uint64_t>(numRecv, 1) * sizeof(FofPair)));
+        CS_TRY(fofAllToAll(pairs, sendCounts, pairsRecv, recvCounts, sizeof(FofPair), "all_to_all_v (fof pairs)"));
+        CS_TRY(fofOwnerTotals(ctx_, pairsRecv, uint32_t(numRecv), offset[rank_], na, totals, answersOut));
+        CS_TRY(fofAllToAll(answersOut, recvCounts, answers, sendCounts, 8, "all_to_all_v (fof totals)"));
+        fofSizesFromAnswers(ctx_, values, answers, numPairs, comp, si, ei, componentTotals, fofSizes_.as<uint64_t>());
+        CS_HIP(ctx_, hipGetLastError());
+        return exchangeHalos(fofSizes_.p, 8);
+    }
+
     cstone_hip_ctx* ctx_;
     int curve_, rank_, P_;
     uint32_t bucket_, bucketFocus_;
@@ -1938,6 +2173,7 @@ private:
     bool peerLoop_  = std::getenv("CSTONE_MR_PEER_LOOP") != nullptr; // tests: take the > 32 ranks path (one traversal per peer)
     int syncs_      = 0;
     bool adapted_   = false; // adaptH ran since the last sync (one call per sync; every sync clears it)
+    int viewSync_   = -1;    // the sync view_ was made by; differs from syncs_ after an abandoned sync (friendsOfFriends)
     std::map<std::string, double> phase_;
     std::chrono::steady_clock::time_point t0_;
     std::vector<K> assignment_;
@@ -1989,6 +2225,8 @@ private:
     std::vector<uint64_t> haloSend_, haloRecv_;
     uint64_t haloRecvLo_ = 0, haloRecvHi_ = 0, haloAssigned_ = 0, haloSel_ = 0, haloAnyLast_ = 0;
     DevBuf layout_, radii_, boxes_, boxFlags_, myBoxes_, allBoxes_, oflags_, cnt_, sel_;
+    // friendsOfFriends(): component ids, labels and sizes before they are handed out, scalars, the size protocol's slices
+    DevBuf fofComp_, fofLabels_, fofSizes_, fofScal_, fofWork_, fofRecv_;
     Out out_[2];
     int cur_ = 0;
 };
@@ -2116,6 +2354,14 @@ int cstone_hip_domain_mr_adapt_h(cstone_hip_domain_mr* dom, const void* x, const
 {
     if (!dom) return CSTONE_E_ARG;
     return dom->impl->adaptH(x, y, z, h, ng0, tol, max_iter, grow_limit, counts, status);
+}
+
+int cstone_hip_domain_mr_fof(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z, double linking_length,
+                             uint32_t max_rounds, uint64_t* labels, uint64_t* group_sizes, uint64_t* num_groups,
+                             uint32_t* rounds)
+{
+    if (!dom) return CSTONE_E_ARG;
+    return dom->impl->friendsOfFriends(x, y, z, linking_length, max_rounds, labels, group_sizes, num_groups, rounds);
 }
 
 int cstone_hip_domain_mr_multipoles_get(cstone_hip_domain_mr* dom, const void** multipoles, int32_t* num_nodes)

@@ -22,10 +22,16 @@
 // All atomics are on integers and every result is a function of the components alone: the same input gives the same bits
 // in every run.  The catalogue (cstone_hip_fof_catalog) is a stable radix sort of (label, index), head flags, two scans
 // and a compaction.
+//
+// Groups across ranks (cstone_hip_domain_mr_fof, domain_mr.hip) take these labels as the components
+// of everything present on a rank and lower 64-bit global labels to the minimum of each component, round after round:
+// cstone_hip_fof_lower_labels below -- all ones, one 64-bit atomic minimum per run of equal components of a wave, a
+// broadcast pass that counts what dropped.  The device steps of the group sizes across ranks (fof_mr.hpp) are here too.
 #include <algorithm>
 
 #include "cstone_hip_device.hpp"
 #include "ctx.hpp"
+#include "fof_mr.hpp"
 #include "scan.hpp"
 #include "union_find.hpp"
 
@@ -183,6 +189,173 @@ __global__ __launch_bounds__(256) void fofFillKernel(const uint32_t* __restrict_
     members[outOff[r] + pos] = values[k];
 }
 
+// ---- joining groups across ranks: the lowering step (cstone_hip_fof_lower_labels) and the group sizes (fof_mr.hpp) -----
+
+constexpr int FOF_ERR_COMPONENT = 32; // bit of the sticky error word: a component id or a label outside its range
+
+__global__ __launch_bounds__(256) void fofFillOnesKernel(uint64_t* __restrict__ words, uint32_t n)
+{
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k < n) words[k] = ~uint64_t(0);
+}
+
+//! a 64-bit value from lane (own lane ^ mask): two 32-bit shuffles, both halves travel
+__device__ inline uint64_t shflXor64(uint64_t v, int mask)
+{
+    const uint32_t lo = uint32_t(__shfl_xor(int(uint32_t(v)), mask));
+    const uint32_t hi = uint32_t(__shfl_xor(int(uint32_t(v >> 32)), mask));
+    return (uint64_t(hi) << 32) | lo;
+}
+
+/*! minOf[c] = min(minOf[c], labels[k]) over the k with component[k] == c.  The pattern of fofCountKernel: one 64-bit
+ *  atomic minimum per distinct component of a wave, by the first lane that carries it, with the minimum over the lanes
+ *  that share it (a butterfly in which the other lanes hold all ones; skipped for a component with one lane).  `same` is a
+ *  ballot, so every branch on it is uniform over the wave. */
+__global__ __launch_bounds__(256) void fofLowerMinKernel(const uint32_t* __restrict__ component, uint32_t n,
+                                                         const uint64_t* __restrict__ labels, uint64_t* __restrict__ minOf,
+                                                         int* __restrict__ errors)
+{
+    const uint32_t k    = blockIdx.x * 256u + threadIdx.x;
+    const unsigned lane = threadIdx.x & 63u;
+    const uint32_t comp = k < n ? component[k] : 0u;
+    const bool ok       = k < n && comp < n; // (a component id beyond n has no word in minOf: reported, never written)
+    if (k < n && !ok) atomicOr(errors, FOF_ERR_COMPONENT);
+    const uint64_t lab = ok ? labels[k] : ~uint64_t(0);
+    uint64_t todo      = __ballot(ok);
+    while (todo)
+    {
+        const int leader    = __ffsll((long long)todo) - 1;
+        const uint32_t head = uint32_t(__shfl(int(comp), leader));
+        const uint64_t same = __ballot(ok && comp == head) & todo;
+        uint64_t low        = lab;
+        if (same & (same - 1)) // more than one lane
+        {
+            low = ((same >> lane) & 1u) ? lab : ~uint64_t(0);
+            for (int offset = 32; offset; offset >>= 1)
+            {
+                const uint64_t other = shflXor64(low, offset);
+                low                  = other < low ? other : low;
+            }
+        }
+        if (int(lane) == leader) (void)__hip_atomic_fetch_min(minOf + head, low, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        todo &= ~same;
+    }
+}
+
+//! labels[k] = minOf[component[k]]; *changed += the k of [first, last) whose label dropped (one atomicAdd per wave)
+__global__ __launch_bounds__(256) void fofLowerBroadcastKernel(const uint32_t* __restrict__ component, uint32_t n,
+                                                               uint32_t first, uint32_t last,
+                                                               const uint64_t* __restrict__ minOf, uint64_t* __restrict__ labels,
+                                                               uint32_t* __restrict__ changed)
+{
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    bool dropped     = false;
+    if (k < n)
+    {
+        const uint32_t comp = component[k];
+        if (comp < n)
+        {
+            const uint64_t low = minOf[comp];
+            if (low < labels[k])
+            {
+                labels[k] = low;
+                dropped   = true;
+            }
+        }
+    }
+    const uint64_t votes = __ballot(dropped && k >= first && k < last);
+    if ((threadIdx.x & 63u) == 0 && votes) atomicAdd(changed, uint32_t(__popcll(votes)));
+}
+
+//! *numOwn += the k < n with labels[k] == firstId + k: the groups whose lowest member is one of these particles
+__global__ __launch_bounds__(256) void fofCountOwnKernel(const uint64_t* __restrict__ labels, uint32_t n, uint64_t firstId,
+                                                         uint32_t* __restrict__ numOwn)
+{
+    const uint32_t k     = blockIdx.x * 256u + threadIdx.x;
+    const uint64_t votes = __ballot(k < n && labels[k] == firstId + k);
+    if ((threadIdx.x & 63u) == 0 && votes) atomicAdd(numOwn, uint32_t(__popcll(votes)));
+}
+
+__global__ __launch_bounds__(256) void fofPairFlagsKernel(const uint32_t* __restrict__ count, uint32_t n,
+                                                          uint32_t* __restrict__ flags)
+{
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    if (c < n) flags[c] = count[c] ? 1u : 0u;
+}
+
+//! one (label, component) pair per component with a counted member; pos: exclusive scan of the flags
+__global__ __launch_bounds__(256) void fofEmitPairsKernel(const uint32_t* __restrict__ count, const uint32_t* __restrict__ pos,
+                                                          const uint64_t* __restrict__ labels, uint32_t n,
+                                                          uint64_t* __restrict__ keys, uint32_t* __restrict__ values)
+{
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= n || !count[c]) return;
+    keys[pos[c]]   = labels[c]; // (a component id is the index of one of its members)
+    values[pos[c]] = c;
+}
+
+__global__ __launch_bounds__(256) void fofPackPairsKernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ values,
+                                                          const uint32_t* __restrict__ count, uint32_t numPairs,
+                                                          FofPair* __restrict__ pairs)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < numPairs) pairs[i] = FofPair{keys[i], uint64_t(count[values[i]])};
+}
+
+//! the owner's side: totals[label - firstId] += count for every received pair (a label that is not mine is reported)
+__global__ __launch_bounds__(256) void fofAddTotalsKernel(const FofPair* __restrict__ pairs, uint32_t numPairs, uint64_t firstId,
+                                                          uint32_t numOwn, unsigned long long* __restrict__ totals,
+                                                          int* __restrict__ errors)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= numPairs) return;
+    const uint64_t slot = pairs[i].label - firstId;
+    if (slot < numOwn) atomicAdd(totals + slot, (unsigned long long)pairs[i].count);
+    else atomicOr(errors, FOF_ERR_COMPONENT);
+}
+
+__global__ __launch_bounds__(256) void fofAnswerKernel(const FofPair* __restrict__ pairs, uint32_t numPairs, uint64_t firstId,
+                                                       uint32_t numOwn, const unsigned long long* __restrict__ totals,
+                                                       uint64_t* __restrict__ answers)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= numPairs) return;
+    const uint64_t slot = pairs[i].label - firstId;
+    answers[i]          = slot < numOwn ? uint64_t(totals[slot]) : 0u;
+}
+
+__global__ __launch_bounds__(256) void fofScatterTotalsKernel(const uint32_t* __restrict__ values,
+                                                              const uint64_t* __restrict__ answers, uint32_t numPairs,
+                                                              uint64_t* __restrict__ componentTotals)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < numPairs) componentTotals[values[i]] = answers[i];
+}
+
+//! sizes[k] = componentTotals[component[k]] for k in [first, last)
+__global__ __launch_bounds__(256) void fofSizesOfComponentsKernel(const uint32_t* __restrict__ component, uint32_t first,
+                                                                  uint32_t last, const uint64_t* __restrict__ componentTotals,
+                                                                  uint64_t* __restrict__ sizes)
+{
+    const uint32_t k = first + blockIdx.x * 256u + threadIdx.x;
+    if (k < last) sizes[k] = componentTotals[component[k]];
+}
+
+//! *out = min(*out, bits of radii[leaf]) over the leaves of [first, last) that hold particles (radii are >= 0: the bit
+//! patterns order like the values)
+__global__ __launch_bounds__(256) void fofMinRadiusKernel(const float* __restrict__ radii, const uint32_t* __restrict__ counts,
+                                                          int first, int last, uint32_t* __restrict__ out)
+{
+    const int leaf = first + int(blockIdx.x * 256u + threadIdx.x);
+    uint32_t bits  = 0x7f800000u; // +inf
+    if (leaf < last && counts[leaf]) bits = __float_as_uint(radii[leaf]);
+    for (int offset = 32; offset; offset >>= 1)
+        bits = min(bits, uint32_t(__shfl_xor(int(bits), offset)));
+    if ((threadIdx.x & 63u) == 0 && bits != 0x7f800000u) atomicMin(out, bits);
+}
+
+__global__ void fofClampFlagKernel(uint32_t* word) { *word = *word ? 1u : 0u; }
+
 template<class T>
 void launchLink(cstone_hip_ctx* ctx, const void* x, const void* y, const void* z, uint32_t first, uint32_t last,
                 const cstone_box& box, const int32_t* childOffsets, const int32_t* internalToLeaf, const uint32_t* layout,
@@ -197,9 +370,106 @@ void launchLink(cstone_hip_ctx* ctx, const void* x, const void* y, const void* z
 
 } // namespace
 
+void fofMinRadius(cstone_hip_ctx* ctx, const float* radii, const uint32_t* counts, int first, int last, uint32_t* outBits)
+{
+    if (last > first)
+        hipLaunchKernelGGL(fofMinRadiusKernel, gridFor(size_t(last - first), 256), 256, 0, ctx->stream, radii, counts, first,
+                           last, outBits);
+}
+
+void fofClampFlag(cstone_hip_ctx* ctx, uint32_t* word) { hipLaunchKernelGGL(fofClampFlagKernel, 1, 1, 0, ctx->stream, word); }
+
+void fofCountOwn(cstone_hip_ctx* ctx, const uint64_t* labels, uint32_t n, uint64_t firstId, uint32_t* numOwn)
+{
+    if (n) hipLaunchKernelGGL(fofCountOwnKernel, gridFor(n, 256), 256, 0, ctx->stream, labels, n, firstId, numOwn);
+}
+
+int fofComponentPairs(cstone_hip_ctx* ctx, const uint32_t* component, uint32_t n, uint32_t first, uint32_t last,
+                      const uint64_t* labels, uint32_t* count, uint64_t* keys, uint32_t* values, uint32_t* numPairsHost)
+{
+    *numPairsHost = 0;
+    if (n == 0 || last <= first) return CSTONE_OK;
+    const size_t words = alignUp(size_t(n) * sizeof(uint32_t));
+    CS_TRY(arenaReserve(ctx, 2 * words + scanArenaBytes(n) + 1024));
+    uint32_t* flags = static_cast<uint32_t*>(arenaTake(ctx, words));
+    uint32_t* pos   = static_cast<uint32_t*>(arenaTake(ctx, words));
+    uint32_t* total = static_cast<uint32_t*>(arenaTake(ctx, 256));
+    const unsigned grid = gridFor(n, 256);
+    int rc              = CSTONE_OK;
+    if (hipError_t e = hipMemsetAsync(count, 0, size_t(n) * sizeof(uint32_t), ctx->stream); e != hipSuccess)
+        rc = fail(ctx, CSTONE_E_HIP, "fof group sizes: %s", hipGetErrorString(e));
+    if (rc == CSTONE_OK)
+    {
+        // (the counting pass of the single-rank call, on the window: count[component[k]] for first <= k < last)
+        hipLaunchKernelGGL(fofCountKernel, gridFor(last - first, 256), 256, 0, ctx->stream, component + first, 0u, last - first,
+                           count);
+        hipLaunchKernelGGL(fofPairFlagsKernel, grid, 256, 0, ctx->stream, count, n, flags);
+        rc = scanU32(ctx, flags, pos, n, 0u, false, total);
+    }
+    if (rc == CSTONE_OK)
+    {
+        hipLaunchKernelGGL(fofEmitPairsKernel, grid, 256, 0, ctx->stream, count, pos, labels, n, keys, values);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess)
+            rc = fail(ctx, CSTONE_E_HIP, "fof group sizes: %s", hipGetErrorString(e));
+    }
+    if (rc == CSTONE_OK) rc = copyToHost(ctx, numPairsHost, total, sizeof(uint32_t));
+    arenaReset(ctx);
+    return rc;
+}
+
+void fofPackPairs(cstone_hip_ctx* ctx, const uint64_t* keys, const uint32_t* values, const uint32_t* count,
+                  uint32_t numPairs, FofPair* pairs)
+{
+    if (numPairs)
+        hipLaunchKernelGGL(fofPackPairsKernel, gridFor(numPairs, 256), 256, 0, ctx->stream, keys, values, count, numPairs, pairs);
+}
+
+int fofOwnerTotals(cstone_hip_ctx* ctx, const FofPair* pairs, uint32_t numPairs, uint64_t firstId, uint32_t numOwn,
+                   uint64_t* totals, uint64_t* answers)
+{
+    if (numOwn) CS_HIP(ctx, hipMemsetAsync(totals, 0, size_t(numOwn) * sizeof(uint64_t), ctx->stream));
+    if (!numPairs) return CSTONE_OK;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t));
+    auto* t = reinterpret_cast<unsigned long long*>(totals);
+    hipLaunchKernelGGL(fofAddTotalsKernel, gridFor(numPairs, 256), 256, 0, ctx->stream, pairs, numPairs, firstId, numOwn, t,
+                       ctx->devScalars + 63);
+    hipLaunchKernelGGL(fofAnswerKernel, gridFor(numPairs, 256), 256, 0, ctx->stream, pairs, numPairs, firstId, numOwn, t,
+                       answers);
+    return CSTONE_OK;
+}
+
+void fofSizesFromAnswers(cstone_hip_ctx* ctx, const uint32_t* values, const uint64_t* answers, uint32_t numPairs,
+                         const uint32_t* component, uint32_t first, uint32_t last, uint64_t* componentTotals, uint64_t* sizes)
+{
+    if (numPairs)
+        hipLaunchKernelGGL(fofScatterTotalsKernel, gridFor(numPairs, 256), 256, 0, ctx->stream, values, answers, numPairs,
+                           componentTotals);
+    if (last > first)
+        hipLaunchKernelGGL(fofSizesOfComponentsKernel, gridFor(last - first, 256), 256, 0, ctx->stream, component, first, last,
+                           componentTotals, sizes);
+}
+
 } // namespace cship
 
 using namespace cship;
+
+extern "C" int cstone_hip_fof_lower_labels(cstone_hip_ctx* ctx, const uint32_t* component, uint32_t n, uint32_t first,
+                                           uint32_t last, uint64_t* labels, uint32_t* changed)
+{
+    if (!ctx || !component || !labels || !changed || last < first || last > n)
+        return fail(ctx, CSTONE_E_ARG, "fof_lower_labels: bad argument");
+    if (n == 0) return CSTONE_OK;
+    CS_TRY(arenaReserve(ctx, alignUp(size_t(n) * sizeof(uint64_t)) + 256));
+    uint64_t* minOf     = static_cast<uint64_t*>(arenaTake(ctx, alignUp(size_t(n) * sizeof(uint64_t))));
+    const unsigned grid = gridFor(n, 256);
+    hipLaunchKernelGGL(fofFillOnesKernel, grid, 256, 0, ctx->stream, minOf, n);
+    hipLaunchKernelGGL(fofLowerMinKernel, grid, 256, 0, ctx->stream, component, n, labels, minOf, ctx->devScalars + 63);
+    hipLaunchKernelGGL(fofLowerBroadcastKernel, grid, 256, 0, ctx->stream, component, n, first, last, minOf, labels, changed);
+    arenaReset(ctx);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+        return fail(ctx, CSTONE_E_HIP, "fof_lower_labels: %s", hipGetErrorString(e));
+    return CSTONE_OK;
+}
 
 extern "C" int cstone_hip_friends_of_friends(cstone_hip_ctx* ctx, int real_bits, const void* x, const void* y, const void* z,
                                              uint32_t first, uint32_t last, const cstone_box* box_host,

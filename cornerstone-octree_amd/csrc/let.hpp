@@ -383,6 +383,8 @@ public:
     const uint32_t* leafCounts() const { return leafCounts_.as<uint32_t>(); }
     const uint32_t* layout() const { return layout_.as<uint32_t>(); }
     const int32_t* haloFlags() const { return flags_.as<int32_t>(); }
+    //! the f32 search radii of the last halo discovery per leaf (0 outside the assigned leaves and for empty ones)
+    const float* haloRadii() const { return radii_.as<float>(); }
     const K* prefixes() const { return prefixes_.as<K>(); }
     const int32_t* childOffsets() const { return child_.as<int32_t>(); }
     const int32_t* parents() const { return parents_.as<int32_t>(); }

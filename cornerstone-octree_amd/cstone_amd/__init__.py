@@ -72,7 +72,11 @@ EXPORTS = [
     "cstone_hip_adapt_smoothing_lengths", "cstone_hip_domain_adapt_h", "cstone_hip_domain_mr_adapt_h",
     # friends-of-friends groups: lock-free union-find on the neighbour walk (csrc/fof.hip)
     "cstone_hip_friends_of_friends", "cstone_hip_fof_catalog", "cstone_hip_domain_fof",
+    # ... across ranks: the lowering step of a round and the collective call (csrc/fof.hip, csrc/domain_mr.hip)
+    "cstone_hip_fof_lower_labels", "cstone_hip_domain_mr_fof",
 ]
+
+FOF_MR_DEFAULT_ROUNDS = 4096  # CSTONE_FOF_MR_DEFAULT_ROUNDS: what max_rounds = 0 means to cstone_hip_domain_mr_fof
 
 # status word of the adapt calls: number of walks in bits 0-7, then the CSTONE_ADAPT_H_* flags
 ADAPT_H_WALKS_MASK, ADAPT_H_NOT_CONVERGED, ADAPT_H_CAPPED, ADAPT_H_STALLED = 0xFF, 0x100, 0x200, 0x400
@@ -122,6 +126,14 @@ def load_library():
     lib = C.CDLL(path)
     lib.cstone_hip_last_error.restype = C.c_char_p
     lib.cstone_hip_sort_pairs_temp_bytes.restype = C.c_size_t
+    # friends-of-friends across ranks: (ctx, component, n, first, last, labels, changed) and (domain, x, y, z,
+    # linking_length, max_rounds, labels, group_sizes, num_groups*, rounds*)
+    lib.cstone_hip_fof_lower_labels.restype = C.c_int
+    lib.cstone_hip_fof_lower_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                C.c_void_p]
+    lib.cstone_hip_domain_mr_fof.restype = C.c_int
+    lib.cstone_hip_domain_mr_fof.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_uint32,
+                                             C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     return lib
 
 
@@ -591,6 +603,15 @@ class Context:
             _ptr(sizes), C.c_double(linking_length), _ptr(labels), _ptr(gs),
             C.byref(ng) if want_num_groups else None), "friends_of_friends")
         return labels, gs, (ng.value if want_num_groups else None)
+
+    def fof_lower_labels(self, component, labels, changed, first=0, last=None):
+        """cstone_hip_fof_lower_labels, the device step of a round of friends-of-friends across ranks: labels (int64
+        tensor holding uint64 bits, IN PLACE) get the minimum over the entries with the same component (int32 tensor,
+        values in [0, n)); changed (int32 tensor of one element) grows by the labels of [first, last) that dropped.
+        Asynchronous"""
+        n = labels.numel()
+        self._chk(self.lib.cstone_hip_fof_lower_labels(self.h, _ptr(component), n, first, n if last is None else last,
+                                                       _ptr(labels), _ptr(changed)), "fof_lower_labels")
 
     def fof_catalog(self, labels, first, last, min_members=1, capacity=None):
         """cstone_hip_fof_catalog: (group_offsets [num_groups + 1], members [number of particles listed]) of the groups with

@@ -368,6 +368,30 @@ class NativeDistributedDomain:
             self.exchange_halos(h)
         return nc, st
 
+    def fof(self, x, y, z, linking_length, want_sizes=True, max_rounds=0):
+        """Friends-of-friends groups over the particles of all ranks (cstone_hip_domain_mr_fof; collective): returns
+        (labels, sizes or None, num_groups, rounds).  labels: int64 tensor (uint64 bits) laid out like the result arrays of
+        the last sync, the lowest global id -- position in the global SFC order -- among the members of each particle's
+        group, halo ranges included; sizes: the members of the group over all ranks, same layout; num_groups: over all
+        ranks; rounds: lowering passes made.  x, y, z: laid out like those arrays and read on the halo ranges too.  The
+        linking length must not exceed the halo radius of the last sync (2 h x halo factor of every assigned leaf) on any
+        rank; want_sizes must be the same on every rank that holds particles.  max_rounds 0: the library's default"""
+        torch = _torch()
+        n = self.view().num_particles_with_halos
+        labels = torch.zeros(n, dtype=torch.int64, device=x.device)
+        sizes = torch.zeros(n, dtype=torch.int64, device=x.device) if want_sizes else None
+        ng, rounds = C.c_uint64(0), C.c_uint32(0)
+        rc = self.ctx.lib.cstone_hip_domain_mr_fof(self.h, x.data_ptr() if n else None, y.data_ptr() if n else None,
+                                                   z.data_ptr() if n else None, linking_length, max_rounds,
+                                                   labels.data_ptr() if n else None,
+                                                   sizes.data_ptr() if want_sizes and n else None, C.byref(ng),
+                                                   C.byref(rounds))
+        if rc != 0 and self.coll.error is not None:
+            err, self.coll.error = self.coll.error, None
+            raise err
+        self.ctx._chk(rc, "domain_mr_fof")
+        return labels, sizes, ng.value, rounds.value
+
     def multipoles(self):
         """(num_nodes, 8) multipoles of the focus tree as the last gravity() built them (a tensor that aliases the
         domain's array), or None"""

@@ -983,6 +983,27 @@ public:
                        "MultiRankDomain::adaptSmoothingLengths");
         if (exchange) exchangeHalos(h);
     }
+    //! what friendsOfFriends reports beside the arrays
+    struct FofResult
+    {
+        std::uint64_t numGroups; //!< groups over all ranks
+        unsigned rounds;         //!< lowering passes made (2 on one rank; grows with the rank boundaries a group crosses)
+    };
+    /*! Friends-of-friends groups over the particles of ALL ranks (cstone_hip_domain_mr_fof; collective): labels[k] = the
+     *  lowest global id -- the position in the global SFC order of the last sync -- among the members of k's group,
+     *  groupSizes[k] (nullable, on every rank alike) = the members of that group over all ranks.  x, y, z, labels,
+     *  groupSizes: device arrays laid out like the result arrays, nParticlesWithHalos() elements; the halo ranges come back
+     *  filled with the owners' values.  The linking length must not exceed the halo radius of the last sync (2 h x halo
+     *  factor of every assigned leaf) on any rank: refused on every rank otherwise.  maxRounds 0: the library's default. */
+    FofResult friendsOfFriends(const T* x, const T* y, const T* z, double linkingLength, std::uint64_t* labels,
+                               std::uint64_t* groupSizes = nullptr, unsigned maxRounds = 0)
+    {
+        FofResult r{0, 0};
+        Context::check(cstone_hip_domain_mr_fof(dom_, x, y, z, linkingLength, maxRounds, labels, groupSizes, &r.numGroups,
+                                                &r.rounds),
+                       "MultiRankDomain::friendsOfFriends");
+        return r;
+    }
     //! the multipoles of the focus tree that the last computeGravity built: 8 values of T per node (device), or null
     const T* multipoles() const
     {
@@ -1386,7 +1407,8 @@ public:
     /*! Friends-of-friends groups (cstone_hip_domain_fof) of the particles [startIndex(), endIndex()) of the last sync at the
      *  given linking length; x, y, z laid out like the result arrays.  labels (and groupSizes, if given) are resized to
      *  nParticles() and indexed from startIndex(); a label is the lowest index into the synced arrays among the members of
-     *  the particle's group.  Returns the number of groups.  One rank: groups are not joined across ranks. */
+     *  the particle's group.  Returns the number of groups.  One rank: its 32-bit labels cannot hold global ids; on
+     *  several ranks use friendsOfFriendsGlobal. */
     unsigned friendsOfFriends(const DeviceVector<T>& x, const DeviceVector<T>& y, const DeviceVector<T>& z,
                               double linkingLength, DeviceVector<LocalIndex>& labels,
                               DeviceVector<unsigned>* groupSizes = nullptr)
@@ -1399,6 +1421,27 @@ public:
                                              groupSizes ? groupSizes->data() : nullptr, &numGroups),
                        "Domain::friendsOfFriends");
         return numGroups;
+    }
+    /*! Friends-of-friends groups over the particles of ALL ranks of a multi-rank domain (MultiRankDomain::friendsOfFriends,
+     *  collective).  x, y, z: the synced arrays, nParticlesWithHalos() elements.  labels and groupSizes (if given; on
+     *  every rank alike) are resized to nParticlesWithHalos() and laid out like x: a label is the lowest GLOBAL id --
+     *  position in the global SFC order of the last sync -- among the members of the particle's group over all ranks, a size
+     *  the number of those members; the halo ranges hold the owners' values.  Returns the number of groups over all ranks;
+     *  *rounds: the lowering passes made.  A domain constructed without collectives has friendsOfFriends instead. */
+    std::uint64_t friendsOfFriendsGlobal(const DeviceVector<T>& x, const DeviceVector<T>& y, const DeviceVector<T>& z,
+                                         double linkingLength, DeviceVector<std::uint64_t>& labels,
+                                         DeviceVector<std::uint64_t>* groupSizes = nullptr, unsigned* rounds = nullptr,
+                                         unsigned maxRounds = 0)
+    {
+        if (!mr_) throw std::runtime_error("Domain friendsOfFriendsGlobal: a domain without collectives (friendsOfFriends)\n");
+        if (x.size() != nParticlesWithHalos() || y.size() != x.size() || z.size() != x.size())
+            throw std::runtime_error("Domain friendsOfFriendsGlobal: x, y, z are not laid out like the synced arrays\n");
+        labels.resize(nParticlesWithHalos());
+        if (groupSizes) groupSizes->resize(nParticlesWithHalos());
+        const auto r = mr_->friendsOfFriends(x.data(), y.data(), z.data(), linkingLength, labels.data(),
+                                             groupSizes ? groupSizes->data() : nullptr, maxRounds);
+        if (rounds) *rounds = r.rounds;
+        return r.numGroups;
     }
     //! R/domain/domain.hpp:411: stores the flag like the reference does (its member convergeTrees, :661, has no reader
     //! there either: the trees converge on the first sync and take one update step per sync afterwards)

@@ -1189,7 +1189,8 @@ extern "C"
      *               index), head flags, two scans, a compaction; last - first < 2^30; synchronises the stream.
      * domain_fof  : friends_of_friends for the particles [start_index, end_index) of the last sync on the view's octree;
      *               x, y, z laid out like the sync's results, labels / group_sizes indexed from start_index, labels hold
-     *               indices into the synced arrays.  One rank only: joining groups across ranks is not provided.
+     *               indices into the synced arrays.  Groups over the particles of several ranks: cstone_hip_domain_mr_fof,
+     *               below.
      * ------------------------------------------------------------------------------------------- */
     int cstone_hip_friends_of_friends(cstone_hip_ctx* ctx, int real_bits, const void* x, const void* y, const void* z,
                                       uint32_t first, uint32_t last, const cstone_box* box_host,
@@ -1202,6 +1203,55 @@ extern "C"
                                uint32_t* num_groups);
     int cstone_hip_domain_fof(cstone_hip_domain* dom, const void* x, const void* y, const void* z, double linking_length,
                               uint32_t* labels, uint32_t* group_sizes, uint32_t* num_groups);
+
+    /* ---------------------------------------------------------------------------------------------
+     * Friends-of-friends groups ACROSS RANKS (csrc/domain_mr.hip, csrc/fof.hip; the method and its proof: DESIGN.md 5f).
+     *
+     * Global id   of an assigned particle i: offset[rank] + (i - start_index), offset = the exclusive sum of the ranks'
+     *             assigned counts in rank order -- the particle's position in the global SFC order of the last sync.  A
+     *             uint64_t.  A halo particle carries its owner's id (the domain's halo exchange of the id array).
+     * Link        the rule of cstone_hip_friends_of_friends, unchanged: the same d2, the same fold, strict <, and b below
+     *             half of every periodic edge.  A group is a connected component over the particles of ALL ranks.
+     * Label       labels[k] = the LOWEST global id among the members of k's group.  Canonical: the same bits in every
+     *             run and on every communicator (for the same global SFC order).
+     * Cover       every particle within b of an assigned particle must be on the rank.  The halos of a sync reach the
+     *             radius  float(2 * max h of the leaf * halo factor)  around every assigned leaf, so the call demands
+     *             b <= that radius for every non-empty assigned leaf of every rank, and compares with the very f32 values
+     *             the halo discovery of the last sync used (they are kept; h is not consulted again).  If one rank fails
+     *             the bound, EVERY rank returns CSTONE_E_ARG with nothing written.  On a communicator of ONE rank every
+     *             particle is on the rank: there is no bound.
+     *
+     * fof_lower_labels : the device step of a round.  component[k] in [0, n) is equal for exactly the members of one
+     *             local group (the labels of cstone_hip_friends_of_friends on [0, n) are such values).  Effect:
+     *             labels[k] = min{ labels[m] : component[m] == component[k] } for all k < n; *changed (device) is
+     *             INCREASED by the number of k in [first, last) whose label dropped.  n 64-bit words of the context's
+     *             workspace, one 64-bit atomic minimum per run of equal components of a wave; integer atomics only, the
+     *             result is a function of the input.  Asynchronous on the context's stream.  CSTONE_E_ARG for a null
+     *             pointer, last < first or last > n; n == 0 is CSTONE_OK.  A component[k] >= n is not followed: it ORs 32
+     *             into the sticky error word (cstone_hip_ctx_sync then fails).
+     *
+     * domain_mr_fof : COLLECTIVE, every rank calls it.  x, y, z, labels, group_sizes: device, laid out like the result
+     *             arrays of the last sync (num_particles_with_halos entries); the halo ranges of labels and group_sizes
+     *             come back filled with the owners' values.  A rank without particles may pass null arrays.
+     *             group_sizes (nullable): the members of k's group over all ranks; computed if ANY rank asks for it.
+     *             *num_groups (host, nullable): the number of groups over all ranks.  *rounds (host, nullable): lowering
+     *             passes made; the rounds { fof_lower_labels over everything present on the rank, halos included;
+     *             exchange_halos(labels); all-reduce of "an assigned label changed" } end with the first quiet one, so a
+     *             communicator of one rank makes 2 (1 without any link), and the number grows with the number of rank
+     *             boundaries the path through a group crosses.  max_rounds: a guard, 0 means
+     *             CSTONE_FOF_MR_DEFAULT_ROUNDS; reaching it is CSTONE_E_INTERNAL on every rank together.
+     *             Refused with CSTONE_E_ARG on every rank, before any collective and with nothing written: no sync yet,
+     *             linking_length <= 0, NaN, or >= half a periodic edge.  Rank-local trouble (a null array, an abandoned
+     *             last sync, no memory) travels in the one all-gather the call starts with, and then every rank
+     *             returns an error together.  Synchronises the stream (one read-back per round).
+     *             Left to the client: a catalogue of the members across ranks (sort by label), masses and centres.
+     * ------------------------------------------------------------------------------------------- */
+#define CSTONE_FOF_MR_DEFAULT_ROUNDS 4096u
+    int cstone_hip_fof_lower_labels(cstone_hip_ctx* ctx, const uint32_t* component, uint32_t n, uint32_t first,
+                                    uint32_t last, uint64_t* labels, uint32_t* changed);
+    int cstone_hip_domain_mr_fof(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z,
+                                 double linking_length, uint32_t max_rounds, uint64_t* labels, uint64_t* group_sizes,
+                                 uint64_t* num_groups, uint32_t* rounds);
 
 #ifdef __cplusplus
 }
