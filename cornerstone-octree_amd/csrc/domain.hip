@@ -136,6 +136,10 @@ struct DomainBase
                        float growLimit, uint32_t* counts, uint32_t* status) = 0;
     virtual int fof(const void* x, const void* y, const void* z, double linkingLength, uint32_t* labels,
                     uint32_t* groupSizes, uint32_t* numGroups) = 0;
+    virtual int fofProperties(const void* x, const void* y, const void* z, const void* m, int massBits, const void* vx,
+                              const void* vy, const void* vz, const uint32_t* groupOffsets, const uint32_t* members,
+                              uint32_t numGroups, void* mass, void* center, void* velocity, void* radius,
+                              uint32_t* flags) = 0;
     virtual void stats(cstone_hip_domain_stats* out)     = 0;
 };
 
@@ -277,6 +281,16 @@ public:
         return cstone_hip_friends_of_friends(ctx_, rb, x, y, z, startIndex_, endIndex_, &box_, fChild_.as<int32_t>(),
                                              fItl_.as<int32_t>(), layout_.as<uint32_t>(), fCenters_.p, fSizes_.p,
                                              linkingLength, labels, groupSizes, numGroups);
+    }
+
+    //! cstone_hip_fof_group_properties with the box of the last sync
+    int fofProperties(const void* x, const void* y, const void* z, const void* m, int massBits, const void* vx, const void* vy,
+                      const void* vz, const uint32_t* groupOffsets, const uint32_t* members, uint32_t numGroups, void* mass,
+                      void* center, void* velocity, void* radius, uint32_t* flags) override
+    {
+        if (firstCall_ || fLeaves_ < 1) return fail(ctx_, CSTONE_E_ARG, "domain_fof_properties: no sync yet");
+        return cstone_hip_fof_group_properties(ctx_, rb, massBits, x, y, z, m, vx, vy, vz, &box_, groupOffsets, members,
+                                               numGroups, mass, center, velocity, radius, flags);
     }
 
     /*! Domain::updateExpansionCenters (R/domain/domain.hpp:415-421) on one rank = FocusedOctree::updateCenters without its
@@ -1225,6 +1239,16 @@ int cstone_hip_domain_fof(cstone_hip_domain* dom, const void* x, const void* y, 
 {
     if (!dom) return CSTONE_E_ARG;
     return dom->impl->fof(x, y, z, linking_length, labels, group_sizes, num_groups);
+}
+
+int cstone_hip_domain_fof_properties(cstone_hip_domain* dom, const void* x, const void* y, const void* z, const void* m,
+                                     int mass_bits, const void* vx, const void* vy, const void* vz,
+                                     const uint32_t* group_offsets, const uint32_t* members, uint32_t num_groups, void* mass,
+                                     void* center, void* velocity, void* radius, uint32_t* flags)
+{
+    if (!dom) return CSTONE_E_ARG;
+    return dom->impl->fofProperties(x, y, z, m, mass_bits, vx, vy, vz, group_offsets, members, num_groups, mass, center,
+                                    velocity, radius, flags);
 }
 
 int cstone_hip_domain_view_get(cstone_hip_domain* dom, cstone_hip_domain_view* out)

@@ -31,6 +31,7 @@
 #include "devbuf.hpp"
 #include "device_keys.hpp"
 #include "fof_mr.hpp"
+#include "fof_props.hpp"
 #include "host_tree.hpp"
 #include "let.hpp"
 #include "resort.hpp"
@@ -369,6 +370,10 @@ struct MrBase
                        float growLimit, uint32_t* counts, uint32_t* status)                = 0;
     virtual int friendsOfFriends(const void* x, const void* y, const void* z, double linkingLength, uint32_t maxRounds,
                                  uint64_t* labels, uint64_t* groupSizes, uint64_t* numGroups, uint32_t* rounds) = 0;
+    virtual int fofCatalog(const void* x, const void* y, const void* z, const void* m, int massBits, const void* vx,
+                           const void* vy, const void* vz, const uint64_t* labels, uint64_t minMembers, size_t capacity,
+                           uint64_t* groupLabels, uint64_t* groupSizes, void* mass, void* center, void* velocity,
+                           void* radius, uint32_t* flags, uint32_t* numGroupsHost) = 0;
     virtual int multipoles(const void** out, int32_t* numNodes)                           = 0;
     virtual int octupoles(const void** out, int32_t* numNodes)                            = 0;
     virtual int view(cstone_hip_domain_mr_view* out)                                     = 0;
@@ -766,7 +771,164 @@ public:
             CS_HIP(ctx_, hipMemcpyAsync(groupSizes, fofSizes_.p, size_t(nh) * 8, hipMemcpyDeviceToDevice, ctx_->stream));
         if (numGroups) *numGroups = uint64_t(groups);
         if (rounds) *rounds = made;
+        fofOffset_     = offset; // the id ranges these labels were made with (fofCatalog)
+        fofOffsetSync_ = syncs_;
         return CSTONE_OK;
+    }
+
+    /*! The group catalogue across ranks (cstone_hip_domain_mr_fof_catalog; the rule and the method: include/cstone_hip.h,
+     *  DESIGN.md section 5f): one partial per distinct label of the assigned range about its first member, the partials
+     *  to the owners of the labels, the owner's combine in (label, source rank) order, filter and finish.  Two
+     *  collectives: the all-gather of the counts per owner, with the status of the local steps on board, and the
+     *  all_to_all_v of the records.  The capacity is judged behind them. */
+    int fofCatalog(const void* x, const void* y, const void* z, const void* m, int massBits, const void* vx, const void* vy,
+                   const void* vz, const uint64_t* labels, uint64_t minMembers, size_t capacity, uint64_t* groupLabels,
+                   uint64_t* groupSizes, void* mass, void* center, void* velocity, void* radius, uint32_t* flags,
+                   uint32_t* numGroupsHost) override
+    {
+        // ---- what is the same on every rank: refused before any collective
+        if (firstCall_) return fail(ctx_, CSTONE_E_ARG, "domain_mr_fof_catalog: no sync yet");
+        if (fofOffsetSync_ != syncs_ || fofOffset_.size() != size_t(P_) + 1)
+            return fail(ctx_, CSTONE_E_ARG, "domain_mr_fof_catalog: no domain_mr_fof since the last sync");
+        const int nv = (vx ? 1 : 0) + (vy ? 1 : 0) + (vz ? 1 : 0);
+        if ((massBits != 32 && massBits != 64) || (nv != 0 && nv != 3) || !numGroupsHost)
+            return fail(ctx_, CSTONE_E_ARG, "domain_mr_fof_catalog: bad argument");
+        if (minMembers == 0) minMembers = 1;
+        const uint32_t si = view_.start_index, ei = view_.end_index, na = ei - si;
+        const std::vector<uint64_t>& offset = fofOffset_;
+        const uint64_t total = offset[P_], firstId = offset[rank_];
+
+        // ---- rank-local trouble and the local steps: collected, not returned
+        enum : uint64_t { FINE = 0, NULL_ARRAY = 1, NO_MEMORY = 2, BAD_LABEL = 3, LOCAL_STEP = 4 };
+        uint64_t trouble = FINE;
+        if (na && (!x || !y || !z || !m || !labels || !groupLabels || !groupSizes || !mass || !center || (nv == 3 && !velocity)))
+            trouble = NULL_ARRAY;
+        else if (na >= (1u << 30)) trouble = LOCAL_STEP;
+        const size_t n1        = std::max<uint32_t>(na, 1);
+        const size_t tempBytes = cstone_hip_sort_pairs_temp_bytes(64, n1);
+        size_t at              = 0;
+        auto take              = [&](size_t bytes) { const size_t here = at; at += alignUp(bytes); return here; };
+        const size_t oKeys = take(n1 * 8), oKeysAlt = take(n1 * 8), oVal = take(n1 * 4), oValAlt = take(n1 * 4),
+                     oTemp = take(tempBytes + 256), oWork = take((2 * n1 + 64) * 4), oStart = take((n1 + 1) * 4),
+                     oRunLabels = take(n1 * 8);
+        // the owners' first ids and the bounds of their records: sized by the number of ranks
+        const size_t oFirstIds = 256, oBounds = oFirstIds + alignUp(size_t(P_) * 8), scalBytes = oBounds + alignUp((size_t(P_) + 1) * 4);
+        if (!trouble && (catWork_.ensure(ctx_, at) || catPart_.ensure(ctx_, sizeof(FofPartial)) || catScal_.ensure(ctx_, scalBytes)))
+            trouble = NO_MEMORY;
+        char* w = catWork_.as<char>();
+        uint32_t runs[2] = {0, 0}; // distinct labels here, labels outside [0, total)
+        std::vector<uint64_t> sendCounts(P_, 0), recvCounts(P_, 0);
+        auto localSteps = [&]() -> int
+        {
+            auto* keys = reinterpret_cast<uint64_t*>(w + oKeys);
+            auto* values = reinterpret_cast<uint32_t*>(w + oVal);
+            auto* runStart = reinterpret_cast<uint32_t*>(w + oStart);
+            auto* runLabels = reinterpret_cast<uint64_t*>(w + oRunLabels);
+            CS_HIP(ctx_, hipMemcpyAsync(keys, labels + si, size_t(na) * 8, hipMemcpyDeviceToDevice, ctx_->stream));
+            CS_TRY(cstone_hip_sequence_u32(ctx_, values, na, si));
+            // stable: the members of a label stay in ascending order, its first member is its lowest index
+            CS_TRY(cstone_hip_sort_pairs(ctx_, 64, keys, values, na, w + oKeysAlt, reinterpret_cast<uint32_t*>(w + oValAlt),
+                                         w + oTemp, tempBytes));
+            CS_TRY(fofRunsU64(ctx_, keys, na, total, reinterpret_cast<uint32_t*>(w + oWork), runStart, runLabels, runs));
+            if (runs[1]) return CSTONE_OK; // (reported as BAD_LABEL)
+            if (catPart_.ensure(ctx_, size_t(runs[0]) * sizeof(FofPartial))) return CSTONE_E_HIP;
+            CS_TRY(fofPropsReduce(ctx_, rb, massBits, x, y, z, m, vx, vy, vz, view_.box, runStart, values, runs[0], FofGroupOut{},
+                                  catPart_.as<FofPartial>(), keys));
+            sendCounts[0] = runs[0];
+            if (P_ > 1)
+            {
+                uint64_t* firstIds  = reinterpret_cast<uint64_t*>(catScal_.as<char>() + oFirstIds);
+                uint32_t* boundsDev = reinterpret_cast<uint32_t*>(catScal_.as<char>() + oBounds);
+                std::vector<uint32_t> bounds(size_t(P_) + 1, runs[0]);
+                CS_TRY(cstone_hip_upload(ctx_, firstIds, offset.data(), size_t(P_) * 8));
+                CS_TRY(cstone_hip_lower_bound_u32(ctx_, 64, runLabels, runs[0], firstIds, P_, boundsDev));
+                CS_TRY(copyToHost(ctx_, bounds.data(), boundsDev, size_t(P_) * 4));
+                for (int p = 0; p < P_; ++p)
+                    sendCounts[p] = bounds[p + 1] - bounds[p];
+            }
+            return CSTONE_OK;
+        };
+        if (!trouble && na)
+        {
+            const int rc = localSteps();
+            if (rc != CSTONE_OK) trouble = rc == CSTONE_E_HIP ? NO_MEMORY : LOCAL_STEP;
+            else if (runs[1]) trouble = BAD_LABEL;
+            if (trouble) std::fill(sendCounts.begin(), sendCounts.end(), uint64_t(0));
+        }
+
+        // ---- collective 1: the counts per owner and the status
+        const size_t rowLen = size_t(P_) + 1;
+        std::vector<uint64_t> rows(rowLen * P_), row(sendCounts);
+        row.push_back(trouble);
+        if (P_ > 1)
+        {
+            CS_TRY(cstone_hip_upload(ctx_, gatherRow(), row.data(), rowLen * 8));
+            CS_TRY(callComm(comm_.all_gather(comm_.user, gatherRow(), gatherRecv(), rowLen * 8), "all_gather (fof catalogue)"));
+            CS_TRY(copyToHost(ctx_, rows.data(), gatherRecv(), rows.size() * 8));
+        }
+        else { rows = row; }
+        for (int p = 0; p < P_; ++p)
+        {
+            const uint64_t st = rows[rowLen * p + P_];
+            if (st == FINE) continue;
+            if (p != rank_)
+                return fail(ctx_, CSTONE_E_INTERNAL, "domain_mr_fof_catalog: rank %d reported a failure (refused on every rank)", p);
+            static const char* const why[] = {"", "null array", "out of device memory", "a label outside [0, total)",
+                                              "a local step failed"};
+            return fail(ctx_, st == NO_MEMORY ? CSTONE_E_HIP : st == LOCAL_STEP ? CSTONE_E_INTERNAL : CSTONE_E_ARG,
+                        "domain_mr_fof_catalog: %s (refused on every rank)", why[st]);
+        }
+        uint64_t numRecv = 0;
+        for (int p = 0; p < P_; ++p)
+            numRecv += recvCounts[p] = rows[rowLen * p + rank_];
+        if (numRecv >= (uint64_t(1) << 30))
+            return fail(ctx_, CSTONE_E_CAPACITY, "domain_mr_fof_catalog: %llu records for one owner", (unsigned long long)numRecv);
+
+        // ---- collective 2: the records to the owners.  How much arrives is known only now, behind the one agreement: a
+        //      rank whose receive buffer cannot be had (or whose share exceeds 2^30 records) returns ALONE, and the others
+        //      then wait in the all_to_all_v -- as in the size protocol of friendsOfFriends
+        const size_t r1 = std::max<uint64_t>(numRecv, 1), tempR = cstone_hip_sort_pairs_temp_bytes(64, r1);
+        at = 0;
+        const size_t oRec = take(r1 * sizeof(FofPartial)), oKeysR = take(r1 * 8), oKeysAltR = take(r1 * 8), oOrd = take(r1 * 4),
+                     oOrdAlt = take(r1 * 4), oTempR = take(tempR + 256), oWorkR = take((2 * r1 + 64) * 4),
+                     oStartR = take((r1 + 1) * 4), oComb = take(r1 * sizeof(FofPartial)), oKeep = take(r1 * 4),
+                     oPos = take(r1 * 4), oTotal = take(256);
+        CS_TRY(catRecv_.ensure(ctx_, at));
+        char* q       = catRecv_.as<char>();
+        auto* records = reinterpret_cast<FofPartial*>(q + oRec);
+        CS_TRY(fofAllToAll(catPart_.p, sendCounts, records, recvCounts, sizeof(FofPartial), "all_to_all_v (fof catalogue)"));
+        *numGroupsHost = 0;
+        if (numRecv == 0) return CSTONE_OK;
+
+        // ---- the owner: stable sort by label (the records arrive by source rank), combine, filter, finish
+        auto* keysR = reinterpret_cast<uint64_t*>(q + oKeysR);
+        auto* order = reinterpret_cast<uint32_t*>(q + oOrd);
+        auto* runStartR = reinterpret_cast<uint32_t*>(q + oStartR);
+        auto* combined = reinterpret_cast<FofPartial*>(q + oComb);
+        auto* keep = reinterpret_cast<uint32_t*>(q + oKeep);
+        auto* pos = reinterpret_cast<uint32_t*>(q + oPos);
+        auto* totalDev = reinterpret_cast<uint32_t*>(q + oTotal);
+        fofPartialLabels(ctx_, records, uint32_t(numRecv), keysR);
+        CS_TRY(cstone_hip_sequence_u32(ctx_, order, numRecv, 0));
+        CS_TRY(cstone_hip_sort_pairs(ctx_, 64, keysR, order, numRecv, q + oKeysAltR, reinterpret_cast<uint32_t*>(q + oOrdAlt),
+                                     q + oTempR, tempR));
+        uint32_t ownRuns[2] = {0, 0};
+        CS_TRY(fofRunsU64(ctx_, keysR, uint32_t(numRecv), ~uint64_t(0), reinterpret_cast<uint32_t*>(q + oWorkR), runStartR,
+                          nullptr, ownRuns));
+        CS_TRY(fofCombinePartials(ctx_, rb, x, y, z, view_.box, records, order, runStartR, ownRuns[0], firstId, si, na,
+                                  minMembers, combined, keep));
+        CS_TRY(arenaReserve(ctx_, scanArenaBytes(ownRuns[0]) + 1024));
+        const int scanned = scanU32(ctx_, keep, pos, ownRuns[0], 0u, false, totalDev);
+        arenaReset(ctx_);
+        CS_TRY(scanned);
+        uint32_t kept = 0;
+        CS_TRY(copyToHost(ctx_, &kept, totalDev, 4));
+        CS_TRY(cstone_hip_ctx_sync(ctx_)); // the sticky device-side error word (a record whose label is not mine)
+        *numGroupsHost = kept;
+        if (kept > capacity)
+            return fail(ctx_, CSTONE_E_CAPACITY, "domain_mr_fof_catalog: %u groups, capacity %zu", kept, capacity);
+        return fofFinishCombined(ctx_, rb, nv == 3, view_.box, combined, keep, pos, ownRuns[0],
+                                 FofGroupOut{mass, center, velocity, radius, flags, groupLabels, groupSizes});
     }
 
     int multipoles(const void** out, int32_t* numNodes) override
@@ -2227,6 +2389,11 @@ private:
     DevBuf layout_, radii_, boxes_, boxFlags_, myBoxes_, allBoxes_, oflags_, cnt_, sel_;
     // friendsOfFriends(): component ids, labels and sizes before they are handed out, scalars, the size protocol's slices
     DevBuf fofComp_, fofLabels_, fofSizes_, fofScal_, fofWork_, fofRecv_;
+    // fofCatalog(): the id ranges of the last friendsOfFriends() and the sync they belong to; the sender's slices, its
+    // partials, the owner's slices
+    std::vector<uint64_t> fofOffset_;
+    int fofOffsetSync_ = -1;
+    DevBuf catWork_, catPart_, catRecv_, catScal_;
     Out out_[2];
     int cur_ = 0;
 };
@@ -2362,6 +2529,17 @@ int cstone_hip_domain_mr_fof(cstone_hip_domain_mr* dom, const void* x, const voi
 {
     if (!dom) return CSTONE_E_ARG;
     return dom->impl->friendsOfFriends(x, y, z, linking_length, max_rounds, labels, group_sizes, num_groups, rounds);
+}
+
+int cstone_hip_domain_mr_fof_catalog(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z, const void* m,
+                                     int mass_bits, const void* vx, const void* vy, const void* vz, const uint64_t* labels,
+                                     uint64_t min_members, size_t capacity, uint64_t* group_labels, uint64_t* group_sizes,
+                                     void* mass, void* center, void* velocity, void* radius, uint32_t* flags,
+                                     uint32_t* num_groups_host)
+{
+    if (!dom) return CSTONE_E_ARG;
+    return dom->impl->fofCatalog(x, y, z, m, mass_bits, vx, vy, vz, labels, min_members, capacity, group_labels, group_sizes,
+                                 mass, center, velocity, radius, flags, num_groups_host);
 }
 
 int cstone_hip_domain_mr_multipoles_get(cstone_hip_domain_mr* dom, const void** multipoles, int32_t* num_nodes)

@@ -74,7 +74,11 @@ EXPORTS = [
     "cstone_hip_friends_of_friends", "cstone_hip_fof_catalog", "cstone_hip_domain_fof",
     # ... across ranks: the lowering step of a round and the collective call (csrc/fof.hip, csrc/domain_mr.hip)
     "cstone_hip_fof_lower_labels", "cstone_hip_domain_mr_fof",
+    # the group catalogue: mass, centre, velocity, radius of every group (csrc/fof_props.hip, csrc/domain_mr.hip)
+    "cstone_hip_fof_group_properties", "cstone_hip_domain_fof_properties", "cstone_hip_domain_mr_fof_catalog",
 ]
+
+FOF_GROUP_WIDE, FOF_GROUP_MASSLESS = 0x1, 0x2  # CSTONE_FOF_GROUP_*: the flags of the group catalogue
 
 FOF_MR_DEFAULT_ROUNDS = 4096  # CSTONE_FOF_MR_DEFAULT_ROUNDS: what max_rounds = 0 means to cstone_hip_domain_mr_fof
 
@@ -134,6 +138,19 @@ def load_library():
     lib.cstone_hip_domain_mr_fof.restype = C.c_int
     lib.cstone_hip_domain_mr_fof.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_uint32,
                                              C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    # the group catalogue: (ctx, real_bits, mass_bits, x, y, z, m, vx, vy, vz, box*, group_offsets, members, num_groups,
+    # mass, center, velocity, radius, flags); the domain's call has the domain and mass_bits behind m instead
+    lib.cstone_hip_fof_group_properties.restype = C.c_int
+    lib.cstone_hip_fof_group_properties.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 10 + [C.c_uint32] +
+                                                    [C.c_void_p] * 5)
+    lib.cstone_hip_domain_fof_properties.restype = C.c_int
+    lib.cstone_hip_domain_fof_properties.argtypes = ([C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 5 + [C.c_uint32] +
+                                                     [C.c_void_p] * 5)
+    # (domain, x, y, z, m, mass_bits, vx, vy, vz, labels, min_members, capacity, group_labels, group_sizes, mass, center,
+    # velocity, radius, flags, num_groups*)
+    lib.cstone_hip_domain_mr_fof_catalog.restype = C.c_int
+    lib.cstone_hip_domain_mr_fof_catalog.argtypes = ([C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 4 +
+                                                     [C.c_uint64, C.c_size_t] + [C.c_void_p] * 7 + [C.POINTER(C.c_uint32)])
     return lib
 
 
@@ -627,6 +644,24 @@ class Context:
                                                   C.byref(ng)), "fof_catalog")
         offsets = offsets[:ng.value + 1]
         return offsets, members[:int(offsets[-1].item())]
+
+    def fof_group_properties(self, x, y, z, m, group_offsets, members, box, vel=None, want_radius=True, want_flags=True):
+        """cstone_hip_fof_group_properties on a catalogue as fof_catalog returns it: (mass [G], center [G, 3], velocity
+        [G, 3] or None, radius [G] or None, flags [G] (int32 holding the CSTONE_FOF_GROUP_* bits) or None) in the
+        coordinate type.  vel: (vx, vy, vz) or None.  The rule: include/cstone_hip.h.  Asynchronous"""
+        torch = _torch()
+        ng = group_offsets.numel() - 1
+        mass = torch.zeros(ng, dtype=x.dtype, device=x.device)
+        center = torch.zeros((ng, 3), dtype=x.dtype, device=x.device)
+        velocity = torch.zeros((ng, 3), dtype=x.dtype, device=x.device) if vel is not None else None
+        radius = torch.zeros(ng, dtype=x.dtype, device=x.device) if want_radius else None
+        flags = torch.zeros(ng, dtype=torch.int32, device=x.device) if want_flags else None
+        vx, vy, vz = vel if vel is not None else (None, None, None)
+        self._chk(self.lib.cstone_hip_fof_group_properties(
+            self.h, x.element_size() * 8, m.element_size() * 8, _ptr(x), _ptr(y), _ptr(z), _ptr(m), _ptr(vx), _ptr(vy),
+            _ptr(vz), C.cast(C.byref(box), C.c_void_p), _ptr(group_offsets), _ptr(members), ng, _ptr(mass), _ptr(center),
+            _ptr(velocity), _ptr(radius), _ptr(flags)), "fof_group_properties")
+        return mass, center, velocity, radius, flags
 
     def compute_fixed_groups(self, first, last, group_size):
         torch = _torch()

@@ -392,6 +392,41 @@ class NativeDistributedDomain:
         self.ctx._chk(rc, "domain_mr_fof")
         return labels, sizes, ng.value, rounds.value
 
+    def fof_catalog(self, x, y, z, m, labels, vel=None, min_members=1, capacity=None):
+        """The group catalogue across ranks (cstone_hip_domain_mr_fof_catalog; collective): the groups whose lowest global
+        id this rank owns, with at least min_members members over all ranks, by ascending label.  Returns (group_labels,
+        group_sizes (int64 tensors holding uint64 bits), mass, center [G, 3], velocity [G, 3] or None, radius, flags) in
+        the coordinate type.  labels: those of fof() for the same sync; x, y, z, m, vel = (vx, vy, vz) or None laid out
+        like the result arrays of the last sync, read on the assigned range only.  capacity: rows to make room for
+        (default: one per assigned particle); too few raises CstoneError (CSTONE_E_CAPACITY) on this rank alone"""
+        torch = _torch()
+        v = self.view()
+        n, na = v.num_particles_with_halos, v.end_index - v.start_index
+        cap = na if capacity is None else capacity
+        rows = max(cap, 1)
+        gl = torch.zeros(rows, dtype=torch.int64, device=self.ctx.device)
+        gs = torch.zeros(rows, dtype=torch.int64, device=self.ctx.device)
+        tdt = x.dtype
+        mass = torch.zeros(rows, dtype=tdt, device=self.ctx.device)
+        center = torch.zeros((rows, 3), dtype=tdt, device=self.ctx.device)
+        velocity = torch.zeros((rows, 3), dtype=tdt, device=self.ctx.device) if vel is not None else None
+        radius = torch.zeros(rows, dtype=tdt, device=self.ctx.device)
+        flags = torch.zeros(rows, dtype=torch.int32, device=self.ctx.device)
+        P = lambda t: t.data_ptr() if (t is not None and n) else None  # noqa: E731
+        vx, vy, vz = vel if vel is not None else (None, None, None)
+        ng = C.c_uint32(0)
+        rc = self.ctx.lib.cstone_hip_domain_mr_fof_catalog(self.h, P(x), P(y), P(z), P(m), m.element_size() * 8, P(vx), P(vy),
+                                                           P(vz), P(labels), min_members, cap, gl.data_ptr(), gs.data_ptr(),
+                                                           mass.data_ptr(), center.data_ptr(),
+                                                           velocity.data_ptr() if vel is not None else None,
+                                                           radius.data_ptr(), flags.data_ptr(), C.byref(ng))
+        if rc != 0 and self.coll.error is not None:
+            err, self.coll.error = self.coll.error, None
+            raise err
+        self.ctx._chk(rc, "domain_mr_fof_catalog")
+        g = ng.value
+        return gl[:g], gs[:g], mass[:g], center[:g], (velocity[:g] if vel is not None else None), radius[:g], flags[:g]
+
     def multipoles(self):
         """(num_nodes, 8) multipoles of the focus tree as the last gravity() built them (a tensor that aliases the
         domain's array), or None"""

@@ -191,6 +191,26 @@ class Domain:
         self.ctx._chk(rc, "domain_fof")
         return labels, gs, ng.value
 
+    def fof_properties(self, x, y, z, m, group_offsets, members, vel=None):
+        """cstone_hip_domain_fof_properties: Context.fof_group_properties with the box of the last sync, on a catalogue
+        (Context.fof_catalog) of this domain's fof labels; x, y, z, m and vel = (vx, vy, vz) or None laid out like the
+        sync's results.  Returns (mass, center, velocity or None, radius, flags)"""
+        import torch
+
+        ng = group_offsets.numel() - 1
+        mass = torch.zeros(ng, dtype=x.dtype, device=x.device)
+        center = torch.zeros((ng, 3), dtype=x.dtype, device=x.device)
+        velocity = torch.zeros((ng, 3), dtype=x.dtype, device=x.device) if vel is not None else None
+        radius = torch.zeros(ng, dtype=x.dtype, device=x.device)
+        flags = torch.zeros(ng, dtype=torch.int32, device=x.device)
+        P = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        vx, vy, vz = vel if vel is not None else (None, None, None)
+        rc = self.ctx.lib.cstone_hip_domain_fof_properties(self.h, P(x), P(y), P(z), P(m), m.element_size() * 8, P(vx), P(vy),
+                                                           P(vz), P(group_offsets), P(members), ng, P(mass), P(center),
+                                                           P(velocity), P(radius), P(flags))
+        self.ctx._chk(rc, "domain_fof_properties")
+        return mass, center, velocity, radius, flags
+
     def reapply_sync(self, field):
         """Domain::reapplySync: field (n rows of the last sync's input, 1..32 bytes each) in the order of the result"""
         import torch

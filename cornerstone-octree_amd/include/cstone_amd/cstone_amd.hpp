@@ -748,6 +748,37 @@ inline unsigned fofCatalogGpu(const LocalIndex* labels, LocalIndex first, LocalI
     return numGroups;
 }
 
+//! the rows of a group catalogue: mass, centre (x, y, z per group), velocity, rms radius and the CSTONE_FOF_GROUP_* flags
+template<class T>
+struct FofGroupTable
+{
+    DeviceVector<T> mass, center, velocity, radius;
+    DeviceVector<unsigned> flags;
+    void resize(std::size_t numGroups, bool velocities)
+    {
+        mass.resize(numGroups), center.resize(3 * numGroups), radius.resize(numGroups), flags.resize(numGroups);
+        velocity.resize(velocities ? 3 * numGroups : 0);
+    }
+};
+
+/*! Mass, centre, velocity and rms radius of every group of a catalogue (cstone_hip_fof_group_properties; the rule is
+ *  stated in include/cstone_hip.h): groupOffsets and members as fofCatalogGpu leaves them, m the masses (float or double),
+ *  vx, vy, vz all three or all null.  The table is resized to the number of groups.  Asynchronous. */
+template<class T, class Tm>
+void fofGroupPropertiesGpu(const T* x, const T* y, const T* z, const Tm* m, const T* vx, const T* vy, const T* vz,
+                           const Box<T>& box, const DeviceVector<LocalIndex>& groupOffsets,
+                           const DeviceVector<LocalIndex>& members, FofGroupTable<T>& table)
+{
+    const std::size_t numGroups = groupOffsets.size() ? groupOffsets.size() - 1 : 0;
+    table.resize(numGroups, vx != nullptr);
+    Context::check(cstone_hip_fof_group_properties(Context::get(), detail::realBits<T>(), int(8 * sizeof(Tm)), x, y, z, m, vx,
+                                                   vy, vz, &box.pod(), groupOffsets.data(), members.data(), unsigned(numGroups),
+                                                   table.mass.data(), table.center.data(),
+                                                   vx ? table.velocity.data() : nullptr, table.radius.data(),
+                                                   table.flags.data()),
+                   "fofGroupPropertiesGpu");
+}
+
 /*! The transport of the multi-rank Domain on a node of MI355X: RCCL, served from C++ inside libcstone_hip on the context's
  *  stream (csrc/comm_rccl.hip) -- replaces the MPI point-to-point exchanges of the reference
  *  (R/domain/domaindecomp_mpi_gpu.cuh:86-185, R/halos/exchange_halos_gpu.cuh:35-119).  One rank obtains the id
@@ -1004,6 +1035,25 @@ public:
                        "MultiRankDomain::friendsOfFriends");
         return r;
     }
+    /*! The group catalogue across ranks (cstone_hip_domain_mr_fof_catalog; collective): this rank's table lists the
+     *  groups whose lowest global id it owns, with at least max(minMembers, 1) members over all ranks, by ascending label.
+     *  labels: those of friendsOfFriends for the same sync; x, y, z, m, vx, vy, vz (all three or all null): laid out like the
+     *  result arrays, read on the assigned range only.  capacity rows in every output; returns the number of groups, and
+     *  CSTONE_E_CAPACITY in *status (nothing written) when they do not fit; every other failure throws. */
+    template<class Tm>
+    unsigned fofCatalog(const T* x, const T* y, const T* z, const Tm* m, const T* vx, const T* vy, const T* vz,
+                        const std::uint64_t* labels, std::uint64_t minMembers, std::size_t capacity,
+                        std::uint64_t* groupLabels, std::uint64_t* groupSizes, T* mass, T* center, T* velocity, T* radius,
+                        unsigned* flags, int* status)
+    {
+        unsigned numGroups = 0;
+        const int rc = cstone_hip_domain_mr_fof_catalog(dom_, x, y, z, m, int(8 * sizeof(Tm)), vx, vy, vz, labels, minMembers,
+                                                        capacity, groupLabels, groupSizes, mass, center, velocity, radius,
+                                                        flags, &numGroups);
+        if (rc != CSTONE_E_CAPACITY) Context::check(rc, "MultiRankDomain::fofCatalog");
+        *status = rc;
+        return numGroups;
+    }
     //! the multipoles of the focus tree that the last computeGravity built: 8 values of T per node (device), or null
     const T* multipoles() const
     {
@@ -1191,7 +1241,7 @@ public:
         scratch.rebind(ps, n, capOf(ps));
         keys.resize(m);
         i = 0;
-        std::apply([&](auto&... vec) { (vec.rebind(pp[i], m, capOf(pp[i])), ..., void(++i)); }, properties);
+        std::apply([&](auto&... vec) { ((vec.rebind(pp[i], m, capOf(pp[i])), ++i), ...); }, properties);
     }
 
     /*! the reference's signature (R/domain/domain.hpp:196-203): the scratch buffers come as a tuple; the first one with
@@ -1442,6 +1492,53 @@ public:
                                              groupSizes ? groupSizes->data() : nullptr, maxRounds);
         if (rounds) *rounds = r.rounds;
         return r.numGroups;
+    }
+    /*! Mass, centre, velocity and rms radius of the groups of a catalogue of friendsOfFriends labels
+     *  (cstone_hip_domain_fof_properties: fofGroupPropertiesGpu with the box of the last sync).  x, y, z, m and vx, vy, vz
+     *  (all three or all null) are laid out like the result arrays. */
+    template<class Tm>
+    void fofGroupProperties(const DeviceVector<T>& x, const DeviceVector<T>& y, const DeviceVector<T>& z,
+                            const DeviceVector<Tm>& m, const DeviceVector<T>* vx, const DeviceVector<T>* vy,
+                            const DeviceVector<T>* vz, const DeviceVector<LocalIndex>& groupOffsets,
+                            const DeviceVector<LocalIndex>& members, FofGroupTable<T>& table)
+    {
+        if (mr_) throw std::runtime_error("Domain fofGroupProperties: on several ranks use fofCatalogGlobal\n");
+        const std::size_t numGroups = groupOffsets.size() ? groupOffsets.size() - 1 : 0;
+        table.resize(numGroups, vx != nullptr);
+        Context::check(cstone_hip_domain_fof_properties(dom_, x.data(), y.data(), z.data(), m.data(), int(8 * sizeof(Tm)),
+                                                        vx ? vx->data() : nullptr, vy ? vy->data() : nullptr,
+                                                        vz ? vz->data() : nullptr, groupOffsets.data(), members.data(),
+                                                        unsigned(numGroups), table.mass.data(), table.center.data(),
+                                                        vx ? table.velocity.data() : nullptr, table.radius.data(),
+                                                        table.flags.data()),
+                       "Domain::fofGroupProperties");
+    }
+    /*! The group catalogue over the particles of ALL ranks of a multi-rank domain (MultiRankDomain::fofCatalog, collective):
+     *  labels are those of friendsOfFriendsGlobal for the same sync.  This rank's rows -- the groups whose lowest global id
+     *  it owns, with at least minMembers members over all ranks, by ascending label -- go to groupLabels, groupSizes and
+     *  the table, all resized to fit.  Returns their number.  Room is made for one group per assigned particle, so the
+     *  call is made once on every rank. */
+    template<class Tm>
+    unsigned fofCatalogGlobal(const DeviceVector<T>& x, const DeviceVector<T>& y, const DeviceVector<T>& z,
+                              const DeviceVector<Tm>& m, const DeviceVector<T>* vx, const DeviceVector<T>* vy,
+                              const DeviceVector<T>* vz, const DeviceVector<std::uint64_t>& labels, std::uint64_t minMembers,
+                              DeviceVector<std::uint64_t>& groupLabels, DeviceVector<std::uint64_t>& groupSizes,
+                              FofGroupTable<T>& table)
+    {
+        if (!mr_) throw std::runtime_error("Domain fofCatalogGlobal: a domain without collectives (fofGroupProperties)\n");
+        const std::size_t capacity = std::max<std::size_t>(nParticles(), 1);
+        groupLabels.resize(capacity), groupSizes.resize(capacity);
+        table.resize(capacity, vx != nullptr);
+        int status = CSTONE_OK;
+        const unsigned numGroups =
+            mr_->fofCatalog(x.data(), y.data(), z.data(), m.data(), vx ? vx->data() : nullptr, vy ? vy->data() : nullptr,
+                            vz ? vz->data() : nullptr, labels.data(), minMembers, capacity, groupLabels.data(),
+                            groupSizes.data(), table.mass.data(), table.center.data(),
+                            vx ? table.velocity.data() : nullptr, table.radius.data(), table.flags.data(), &status);
+        Context::check(status, "Domain::fofCatalogGlobal");
+        groupLabels.resize(numGroups), groupSizes.resize(numGroups);
+        table.resize(numGroups, vx != nullptr);
+        return numGroups;
     }
     //! R/domain/domain.hpp:411: stores the flag like the reference does (its member convergeTrees, :661, has no reader
     //! there either: the trees converge on the first sync and take one update step per sync afterwards)

@@ -1244,7 +1244,8 @@ extern "C"
      *             linking_length <= 0, NaN, or >= half a periodic edge.  Rank-local trouble (a null array, an abandoned
      *             last sync, no memory) travels in the one all-gather the call starts with, and then every rank
      *             returns an error together.  Synchronises the stream (one read-back per round).
-     *             Left to the client: a catalogue of the members across ranks (sort by label), masses and centres.
+     *             Masses, centres, velocities and radii of the groups across ranks: cstone_hip_domain_mr_fof_catalog, below.
+     *             Left to the client: the list of the members of a group across ranks (sort by label).
      * ------------------------------------------------------------------------------------------- */
 #define CSTONE_FOF_MR_DEFAULT_ROUNDS 4096u
     int cstone_hip_fof_lower_labels(cstone_hip_ctx* ctx, const uint32_t* component, uint32_t n, uint32_t first,
@@ -1252,6 +1253,80 @@ extern "C"
     int cstone_hip_domain_mr_fof(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z,
                                  double linking_length, uint32_t max_rounds, uint64_t* labels, uint64_t* group_sizes,
                                  uint64_t* num_groups, uint32_t* rounds);
+
+    /* ---------------------------------------------------------------------------------------------
+     * The friends-of-friends GROUP CATALOGUE (csrc/fof_props.hip): mass, centre, velocity and rms radius of every group.
+     * The rule, stated so that a restatement reproduces the flags bit for bit and the sums within a derived bound
+     * (tests/fof_props_support.py is one).  A group has members j with masses m_j and a reference particle ref; on one
+     * rank ref is members[group_offsets[g]], for a catalogue of cstone_hip_fof_catalog the group's label particle.
+     *
+     *   Offset   T = coordinate type.  d_a = r_j,a - r_ref,a in T.  On a periodic axis a, with L_a = T(lim[2a+1]) -
+     *            T(lim[2a]) in T:  if d_a >= T(0.5) * L_a then d_a -= L_a, else if d_a < -(T(0.5) * L_a) then d_a += L_a.
+     *            At most one fold, no contraction.
+     *   Sums     in double whatever real_bits and mass_bits are, every operand converted first:
+     *            M = sum m_j,  S_a = sum m_j * d_a,  Q = sum m_j * (d_x * d_x + d_y * d_y + d_z * d_z),  P_a = sum m_j * v_j,a.
+     *   Results  mass = T(M).  center_a: c = double(r_ref,a) + S_a / M; on a periodic axis c += L_a if c < lo_a, else
+     *            c -= L_a if c >= hi_a; T(c), and lo_a in place of a T(c) that rounded up to hi_a: in [lo_a, hi_a).
+     *            velocity_a = T(P_a / M).  radius = T(sqrt(max(0, Q / M - |S / M|^2))), the mass-weighted rms distance
+     *            of the members from the centre.  M == 0: center = r_ref, velocity = 0, radius = 0 and
+     *            CSTONE_FOF_GROUP_MASSLESS.
+     *   Flag     CSTONE_FOF_GROUP_WIDE iff some member has |d_a| >= T(0.25) * L_a on a periodic axis a.  While it is clear
+     *            every two members are closer than half the box on every periodic axis and the unwrapping is unambiguous.
+     *            When it is set (a percolating group, say) mass, velocity and size are still exact statements, centre and
+     *            radius are only the rule's values.
+     *   Order    no floating-point atomics.  The order of every sum is fixed by the member order and the kernel's fixed
+     *            shape (csrc/fof_props.hip; the launch shape is no argument): the same input gives the same bits in every
+     *            run, on every stream and context.
+     *
+     * fof_group_properties : x, y, z (T), m (mass_bits), vx, vy, vz (T; all three or none), group_offsets [num_groups + 1]
+     *            and members: device, exactly what cstone_hip_fof_catalog writes; any partition in this form is taken
+     *            (group_offsets ascend strictly from 0: no empty group).  mass T[G], center T[G][3], velocity T[G][3]
+     *            (untouched without velocities), radius T[G], flags u32[G]; the last three nullable.  Asynchronous on the
+     *            context's stream: the number of members is read on the device.  CSTONE_E_ARG with nothing written for
+     *            bad bits, only some of vx, vy, vz, velocities without `velocity`, a null required pointer while
+     *            num_groups > 0.  num_groups == 0: CSTONE_OK.
+     * domain_fof_properties : the same with the box of the domain's last sync (CSTONE_E_ARG before the first).
+     *
+     * domain_mr_fof_catalog : COLLECTIVE.  labels: those of cstone_hip_domain_mr_fof for the same sync (the call keeps
+     *            the ranks' id ranges of that call; without one since the last sync: CSTONE_E_ARG on every rank before
+     *            any collective, like "no sync yet").  x, y, z, m, vx, vy, vz (all three or none), labels: laid out like
+     *            the sync's results; only [start_index, end_index) is read.  Every group is reported by exactly ONE rank,
+     *            the owner of its lowest global id: rows 0 .. *num_groups_host - 1 of group_labels, group_sizes, mass,
+     *            center, velocity, radius, flags (the last four nullable; velocity required with velocities) list its groups
+     *            with at least max(min_members, 1) members over all ranks by ascending label.  capacity: rows the
+     *            arrays hold; too few: CSTONE_E_CAPACITY with *num_groups_host set and nothing written, on that rank
+     *            alone -- decided behind the last collective.
+     *            Method: a stable sort of (label, index) over the assigned range; the segmented reduction gives one
+     *            partial {n_p, M_p, S_p, Q_p, P_p, wide, r_p} per distinct label about its first member r_p in that
+     *            order; one all-gather of the counts per owner (rank-local trouble -- a null array with particles
+     *            present, no memory for the local steps, a label outside [0, total) -- rides in it: every rank fails
+     *            together), one all_to_all_v of the records.  NOT covered by that agreement: the owner's receive buffer,
+     *            whose size is known only behind it -- a rank that cannot allocate it, or is sent 2^30 records or more,
+     *            returns alone with CSTONE_E_HIP / CSTONE_E_CAPACITY while the others wait in the all_to_all_v.  The owner sorts them stably by label (source-rank order is kept) and
+     *            combines in that order about r_ref, the position of its particle with that id: s = fold(r_p - r_ref),
+     *            M += M_p, S += S_p + M_p s, Q += Q_p + 2 s.S_p + M_p |s|^2, P += P_p, n += n_p; WIDE if a partial is
+     *            wide or some |s_a| >= T(0.25) L_a (conservative: while clear, every member lies within half a box of
+     *            r_ref).  Then the filter by n and the results as above.  No reply travels.
+     *            One rank: no collective, r_p = r_ref, s = 0 -- with min_members <= 1 the bits are those of
+     *            fof_group_properties on the catalogue of the same labels (a catalogue filtered by min_members > 1 lists
+     *            fewer members, the group edges fall on other lanes and the sums may differ in the last place).
+     * ------------------------------------------------------------------------------------------- */
+#define CSTONE_FOF_GROUP_WIDE 0x1u
+#define CSTONE_FOF_GROUP_MASSLESS 0x2u
+    int cstone_hip_fof_group_properties(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
+                                        const void* z, const void* m, const void* vx, const void* vy, const void* vz,
+                                        const cstone_box* box_host, const uint32_t* group_offsets, const uint32_t* members,
+                                        uint32_t num_groups, void* mass, void* center, void* velocity, void* radius,
+                                        uint32_t* flags);
+    int cstone_hip_domain_fof_properties(cstone_hip_domain* dom, const void* x, const void* y, const void* z, const void* m,
+                                         int mass_bits, const void* vx, const void* vy, const void* vz,
+                                         const uint32_t* group_offsets, const uint32_t* members, uint32_t num_groups,
+                                         void* mass, void* center, void* velocity, void* radius, uint32_t* flags);
+    int cstone_hip_domain_mr_fof_catalog(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z, const void* m,
+                                         int mass_bits, const void* vx, const void* vy, const void* vz, const uint64_t* labels,
+                                         uint64_t min_members, size_t capacity, uint64_t* group_labels, uint64_t* group_sizes,
+                                         void* mass, void* center, void* velocity, void* radius, uint32_t* flags,
+                                         uint32_t* num_groups_host);
 
 #ifdef __cplusplus
 }
