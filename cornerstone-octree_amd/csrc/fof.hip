@@ -1,10 +1,13 @@
 // Friends-of-friends groups on gfx950: particles closer than a linking length b are friends, groups are the connected
 // components of that relation.  The rule is stated in include/cstone_hip.h, cstone_hip_friends_of_friends: i and j of the
-// target range are linked iff cstone_hip_find_neighbors at ext = 1 reports j for i when h[i] = T(0.5) * T(b) -- the same
-// walk (cstone_hip::traverseNeighborsH), the same d^2, the same strict <, compiled with -ffp-contract=off like
-// neighbors.hip --, so a brute force over all pairs in the coordinate type plus any union-find reproduces the labels with
-// ==.  The relation is symmetric (b below half of every periodic edge is enforced), so a pair is united once, by the lane
-// of the larger index.
+// target range are linked iff cstone_hip_find_neighbors at ext = 1 reports j for i OR i for j when h = T(0.5) * T(b) -- the
+// same walk (cstone_hip::traverseNeighborsH), the same d^2, the same strict <, compiled with -ffp-contract=off like
+// neighbors.hip.  The pair test is symmetric (b below half of every periodic edge is enforced), the walk is not quite: a
+// pair within rounding of b across a cell face can be pruned by the node test from one side and reported from the other
+// (tests/test_face_pairs.py).  So every lane unites its target with EVERY reported j of the range, not only with the
+// smaller ones: the relation is the symmetric closure of the walk's and does not depend on how the particles are numbered.
+// Wherever no such pair is pruned from both sides this is the brute force over all pairs in the coordinate type, and any
+// union-find reproduces the labels with ==.
 //
 // The forest is the label array itself (union_find.hpp: parent[v] <= v, parent[v] in v's component).  Four passes:
 //   init     labels[k] = first + k
@@ -80,11 +83,13 @@ __global__ __launch_bounds__(FOF_BLOCK) void fofLinkKernel(const T* __restrict__
     const DeviceParents ops{parent, first};
     uint32_t root = i; // the root of i's tree as last seen: every find of this lane starts there, not at i
     bool gaveUp   = false;
-    // j < i: the relation is symmetric, the lane of the larger index makes the union; j < first: not a target, it links
-    // nothing (and has no entry in parent).  j < i < last.
+    // every reported j of the range, whichever of i and j is larger: the walk of j may have pruned i's leaf by a rounding
+    // of its node test (above), and ufUnite hooks the larger root under the smaller whatever the order.  A pair that both
+    // walks report is united twice; the second union finds equal roots and writes nothing.  j outside [first, last) is
+    // not a target: it links nothing and has no entry in parent.
     auto link = [&](uint32_t j, T, T, T, T)
     {
-        if (j < i && j >= first) root = ufUnite(ops, root, j, ufRetryCap, &gaveUp);
+        if (j >= first && j < last) root = ufUnite(ops, root, j, ufRetryCap, &gaveUp);
     };
     (void)cstone_hip::traverseNeighborsH(valid, i, x, y, z, hi, tree, box, 1.0f, stacks[wave], errors, link);
     if (valid) ufCompress(ops, i, root);

@@ -560,6 +560,10 @@ extern "C"
      * (R/tree/octree.hpp:297-317).  For i in [first,last): counts[i-first] = number of j != i with
      * |r_i - r_j|^2 < (2 h_i)^2 (minimum image if periodic); the first ngmax are stored row-major in
      * neighbors[(i-first)*ngmax + k] in the reference's CPU traversal order.
+     * As in the reference, a neighbour within rounding of 2 h_i across a cell face may be MISSING: the walk descends into a
+     * node when its node test passes (|c - r_i| - size per axis, folded, clamped at 0, dx*dx + (dy*dy + dz*dz) <
+     * 4 h_i^2 ext^2, products not fused), and that distance to the node can come out a rounding above the distance to a
+     * particle on the node's face.  The lists are the reference's, entry for entry, there too (tests/test_face_pairs.py).
      * ------------------------------------------------------------------------------------------- */
     int cstone_hip_find_neighbors(cstone_hip_ctx* ctx, int real_bits, const void* x, const void* y, const void* z,
                                   const void* h, uint32_t first, uint32_t last, const cstone_box* box_host,
@@ -1155,15 +1159,19 @@ extern "C"
      * reference has no such call; the rule below is this library's, stated so that a restatement reproduces it bit for bit.
      *
      *     T = coordinate type, hi = T(0.5) * T(linking_length).  Particles i != j of [first, last) are LINKED iff
-     *     cstone_hip_find_neighbors at ext = 1 reports j as a neighbour of i when h[i] = hi:
+     *     cstone_hip_find_neighbors at ext = 1 with every h = hi reports j as a neighbour of i OR i as a neighbour of j:
      *         d2 = dx*dx + dy*dy + dz*dz      -- left fold, products not fused, dx = x_j - x_i after the walk's periodic fold
-     *         linked iff d2 < T(4) * hi * hi  -- strict
+     *         reported iff d2 < T(4) * hi * hi (strict) and the walk reaches the other particle's leaf (below)
      *     A particle outside [first, last) (a halo, say) links nothing and bridges nothing.
      *
-     * The relation is symmetric while b is below half of every periodic box edge (a target whose sphere lies inside the box
+     * The pair test is symmetric while b is below half of every periodic box edge (a target whose sphere lies inside the box
      * skips the fold, and for such a pair the fold is the identity), so  linking_length >= 0.5 * (lim[2d+1] - lim[2d])  on a
-     * periodic axis d is CSTONE_E_ARG, as are linking_length <= 0 and a NaN.  The kernel then unites a pair once, from the
-     * lane of the larger index.
+     * periodic axis d is CSTONE_E_ARG, as are linking_length <= 0 and a NaN.  The WALK is not quite symmetric: a pair within
+     * rounding of b across a cell face can be pruned by the node test of one particle's walk and reported by the other's (see
+     * cstone_hip_find_neighbors).  The link pass therefore unites a target with every particle its walk reports, whichever
+     * index is larger: the relation is the symmetric closure of the walk's, and the groups do not depend on the numbering
+     * of the particles.  Wherever no pair within b is pruned from BOTH sides -- no case is known -- this is the brute force
+     * over all pairs with the d2 above.
      *
      * labels[i - first]      the LOWEST particle index (absolute, in [first, last)) among the members of i's group; a particle
      *                        without a friend labels itself.  The array doubles as the parent array of a lock-free

@@ -3,7 +3,8 @@
 The restatement of friends-of-friends across ranks works on what every rank holds after a sync -- its arrays with the
 halos, and for every entry the particle's global id, i.e. its position in the global SFC order: local components by the
 brute force of tests/fof_support.py over EVERYTHING present on the rank, then rounds of lower / exchange until no rank
-changes an assigned label."""
+changes an assigned label.  The brute force is what the ranks' walks give wherever no pair within b is pruned by a node
+test from both sides (tests/fof_support.py); the cloud "faces" puts that to the test across a rank boundary."""
 import numpy as np
 
 import fof_support as fs
@@ -45,8 +46,38 @@ CLOUDS = {  # name: (coordinate type, boundary conditions)
 }
 
 
+FACES_N, FACES_SHIFT = 1200, 0.1
+
+
+def faces_cloud():
+    """600 pairs across the x faces of the level-3 cells of the anisotropic open box (tests/face_support.py), every pair
+    0.1 cell edges apart up to the rounding of its coordinates, and b = twice the median of the pairs' threshold h: about
+    half of the pairs are linked, every one of them within a few ulp of b, and hardly any particle has a third one
+    within b -- a group IS its pair's own link.  Particles 2p and 2p + 1 are a pair; the last two particles sit in two
+    opposite corners of the box, so that the limits fitted to an open domain are the box's and the faces stay faces"""
+    import face_support as fa
+    from helpers import Box
+
+    x, y, z, _, _ = fa.face_cloud(np.float64, fa.ANISO, (0, 0, 0), axis_mix=False, n=FACES_N, edge_every=0,
+                                  shift=(FACES_SHIFT, FACES_SHIFT))
+    x, y, z = [np.concatenate([a, fa.ANISO[2 * d:2 * d + 2]]) for d, a in enumerate((x, y, z))]
+    even = np.arange(0, FACES_N, 2)
+    h = fa.threshold_h(fs.stub_case(x, y, z, 1.0, Box(fa.ANISO, (0, 0, 0))), even, even + 1)
+    return [x, y, z], 2.0 * float(np.sort(h)[h.size // 2])
+
+
+def cloud_limits(name):
+    """the box a domain is made with for the cloud"""
+    import face_support as fa
+
+    return list(map(float, fa.ANISO)) if name == "faces" else [0.0, 1.0] * 3
+
+
 def cloud(name):
-    """((x, y, z), b, bc)"""
+    """((x, y, z), b, bc).  "faces" is not among CLOUDS: it runs on two ranks only (tests/test_face_pairs.py)"""
+    if name == "faces":
+        coords, b = faces_cloud()
+        return coords, b, (0, 0, 0)
     T, bc = CLOUDS[name]
     (x, y, z), b = serpentine_cloud() if name == "serpentine" else uniform_cloud(T)
     return (x, y, z), b, bc

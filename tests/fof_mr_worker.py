@@ -2,7 +2,8 @@
 tests/fof_mr_support.py, checked on rank 0 against the brute force over the WHOLE cloud and the numpy restatement of the
 rounds.  Started by `python -m torch.distributed.run`; the ranks talk over gloo and share the one GPU.  Every particle
 carries its index in the generated cloud as a property; the sync uses h = 0.6 b and a halo factor of 1, so the halos
-reach 1.2 b.  Rank 0 prints one line `FOF_MR_RESULT {json}`.
+reach 1.2 b.  Rank 0 prints one line `FOF_MR_RESULT {json}`.  Cloud names on the command line replace the default set
+(tests/test_face_pairs.py runs "faces" that way).
 
 A failed check is recorded and the rank goes on, so that no rank waits in a collective for one that has stopped."""
 import ctypes as C
@@ -38,12 +39,12 @@ class Run:
     def fail(self, what, text):
         self.bad.append(f"rank {self.rank}, {what}: {text}")
 
-    def domain(self, rb, bc, owner_side):
+    def domain(self, rb, bc, owner_side, lim=None):
         import cstone_amd
         from cstone_amd.distributed import NativeDistributedDomain
 
         mode = NativeDistributedDomain.HALOS_OWNER_SIDE if owner_side else None  # (None: the locally essential tree)
-        return NativeDistributedDomain(self.hip, cstone_amd.HILBERT, 64, rb, 64, 16, [0.0, 1.0] * 3, bc, halo_mode=mode)
+        return NativeDistributedDomain(self.hip, cstone_amd.HILBERT, 64, rb, 64, 16, lim or [0.0, 1.0] * 3, bc, halo_mode=mode)
 
     def sync(self, dom, coords, h_value):
         """this rank's share of the cloud (drawn at random) through a sync; the cloud index follows as a property"""
@@ -122,8 +123,21 @@ class Run:
                 self.fail(what, f"rank {q}: the restated rounds do not end at the brute force's labels")
             if p["rounds"] != model_rounds:
                 self.fail(what, f"rank {q}: {p['rounds']} rounds, the restatement makes {model_rounds}")
-        return dict(groups=ref_ng, largest=int(ref_sizes.max()), rounds=int(parts[0]["rounds"]), model_rounds=model_rounds,
+        figs = dict(groups=ref_ng, largest=int(ref_sizes.max()), rounds=int(parts[0]["rounds"]), model_rounds=model_rounds,
                     halos=[int(p["x"].size - (p["end"] - p["start"])) for p in parts])
+        if name == "faces":
+            # the fitted limits are the box's (the faces are faces of the domain's cells); the pairs 2p, 2p + 1 that the
+            # brute force puts into one group, and those of them whose two particles belong to different ranks
+            if not np.array_equal(np.asarray(parts[0]["lim"]), np.asarray(ms.cloud_limits(name))):
+                self.fail(what, f"the domain's limits {list(parts[0]['lim'])} are not the box's")
+            owner = np.empty(n, dtype=np.int64)
+            for q, p in enumerate(parts):
+                owner[p["index"][p["start"]:p["end"]]] = q
+            even = np.arange(0, ms.FACES_N, 2)
+            joined = ref_labels[gid[even]] == ref_labels[gid[even + 1]]
+            figs.update(pairs=int(even.size), pairs_joined=int(joined.sum()),
+                        joined_across_ranks=int((joined & (owner[even] != owner[even + 1])).sum()))
+        return figs
 
     def one_rank_equals_the_single_rank_call(self, name, dom, r, b, res):
         """world of one rank: labels - start_index == cstone_hip_friends_of_friends on the assigned range of the same arrays"""
@@ -144,7 +158,7 @@ class Run:
         coords, b, bc = ms.cloud(name)
         T = coords[0].dtype.type
         what = name + (", owner-side halos" if owner_side else "")
-        dom = self.domain(coords[0].itemsize * 8, bc, owner_side)
+        dom = self.domain(coords[0].itemsize * 8, bc, owner_side, ms.cloud_limits(name))
         self.refused(dom, None, b, f"{what}, a call before the first sync")
 
         # ---- a sync whose halos do not reach b: h = 0.4 b
@@ -191,10 +205,14 @@ def main():
     run = Run(cstone_amd.Context(0), rank, P)
     figs = {}
     try:
-        for name in ms.CLOUDS:
-            figs[name] = run.cloud(name)
-        # the other way of finding halos keeps its radii elsewhere and exchanges halos along other routes
-        figs[OWNER_SIDE] = run.cloud("uniform-open", owner_side=True)
+        if len(sys.argv) > 1:  # the clouds named on the command line only
+            for name in sys.argv[1:]:
+                figs[name] = run.cloud(name)
+        else:
+            for name in ms.CLOUDS:
+                figs[name] = run.cloud(name)
+            # the other way of finding halos keeps its radii elsewhere and exchanges halos along other routes
+            figs[OWNER_SIDE] = run.cloud("uniform-open", owner_side=True)
     except Exception as e:  # (the other ranks may now wait in a collective: the launcher's timeout ends them)
         import traceback
 

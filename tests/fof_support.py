@@ -1,5 +1,10 @@
 """Shapes and the plain reference of tests/test_fof.py (host side only: numpy and plain Python, no scipy).
 
+The rule of cstone_hip_friends_of_friends: i and j of the target range are linked iff the walk of either reports the
+other at h = T(0.5) * T(b).  That is the brute force wherever the walk prunes no pair within b (a pair within rounding of
+b across a cell face can be pruned by the node test from one side: tests/face_support.py, tests/test_face_pairs.py);
+the shapes here assert that they are of that kind (test_brute_force_is_symmetric_and_equals_the_oracles_walk).
+
 The reference: the brute force of tests/neighbors_support.py (Case.pair_table: all pairs in the coordinate type,
 d2 = dx*dx + dy*dy + dz*dz left to right, products not fused, the walk's periodic fold, strict <) at h = T(0.5) * T(b),
 restricted to the target range, followed by a plain sequential union-find that labels every particle with the lowest

@@ -2,10 +2,12 @@
 particles closer than a linking length b are friends, groups are the connected components, the label of a particle is the
 lowest index of its group.
 
-The reference is the brute force of tests/fof_support.py: all pairs in the coordinate type with the d2 expression and the
-fold of tests/neighbors_support.py at h = T(0.5) * T(b), then a plain sequential union-find.  The CPU tests establish that
-it may serve -- the link matrix is symmetric, and the labels built from the oracle's WALK at that h (the walk the kernel
-makes) are the same -- and that every shape has the property it is here for.  The GPU tests compare labels, sizes, the
+The rule: linked iff the walk of either particle reports the other.  The reference is the brute force of
+tests/fof_support.py: all pairs in the coordinate type with the d2 expression and the fold of tests/neighbors_support.py at
+h = T(0.5) * T(b), then a plain sequential union-find.  The CPU tests establish that it may serve on these shapes -- the
+link matrix is symmetric, and the labels built from the oracle's WALK at that h (the walk the kernel makes) are the same:
+no pair within b is pruned by a node test here; tests/test_face_pairs.py has the clouds where some are -- and that every
+shape has the property it is here for.  The GPU tests compare labels, sizes, the
 number of groups and the catalogue with ==, on outputs pre-filled with a sentinel; the sticky error word must be 0 (a
 union that gave up at its retry cap sets it).  The union-find itself (csrc/union_find.hpp) runs under threads and
 sanitizers in a stand-alone host program, tests/union_find_check.cpp."""
@@ -140,8 +142,9 @@ def _tsan_links(tmp_path):
 @pytest.mark.parametrize("build", ["plain", "asan_ubsan", "tsan"])
 def test_union_find_on_host_threads(tmp_path, build):
     """csrc/union_find.hpp with std::atomic: 8 threads unite the edges of a path, a star, two cliques with and without a
-    bridge and random graphs in shuffled order; every vertex ends at the minimum of its component, no union gives up, and
-    a compare-and-swap that always fails ends at the retry cap and is reported"""
+    bridge and random graphs in shuffled order, each also with every edge in both orientations and some twice (the link
+    pass unites a pair from either side); every vertex ends at the minimum of its component, no union gives up, and a
+    compare-and-swap that always fails ends at the retry cap and is reported"""
     flags = {"plain": [], "asan_ubsan": ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"],
              "tsan": ["-fsanitize=thread"]}[build]
     if build == "tsan" and not _tsan_links(tmp_path):

@@ -1,7 +1,10 @@
 // The lock-free union-find of the friends-of-friends finder (cornerstone-octree_amd/csrc/union_find.hpp) on the host: the
 // text the link kernel runs, with std::atomic for the device atomics.  Several threads unite the edges of known graphs in
 // shuffled order; afterwards every vertex must end at the minimum index of its component (computed by a plain sequential
-// search), the invariant parent[v] <= v must hold, and no union may have given up.  A compare-and-swap that always fails
+// search), the invariant parent[v] <= v must hold, and no union may have given up.  Every graph runs twice: with each edge
+// once, in a random orientation, and with each edge in BOTH orientations plus a second copy of every third one -- what the
+// link kernel hands over now that a pair is united from either side (a pair that both walks report comes twice, (i, j)
+// from the lane of i and (j, i) from the lane of j, usually at the same time).  A compare-and-swap that always fails
 // shows that the retry cap ends the loop and is reported.  Build plain, with -fsanitize=address,undefined and with
 // -fsanitize=thread: this is where a lost update or a retry that does not end is found.
 //
@@ -79,9 +82,18 @@ static std::vector<uint32_t> sequentialLabels(uint32_t first, uint32_t n, const 
 
 static int failures = 0;
 
-static void check(const std::string& name, uint32_t first, uint32_t n, std::vector<Edge> edges, int threads, uint32_t seed,
-                  bool keepRoot)
+static void checkOnce(const std::string& name, uint32_t first, uint32_t n, std::vector<Edge> edges, int threads,
+                      uint32_t seed, bool keepRoot, bool doubled)
 {
+    if (doubled)
+    {
+        const size_t m = edges.size();
+        for (size_t e = 0; e < m; ++e)
+        {
+            edges.push_back({edges[e].second, edges[e].first});
+            if (e % 3 == 0) edges.push_back(edges[e]);
+        }
+    }
     std::unique_ptr<std::atomic<uint32_t>[]> parent(new std::atomic<uint32_t>[n]);
     for (uint32_t k = 0; k < n; ++k)
         parent[k].store(first + k);
@@ -131,9 +143,16 @@ static void check(const std::string& name, uint32_t first, uint32_t n, std::vect
     if (bad || broken || gaveUp.load())
     {
         ++failures;
-        std::printf("UNION_FIND FAIL %s: %u wrong labels, %u parents above their vertex, %d threads gave up\n", name.c_str(),
-                    bad, broken, gaveUp.load());
+        std::printf("UNION_FIND FAIL %s%s: %u wrong labels, %u parents above their vertex, %d threads gave up\n", name.c_str(),
+                    doubled ? " (edges doubled)" : "", bad, broken, gaveUp.load());
     }
+}
+
+static void check(const std::string& name, uint32_t first, uint32_t n, const std::vector<Edge>& edges, int threads,
+                  uint32_t seed, bool keepRoot)
+{
+    checkOnce(name, first, n, edges, threads, seed, keepRoot, false);
+    checkOnce(name, first, n, edges, threads, seed + 500, keepRoot, true);
 }
 
 int main(int argc, char** argv)
@@ -220,6 +239,8 @@ int main(int argc, char** argv)
         }
     }
     if (failures) return 1;
-    std::printf("UNION_FIND OK: %d graphs, %d threads, retry cap checked\n", graphs, threads);
+    std::printf("UNION_FIND OK: %d graphs, %d threads, retry cap checked; every graph also with its edges reversed and "
+                "duplicated\n",
+                graphs, threads);
     return 0;
 }
