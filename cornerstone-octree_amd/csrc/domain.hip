@@ -140,6 +140,9 @@ struct DomainBase
                               const void* vy, const void* vz, const uint32_t* groupOffsets, const uint32_t* members,
                               uint32_t numGroups, void* mass, void* center, void* velocity, void* radius,
                               uint32_t* flags) = 0;
+    virtual int sphereProfiles(const void* x, const void* y, const void* z, const void* w, int massBits, const void* queryCenters,
+                               const void* queryScale, uint32_t numQueries, const double* edgesHost, int numBins,
+                               uint64_t* counts, double* sums, uint32_t* flags) = 0;
     virtual void stats(cstone_hip_domain_stats* out)     = 0;
 };
 
@@ -291,6 +294,17 @@ public:
         if (firstCall_ || fLeaves_ < 1) return fail(ctx_, CSTONE_E_ARG, "domain_fof_properties: no sync yet");
         return cstone_hip_fof_group_properties(ctx_, rb, massBits, x, y, z, m, vx, vy, vz, &box_, groupOffsets, members,
                                                numGroups, mass, center, velocity, radius, flags);
+    }
+
+    //! cstone_hip_sphere_profiles on the octree, the box and [start_index, end_index) of the last sync
+    int sphereProfiles(const void* x, const void* y, const void* z, const void* w, int massBits, const void* queryCenters,
+                       const void* queryScale, uint32_t numQueries, const double* edgesHost, int numBins, uint64_t* counts,
+                       double* sums, uint32_t* flags) override
+    {
+        if (firstCall_ || fLeaves_ < 1) return fail(ctx_, CSTONE_E_ARG, "domain_sphere_profiles: no sync yet");
+        return cstone_hip_sphere_profiles(ctx_, rb, massBits, x, y, z, w, startIndex_, endIndex_, &box_, fChild_.as<int32_t>(),
+                                          fItl_.as<int32_t>(), layout_.as<uint32_t>(), fCenters_.p, fSizes_.p, queryCenters,
+                                          queryScale, numQueries, edgesHost, numBins, counts, sums, flags);
     }
 
     /*! Domain::updateExpansionCenters (R/domain/domain.hpp:415-421) on one rank = FocusedOctree::updateCenters without its
@@ -1249,6 +1263,16 @@ int cstone_hip_domain_fof_properties(cstone_hip_domain* dom, const void* x, cons
     if (!dom) return CSTONE_E_ARG;
     return dom->impl->fofProperties(x, y, z, m, mass_bits, vx, vy, vz, group_offsets, members, num_groups, mass, center,
                                     velocity, radius, flags);
+}
+
+int cstone_hip_domain_sphere_profiles(cstone_hip_domain* dom, const void* x, const void* y, const void* z, const void* w,
+                                      int mass_bits, const void* query_centers, const void* query_scale,
+                                      uint32_t num_queries, const double* edges_host, int num_bins, uint64_t* counts,
+                                      double* sums, uint32_t* flags)
+{
+    if (!dom) return CSTONE_E_ARG;
+    return dom->impl->sphereProfiles(x, y, z, w, mass_bits, query_centers, query_scale, num_queries, edges_host, num_bins,
+                                     counts, sums, flags);
 }
 
 int cstone_hip_domain_view_get(cstone_hip_domain* dom, cstone_hip_domain_view* out)

@@ -32,6 +32,7 @@
 #include "device_keys.hpp"
 #include "fof_mr.hpp"
 #include "fof_props.hpp"
+#include "sphere.hpp"
 #include "host_tree.hpp"
 #include "let.hpp"
 #include "resort.hpp"
@@ -374,6 +375,9 @@ struct MrBase
                            const void* vy, const void* vz, const uint64_t* labels, uint64_t minMembers, size_t capacity,
                            uint64_t* groupLabels, uint64_t* groupSizes, void* mass, void* center, void* velocity,
                            void* radius, uint32_t* flags, uint32_t* numGroupsHost) = 0;
+    virtual int sphereProfiles(const void* x, const void* y, const void* z, const void* w, int massBits, const void* queryCenters,
+                               const void* queryScale, uint32_t numQueries, const double* edgesHost, int numBins,
+                               uint64_t* counts, double* sums, uint32_t* flags) = 0;
     virtual int multipoles(const void** out, int32_t* numNodes)                           = 0;
     virtual int octupoles(const void** out, int32_t* numNodes)                            = 0;
     virtual int view(cstone_hip_domain_mr_view* out)                                     = 0;
@@ -929,6 +933,86 @@ public:
             return fail(ctx_, CSTONE_E_CAPACITY, "domain_mr_fof_catalog: %u groups, capacity %zu", kept, capacity);
         return fofFinishCombined(ctx_, rb, nv == 3, view_.box, combined, keep, pos, ownRuns[0],
                                  FofGroupOut{mass, center, velocity, radius, flags, groupLabels, groupSizes});
+    }
+
+    /*! Sphere profiles over the particles of all ranks (cstone_hip_domain_mr_sphere_profiles; the rule: include/
+     *  cstone_hip.h).  Every rank bins its assigned range on its own octree into the caller's arrays; one all-gather of
+     *  {status, Q, NB, w given} lets every rank fail together; one all-reduce of {counts as doubles, sums} follows. */
+    int sphereProfiles(const void* x, const void* y, const void* z, const void* w, int massBits, const void* queryCenters,
+                       const void* queryScale, uint32_t numQueries, const double* edgesHost, int numBins, uint64_t* counts,
+                       double* sums, uint32_t* flags) override
+    {
+        // ---- what is the same on every rank: refused before any collective
+        if (firstCall_) return fail(ctx_, CSTONE_E_ARG, "domain_mr_sphere_profiles: no sync yet");
+        if (!sphereEdgesOk(edgesHost, numBins)) return fail(ctx_, CSTONE_E_ARG, "domain_mr_sphere_profiles: bad edges");
+        if (w && massBits != 32 && massBits != 64) return fail(ctx_, CSTONE_E_ARG, "domain_mr_sphere_profiles: bad mass_bits");
+        const uint32_t si = view_.start_index, ei = view_.end_index, na = ei - si;
+        cstone_hip_domain_mr_octree t{};
+        if (P_ == 1)
+        {
+            if (numQueries == 0) return CSTONE_OK;
+            CS_TRY(octree(&t));
+            return cstone_hip_sphere_profiles(ctx_, rb, massBits, x, y, z, w, si, ei, &view_.box, t.child_offsets,
+                                              t.internal_to_leaf, t.layout, t.centers, t.sizes, queryCenters, queryScale,
+                                              numQueries, edgesHost, numBins, counts, sums, flags);
+        }
+
+        // ---- rank-local trouble: collected, not returned
+        enum : uint64_t { FINE = 0, NULL_ARRAY = 1, NO_MEMORY = 2, LOCAL_STEP = 3, MISMATCH = 4 };
+        enum : uint64_t { W_NONE = 0, W_GIVEN = 1, W_ANY = 2 }; // a rank without particles goes with the others
+        const size_t cells = size_t(numQueries) * size_t(numBins);
+        uint64_t trouble   = FINE;
+        if (numQueries && (!queryCenters || !counts || (w && !sums) || (na && (!x || !y || !z)))) trouble = NULL_ARRAY;
+        else if (sphereBuf_.ensure(ctx_, std::max<size_t>(2 * cells * sizeof(double), 256))) trouble = NO_MEMORY;
+        else if (na && octree(&t)) trouble = LOCAL_STEP;
+        const uint64_t row[4] = {trouble, numQueries, uint64_t(numBins), na ? (w ? W_GIVEN : W_NONE) : (w ? W_GIVEN : W_ANY)};
+        std::vector<uint64_t> rows(4 * size_t(P_));
+        CS_TRY(cstone_hip_upload(ctx_, gatherRow(), row, sizeof row));
+        CS_TRY(callComm(comm_.all_gather(comm_.user, gatherRow(), gatherRecv(), sizeof row), "all_gather (sphere profiles)"));
+        CS_TRY(copyToHost(ctx_, rows.data(), gatherRecv(), rows.size() * 8));
+        uint64_t wMode = W_ANY;
+        for (int p = 0; p < P_; ++p)
+        {
+            const uint64_t* r = rows.data() + 4 * size_t(p);
+            uint64_t st       = r[0];
+            if (st == FINE && (r[1] != rows[1] || r[2] != rows[2])) st = MISMATCH;
+            if (st == FINE && r[3] != W_ANY)
+            {
+                if (wMode == W_ANY) wMode = r[3];
+                else if (wMode != r[3]) st = MISMATCH;
+            }
+            if (st == FINE) continue;
+            if (st == MISMATCH)
+                return fail(ctx_, CSTONE_E_ARG,
+                            "domain_mr_sphere_profiles: the ranks disagree on num_queries, num_bins or whether there is a w "
+                            "(rank %d; refused on every rank)", p);
+            if (p != rank_)
+                return fail(ctx_, CSTONE_E_INTERNAL, "domain_mr_sphere_profiles: rank %d reported a failure (refused on every rank)", p);
+            static const char* const why[] = {"", "null array", "out of device memory", "no octree"};
+            return fail(ctx_, st == NO_MEMORY ? CSTONE_E_HIP : st == LOCAL_STEP ? CSTONE_E_INTERNAL : CSTONE_E_ARG,
+                        "domain_mr_sphere_profiles: %s (refused on every rank)", why[st]);
+        }
+        if (numQueries == 0) return CSTONE_OK;
+        const bool globalW = wMode == W_GIVEN;
+
+        // ---- the local profiles, into the caller's arrays.  A rank without particles has nothing to read: its empty
+        //      range zeroes the rows and sets the flags, and the operand itself stands in for the arrays it may not have
+        const void* dummy = sphereBuf_.p;
+        auto nz           = [&](const void* ptr) { return ptr ? ptr : dummy; };
+        CS_TRY(cstone_hip_sphere_profiles(ctx_, rb, massBits, nz(x), nz(y), nz(z), w, si, ei, &view_.box,
+                                          static_cast<const int32_t*>(nz(t.child_offsets)),
+                                          static_cast<const int32_t*>(nz(t.internal_to_leaf)),
+                                          static_cast<const uint32_t*>(nz(t.layout)), nz(t.centers), nz(t.sizes), queryCenters,
+                                          queryScale, numQueries, edgesHost, numBins, counts, sums, flags));
+        // ---- one all-reduce: {counts as doubles, sums}
+        double* buf = sphereBuf_.as<double>();
+        if (globalW && !w) CS_HIP(ctx_, hipMemsetAsync(buf + cells, 0, cells * sizeof(double), ctx_->stream));
+        spherePackRows(ctx_, counts, w ? sums : nullptr, cells, buf);
+        CS_TRY(callComm(comm_.all_reduce(comm_.user, buf, (globalW ? 2 : 1) * cells, 0, 0), "all_reduce (sphere profiles)"));
+        sphereUnpackRows(ctx_, buf, cells, counts, globalW ? sums : nullptr);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess)
+            return fail(ctx_, CSTONE_E_HIP, "domain_mr_sphere_profiles: %s", hipGetErrorString(e));
+        return CSTONE_OK;
     }
 
     int multipoles(const void** out, int32_t* numNodes) override
@@ -2394,6 +2478,7 @@ private:
     std::vector<uint64_t> fofOffset_;
     int fofOffsetSync_ = -1;
     DevBuf catWork_, catPart_, catRecv_, catScal_;
+    DevBuf sphereBuf_; // the operand of the all-reduce of sphereProfiles: {counts as doubles, sums}
     Out out_[2];
     int cur_ = 0;
 };
@@ -2540,6 +2625,16 @@ int cstone_hip_domain_mr_fof_catalog(cstone_hip_domain_mr* dom, const void* x, c
     if (!dom) return CSTONE_E_ARG;
     return dom->impl->fofCatalog(x, y, z, m, mass_bits, vx, vy, vz, labels, min_members, capacity, group_labels, group_sizes,
                                  mass, center, velocity, radius, flags, num_groups_host);
+}
+
+int cstone_hip_domain_mr_sphere_profiles(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z,
+                                         const void* w, int mass_bits, const void* query_centers, const void* query_scale,
+                                         uint32_t num_queries, const double* edges_host, int num_bins, uint64_t* counts,
+                                         double* sums, uint32_t* flags)
+{
+    if (!dom) return CSTONE_E_ARG;
+    return dom->impl->sphereProfiles(x, y, z, w, mass_bits, query_centers, query_scale, num_queries, edges_host, num_bins,
+                                     counts, sums, flags);
 }
 
 int cstone_hip_domain_mr_multipoles_get(cstone_hip_domain_mr* dom, const void** multipoles, int32_t* num_nodes)

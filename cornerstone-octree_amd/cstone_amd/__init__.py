@@ -76,9 +76,16 @@ EXPORTS = [
     "cstone_hip_fof_lower_labels", "cstone_hip_domain_mr_fof",
     # the group catalogue: mass, centre, velocity, radius of every group (csrc/fof_props.hip, csrc/domain_mr.hip)
     "cstone_hip_fof_group_properties", "cstone_hip_domain_fof_properties", "cstone_hip_domain_mr_fof_catalog",
+    # sphere queries at arbitrary points: radial profiles and spherical-overdensity masses (csrc/sphere.hip)
+    "cstone_hip_sphere_profiles", "cstone_hip_spherical_overdensity", "cstone_hip_domain_sphere_profiles",
+    "cstone_hip_domain_mr_sphere_profiles",
 ]
 
 FOF_GROUP_WIDE, FOF_GROUP_MASSLESS = 0x1, 0x2  # CSTONE_FOF_GROUP_*: the flags of the group catalogue
+
+SPHERE_MAX_BINS = 64  # CSTONE_SPHERE_MAX_BINS
+# CSTONE_SPHERE_TOO_WIDE (profiles and overdensity), CSTONE_SO_NOT_REACHED, CSTONE_SO_UNRESOLVED (overdensity)
+SPHERE_TOO_WIDE, SO_NOT_REACHED, SO_UNRESOLVED = 0x1, 0x2, 0x4
 
 FOF_MR_DEFAULT_ROUNDS = 4096  # CSTONE_FOF_MR_DEFAULT_ROUNDS: what max_rounds = 0 means to cstone_hip_domain_mr_fof
 
@@ -151,7 +158,33 @@ def load_library():
     lib.cstone_hip_domain_mr_fof_catalog.restype = C.c_int
     lib.cstone_hip_domain_mr_fof_catalog.argtypes = ([C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 4 +
                                                      [C.c_uint64, C.c_size_t] + [C.c_void_p] * 7 + [C.POINTER(C.c_uint32)])
+    # sphere queries: (ctx, real_bits, mass_bits, x, y, z, w, first, last, box*, child_offsets, internal_to_leaf, layout,
+    # centers, sizes, query_centers, query_scale, num_queries, edges*, num_bins, counts, sums, flags); the finish: (ctx,
+    # real_bits, query_scale, num_queries, edges*, num_bins, sums, profile_flags, rho, r_delta, m_delta, flags); the
+    # domains': (domain, x, y, z, w, mass_bits, query_centers, query_scale, num_queries, edges*, num_bins, counts, sums, flags)
+    lib.cstone_hip_sphere_profiles.restype = C.c_int
+    lib.cstone_hip_sphere_profiles.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_uint32] * 2 +
+                                               [C.c_void_p] * 8 + [C.c_uint32, C.POINTER(C.c_double), C.c_int] +
+                                               [C.c_void_p] * 3)
+    lib.cstone_hip_spherical_overdensity.restype = C.c_int
+    lib.cstone_hip_spherical_overdensity.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_double),
+                                                      C.c_int, C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 3)
+    for fn in (lib.cstone_hip_domain_sphere_profiles, lib.cstone_hip_domain_mr_sphere_profiles):
+        fn.restype = C.c_int
+        fn.argtypes = ([C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 2 + [C.c_uint32, C.POINTER(C.c_double), C.c_int] +
+                       [C.c_void_p] * 3)
     return lib
+
+
+def sphere_edges(edges):
+    """(host array of C doubles, number of bins) of a sequence of bin edges, as the sphere calls take them"""
+    e = [float(v) for v in edges]
+    return (C.c_double * max(len(e), 1))(*e), len(e) - 1
+
+
+def _opt(t):
+    """data pointer of a tensor, or None"""
+    return None if t is None else t.data_ptr()
 
 
 def _torch():
@@ -662,6 +695,56 @@ class Context:
             _ptr(vz), C.cast(C.byref(box), C.c_void_p), _ptr(group_offsets), _ptr(members), ng, _ptr(mass), _ptr(center),
             _ptr(velocity), _ptr(radius), _ptr(flags)), "fof_group_properties")
         return mass, center, velocity, radius, flags
+
+    def sphere_profiles(self, x, y, z, w, first, last, box, octree, layout, centers, sizes, query_centers, edges,
+                        query_scale=None, num_queries=None, counts=None, sums=None, flags=None, real_bits=None,
+                        mass_bits=None):
+        """cstone_hip_sphere_profiles: for every query centre (query_centers [Q, 3], the coordinates' type) the particles
+        of [first, last) counted, and their weights w (float32 / float64 tensor or None) summed in float64, in the
+        half-open distance bins [s * edges[b], s * edges[b + 1]), s = query_scale[q] (or 1).  edges: NB + 1 host numbers.
+        Returns (counts [Q, NB] int64, sums [Q, NB] float64 or None without w, flags [Q] int32 holding SPHERE_TOO_WIDE).
+        The rule: include/cstone_hip.h.  counts, sums, flags: tensors to write into instead of new ones; num_queries,
+        real_bits, mass_bits: overrides of what the tensors imply.  Asynchronous"""
+        torch = _torch()
+        e, nb = sphere_edges(edges)
+        nq = query_centers.shape[0] if num_queries is None else num_queries
+        dev = query_centers.device
+        rows = (nq, max(nb, 0))
+        if counts is None:
+            counts = torch.zeros(rows, dtype=torch.int64, device=dev)
+        if sums is None and w is not None:
+            sums = torch.zeros(rows, dtype=torch.float64, device=dev)
+        if flags is None:
+            flags = torch.zeros(nq, dtype=torch.int32, device=dev)
+        rb = query_centers.element_size() * 8 if real_bits is None else real_bits
+        mb = (w.element_size() * 8 if w is not None else 64) if mass_bits is None else mass_bits
+        self._chk(self.lib.cstone_hip_sphere_profiles(
+            self.h, rb, mb, _opt(x), _opt(y), _opt(z), _opt(w), first, last, C.cast(C.byref(box), C.c_void_p),
+            _opt(octree["child_offsets"]), _opt(octree["internal_to_leaf"]), _opt(layout), _opt(centers), _opt(sizes),
+            _opt(query_centers), _opt(query_scale), nq, e, nb, _opt(counts), _opt(sums), _opt(flags)), "sphere_profiles")
+        return counts, sums, flags
+
+    def spherical_overdensity(self, sums, edges, rho_threshold, query_scale=None, profile_flags=None, real_bits=64,
+                              num_queries=None, r_delta=None, m_delta=None, flags=None):
+        """cstone_hip_spherical_overdensity: (R_Delta [Q], M_Delta [Q], flags [Q]) from the sums [Q, NB] of a
+        sphere_profiles call with the same edges (edges[0] must be 0) and scales: the radius where the mean enclosed
+        density falls to rho_threshold, interpolated between the bin edges, and the mass inside; flags hold
+        SPHERE_TOO_WIDE (passed on), SO_NOT_REACHED, SO_UNRESOLVED.  real_bits: the type of query_scale.  Asynchronous"""
+        torch = _torch()
+        e, nb = sphere_edges(edges)
+        nq = sums.shape[0] if num_queries is None else num_queries
+        if query_scale is not None:
+            real_bits = query_scale.element_size() * 8
+        if r_delta is None:
+            r_delta = torch.zeros(nq, dtype=torch.float64, device=sums.device)
+        if m_delta is None:
+            m_delta = torch.zeros(nq, dtype=torch.float64, device=sums.device)
+        if flags is None:
+            flags = torch.zeros(nq, dtype=torch.int32, device=sums.device)
+        self._chk(self.lib.cstone_hip_spherical_overdensity(
+            self.h, real_bits, _opt(query_scale), nq, e, nb, _opt(sums), _opt(profile_flags), float(rho_threshold),
+            _opt(r_delta), _opt(m_delta), _opt(flags)), "spherical_overdensity")
+        return r_delta, m_delta, flags
 
     def compute_fixed_groups(self, first, last, group_size):
         torch = _torch()

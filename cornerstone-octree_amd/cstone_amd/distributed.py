@@ -427,6 +427,36 @@ class NativeDistributedDomain:
         g = ng.value
         return gl[:g], gs[:g], mass[:g], center[:g], (velocity[:g] if vel is not None else None), radius[:g], flags[:g]
 
+    def sphere_profiles(self, x, y, z, w, query_centers, edges, query_scale=None, num_queries=None, counts=None,
+                        sums=None, flags=None):
+        """cstone_hip_domain_mr_sphere_profiles (COLLECTIVE): the profiles of Context.sphere_profiles over the particles
+        of all ranks.  Every rank passes the same query_centers [Q, 3], query_scale [Q] or None and edges; x, y, z, w
+        (or None) are laid out like the result arrays of the last sync and read on the assigned range only.  Returns
+        (counts [Q, NB] int64, sums [Q, NB] float64 or None without w, flags [Q] int32), the same on every rank.
+        counts, sums, flags: tensors to write into instead of new ones; num_queries: override of query_centers' rows"""
+        torch = _torch()
+        import cstone_amd
+
+        e, nb = cstone_amd.sphere_edges(edges)
+        nq = query_centers.shape[0] if num_queries is None else num_queries
+        rows = (nq, max(nb, 0))
+        if counts is None:
+            counts = torch.zeros(rows, dtype=torch.int64, device=self.ctx.device)
+        if sums is None and w is not None:
+            sums = torch.zeros(rows, dtype=torch.float64, device=self.ctx.device)
+        if flags is None:
+            flags = torch.zeros(nq, dtype=torch.int32, device=self.ctx.device)
+        P = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        rc = self.ctx.lib.cstone_hip_domain_mr_sphere_profiles(self.h, P(x), P(y), P(z), P(w),
+                                                               w.element_size() * 8 if w is not None else 64,
+                                                               P(query_centers), P(query_scale), nq, e, nb, P(counts),
+                                                               P(sums), P(flags))
+        if rc != 0 and self.coll.error is not None:
+            err, self.coll.error = self.coll.error, None
+            raise err
+        self.ctx._chk(rc, "domain_mr_sphere_profiles")
+        return counts, sums, flags
+
     def multipoles(self):
         """(num_nodes, 8) multipoles of the focus tree as the last gravity() built them (a tensor that aliases the
         domain's array), or None"""

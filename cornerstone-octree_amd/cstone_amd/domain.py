@@ -211,6 +211,27 @@ class Domain:
         self.ctx._chk(rc, "domain_fof_properties")
         return mass, center, velocity, radius, flags
 
+    def sphere_profiles(self, x, y, z, w, query_centers, edges, query_scale=None):
+        """cstone_hip_domain_sphere_profiles: Context.sphere_profiles on the octree, the box and the particles
+        [start_index, end_index) of the last sync; x, y, z and w (or None) laid out like the sync's results.  Returns
+        (counts [Q, NB] int64, sums [Q, NB] float64 or None, flags [Q] int32)"""
+        import torch
+
+        from . import sphere_edges
+
+        e, nb = sphere_edges(edges)
+        nq = query_centers.shape[0]
+        dev = query_centers.device
+        counts = torch.zeros((nq, max(nb, 0)), dtype=torch.int64, device=dev)
+        sums = torch.zeros((nq, max(nb, 0)), dtype=torch.float64, device=dev) if w is not None else None
+        flags = torch.zeros(nq, dtype=torch.int32, device=dev)
+        P = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        rc = self.ctx.lib.cstone_hip_domain_sphere_profiles(self.h, P(x), P(y), P(z), P(w),
+                                                            w.element_size() * 8 if w is not None else 64, P(query_centers),
+                                                            P(query_scale), nq, e, nb, P(counts), P(sums), P(flags))
+        self.ctx._chk(rc, "domain_sphere_profiles")
+        return counts, sums, flags
+
     def reapply_sync(self, field):
         """Domain::reapplySync: field (n rows of the last sync's input, 1..32 bytes each) in the order of the result"""
         import torch

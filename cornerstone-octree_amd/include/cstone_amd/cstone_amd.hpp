@@ -779,6 +779,60 @@ void fofGroupPropertiesGpu(const T* x, const T* y, const T* z, const Tm* m, cons
                    "fofGroupPropertiesGpu");
 }
 
+//! the rows of a set of sphere queries: counts and sums are [numQueries][numBins], flags the CSTONE_SPHERE_* bits per query
+struct SphereProfileTable
+{
+    DeviceVector<std::uint64_t> counts;
+    DeviceVector<double> sums;
+    DeviceVector<unsigned> flags;
+    void resize(std::size_t numQueries, std::size_t numBins, bool weights)
+    {
+        counts.resize(numQueries * numBins), flags.resize(numQueries);
+        sums.resize(weights ? numQueries * numBins : 0);
+    }
+};
+
+/*! Radial profiles about arbitrary points (cstone_hip_sphere_profiles; the rule is stated in include/cstone_hip.h): for
+ *  every query centre (queryCenters: x, y, z per query, device) the particles of [first, last) are counted, and their
+ *  weights w (float or double, nullable) summed in double, in the half-open distance bins [s * edges[b], s * edges[b + 1])
+ *  with s = queryScale[q] (device, nullable: 1).  edges: numBins + 1 host values.  The table is resized.  Asynchronous. */
+template<class T, class Tw, class KeyType>
+void sphereProfilesGpu(const T* x, const T* y, const T* z, const Tw* w, LocalIndex first, LocalIndex last, const Box<T>& box,
+                       const OctreeNsView<T, KeyType>& tree, const T* queryCenters, const T* queryScale,
+                       std::size_t numQueries, const std::vector<double>& edges, SphereProfileTable& table)
+{
+    const int numBins = int(edges.size()) - 1;
+    table.resize(numQueries, std::size_t(std::max(numBins, 0)), w != nullptr);
+    Context::check(cstone_hip_sphere_profiles(Context::get(), detail::realBits<T>(), int(8 * sizeof(Tw)), x, y, z, w, first,
+                                              last, &box.pod(), tree.childOffsets, tree.internalToLeaf, tree.layout,
+                                              tree.centers, tree.sizes, queryCenters, queryScale, unsigned(numQueries),
+                                              edges.data(), numBins, table.counts.data(),
+                                              w ? table.sums.data() : nullptr, table.flags.data()),
+                   "sphereProfilesGpu");
+}
+
+//! what sphericalOverdensityGpu leaves: R_Delta, M_Delta and the CSTONE_SPHERE_TOO_WIDE / CSTONE_SO_* bits per query
+struct SphericalOverdensityTable
+{
+    DeviceVector<double> radius, mass;
+    DeviceVector<unsigned> flags;
+};
+
+/*! The spherical-overdensity radius and mass of every query from its profile (cstone_hip_spherical_overdensity): the
+ *  radius at which the mean enclosed density of the table's sums falls to rhoThreshold, interpolated linearly between the
+ *  bin edges, and the mass inside.  edges[0] must be 0.  queryScale as given to the profile call.  Asynchronous. */
+template<class T>
+void sphericalOverdensityGpu(const T* queryScale, std::size_t numQueries, const std::vector<double>& edges,
+                             const SphereProfileTable& table, double rhoThreshold, SphericalOverdensityTable& out)
+{
+    out.radius.resize(numQueries), out.mass.resize(numQueries), out.flags.resize(numQueries);
+    Context::check(cstone_hip_spherical_overdensity(Context::get(), detail::realBits<T>(), queryScale, unsigned(numQueries),
+                                                    edges.data(), int(edges.size()) - 1, table.sums.data(),
+                                                    table.flags.data(), rhoThreshold, out.radius.data(), out.mass.data(),
+                                                    out.flags.data()),
+                   "sphericalOverdensityGpu");
+}
+
 /*! The transport of the multi-rank Domain on a node of MI355X: RCCL, served from C++ inside libcstone_hip on the context's
  *  stream (csrc/comm_rccl.hip) -- replaces the MPI point-to-point exchanges of the reference
  *  (R/domain/domaindecomp_mpi_gpu.cuh:86-185, R/halos/exchange_halos_gpu.cuh:35-119).  One rank obtains the id
@@ -1053,6 +1107,18 @@ public:
         if (rc != CSTONE_E_CAPACITY) Context::check(rc, "MultiRankDomain::fofCatalog");
         *status = rc;
         return numGroups;
+    }
+    /*! Sphere profiles over the particles of ALL ranks (cstone_hip_domain_mr_sphere_profiles; collective): every rank
+     *  passes the same queries and edges and receives the same rows.  x, y, z, w (nullable): laid out like the result
+     *  arrays, read on the assigned range only.  counts, sums (nullable without w): numQueries * numBins, flags numQueries. */
+    template<class Tw>
+    void sphereProfiles(const T* x, const T* y, const T* z, const Tw* w, const T* queryCenters, const T* queryScale,
+                        unsigned numQueries, const double* edges, int numBins, std::uint64_t* counts, double* sums,
+                        unsigned* flags)
+    {
+        Context::check(cstone_hip_domain_mr_sphere_profiles(dom_, x, y, z, w, int(8 * sizeof(Tw)), queryCenters, queryScale,
+                                                            numQueries, edges, numBins, counts, sums, flags),
+                       "MultiRankDomain::sphereProfiles");
     }
     //! the multipoles of the focus tree that the last computeGravity built: 8 values of T per node (device), or null
     const T* multipoles() const
@@ -1539,6 +1605,40 @@ public:
         groupLabels.resize(numGroups), groupSizes.resize(numGroups);
         table.resize(numGroups, vx != nullptr);
         return numGroups;
+    }
+    /*! Radial profiles about arbitrary points over the particles [startIndex(), endIndex()) of the last sync
+     *  (cstone_hip_domain_sphere_profiles: sphereProfilesGpu on the domain's octree and box).  x, y, z and w (nullable) are
+     *  laid out like the result arrays; queryCenters holds x, y, z per query, queryScale (nullable) one scale per query. */
+    template<class Tw>
+    void sphereProfiles(const DeviceVector<T>& x, const DeviceVector<T>& y, const DeviceVector<T>& z,
+                        const DeviceVector<Tw>* w, const DeviceVector<T>& queryCenters, const DeviceVector<T>* queryScale,
+                        const std::vector<double>& edges, SphereProfileTable& table)
+    {
+        if (mr_) throw std::runtime_error("Domain sphereProfiles: on several ranks use sphereProfilesGlobal\n");
+        const std::size_t numQueries = queryCenters.size() / 3;
+        const int numBins            = int(edges.size()) - 1;
+        table.resize(numQueries, std::size_t(std::max(numBins, 0)), w != nullptr);
+        Context::check(cstone_hip_domain_sphere_profiles(dom_, x.data(), y.data(), z.data(), w ? w->data() : nullptr,
+                                                         int(8 * sizeof(Tw)), queryCenters.data(),
+                                                         queryScale ? queryScale->data() : nullptr, unsigned(numQueries),
+                                                         edges.data(), numBins, table.counts.data(),
+                                                         w ? table.sums.data() : nullptr, table.flags.data()),
+                       "Domain::sphereProfiles");
+    }
+    /*! The same over the particles of ALL ranks of a multi-rank domain (MultiRankDomain::sphereProfiles, collective):
+     *  every rank passes the same queries and edges and receives the same table. */
+    template<class Tw>
+    void sphereProfilesGlobal(const DeviceVector<T>& x, const DeviceVector<T>& y, const DeviceVector<T>& z,
+                              const DeviceVector<Tw>* w, const DeviceVector<T>& queryCenters,
+                              const DeviceVector<T>* queryScale, const std::vector<double>& edges, SphereProfileTable& table)
+    {
+        if (!mr_) throw std::runtime_error("Domain sphereProfilesGlobal: a domain without collectives (sphereProfiles)\n");
+        const std::size_t numQueries = queryCenters.size() / 3;
+        const int numBins            = int(edges.size()) - 1;
+        table.resize(numQueries, std::size_t(std::max(numBins, 0)), w != nullptr);
+        mr_->sphereProfiles(x.data(), y.data(), z.data(), w ? w->data() : static_cast<const Tw*>(nullptr), queryCenters.data(),
+                            queryScale ? queryScale->data() : nullptr, unsigned(numQueries), edges.data(), numBins,
+                            table.counts.data(), w ? table.sums.data() : nullptr, table.flags.data());
     }
     //! R/domain/domain.hpp:411: stores the flag like the reference does (its member convergeTrees, :661, has no reader
     //! there either: the trees converge on the first sync and take one update step per sync afterwards)

@@ -1336,6 +1336,105 @@ extern "C"
                                          void* mass, void* center, void* velocity, void* radius, uint32_t* flags,
                                          uint32_t* num_groups_host);
 
+    /* ---------------------------------------------------------------------------------------------
+     * SPHERE QUERIES at arbitrary points (csrc/sphere.hip): the particles around every query centre, binned by distance
+     * -- radial profiles, aperture masses, and from them the spherical-overdensity radius and mass (R_Delta, M_Delta;
+     * "M200") of a group about its centre.  The walks above take their targets from the particle arrays; a query centre
+     * here is any point.  The rule, stated so that a restatement reproduces counts and flags bit for bit and the sums
+     * within the bound of an arbitrary order of addition (tests/sphere_support.py is one):
+     *
+     *   T = coordinate type (real_bits).  Query q has a centre c_q (query_centers: T[Q][3], device) and a scale s_q
+     *   (query_scale: T[Q], device; NULL means 1).  edges_host[0 .. NB]: HOST doubles, finite, edges[0] >= 0, strictly
+     *   ascending, 1 <= NB <= CSTONE_SPHERE_MAX_BINS.
+     *   Edges    e_b = T(s_q) * T(edges[b]) in T,  e2_b = e_b * e_b in T.
+     *   Offset   d_a = r_j,a - c_q,a in T; on a periodic axis d_a = d_a - len_a * rint(d_a * inv_a) with len and inv in T as
+     *            the neighbour walk has them (len = T(hi) - T(lo), inv = T(1) / len), for EVERY particle, unconditionally.
+     *            d2 = dx*dx + dy*dy + dz*dz, left fold, products not fused.
+     *   Bin      particle j of [first, last) is counted in bin b of query q iff  e2_b <= d2 < e2_{b+1}  and e_NB > 0.
+     *            Half-open: a particle at exactly e_NB is outside, one inside e_0 is in no bin.  Particles outside
+     *            [first, last) -- halos, the other half of a leaf the range cuts -- count nowhere.
+     *   Outputs  counts u64[Q][NB]; sums double[Q][NB] = sum of double(w_j) over the bin whatever real_bits and mass_bits
+     *            are; w == NULL: sums is not written and may be NULL.  flags u32[Q], nullable.
+     *   Flag     CSTONE_SPHERE_TOO_WIDE iff e_NB >= T(0.5) * len_a on some periodic axis a: the minimum image is not
+     *            unique, and the row of such a query is all zeros.
+     *   Scales   a scale of 0, a negative one or a NaN gives a row of zeros and no flag: no e_b is above 0 then (the
+     *            condition e_NB > 0 above; the comparisons of the squares alone would not do, the squares of negative edges
+     *            ascend again).
+     *   Tree     the particle test is the authority: the call is the brute force over all (query, particle) pairs, count
+     *            for count.  The node test only prunes: a node is skipped when its minimum-image distance -- centre offset
+     *            folded, |d| - size, clamped at 0 -- exceeds e_NB * (1 + 16 eps) + 64 eps L, L = the largest of |lo_a|,
+     *            |hi_a|, len_a, eps that of T: a relative term for the squares and an ABSOLUTE one for the cancellation in
+     *            |c_node - c_q| - size (derived in csrc/sphere.hip; it takes query centres within two box lengths of the
+     *            particles on a periodic axis).
+     *   Order    no floating-point atomics.  One wave per query; every lane adds to its own accumulator and the 64 lanes of
+     *            a bin are combined in a fixed tree.  The order of every sum is fixed by the octree, the range and that
+     *            shape (the launch shape is no argument): the same input gives the same bits in every run, on every stream
+     *            and context.
+     *
+     * sphere_profiles : x, y, z (T), w (mass_bits: 32 or 64; nullable), the tree arguments of
+     *            cstone_hip_friends_of_friends.  CSTONE_E_ARG with nothing written: bad real_bits, bad mass_bits with a w,
+     *            last < first, num_bins outside 1 .. 64, edges that are not finite, negative or not strictly ascending
+     *            (decided on the host from the host array), a null required pointer while num_queries > 0.
+     *            num_queries == 0: CSTONE_OK.  last == first: CSTONE_OK, counts (and sums with a w, flags if given) of the
+     *            num_queries rows are zeroed, TOO_WIDE still reported.  A traversal stack overflow ORs 4 into the sticky
+     *            error word (cstone_hip_ctx_sync then fails); the stack is sized for the deepest tree.  Asynchronous on
+     *            the context's stream.  A count per lane is kept in 32 bits: fewer than 2^32 particles per query.
+     *
+     * spherical_overdensity : the finish, one lane per query, all in double.  Requires edges[0] == 0.
+     *            E_b = double(T(s_q)) * edges[b];  C_b = sums[q][0] + ... + sums[q][b-1] in ascending b (C_0 = 0);
+     *            V_b = (4 pi / 3) * (E_b * E_b * E_b), pi = 3.14159265358979323846;  f_b = C_b - rho_threshold * V_b for
+     *            b = 1 .. NB;  b* = the smallest b with f_b < 0.
+     *              none:      flag CSTONE_SO_NOT_REACHED, R = E_NB, M = C_NB
+     *              b* == 1:   flag CSTONE_SO_UNRESOLVED,  R = M = 0
+     *              otherwise: t = f_{b*-1} / (f_{b*-1} - f_{b*}),  R = E_{b*-1} + t * (E_{b*} - E_{b*-1}),
+     *                         M = C_{b*-1} + t * (C_{b*} - C_{b*-1})
+     *            A row whose profile_flags (nullable) has CSTONE_SPHERE_TOO_WIDE passes that flag on with R = M = 0.
+     *            r_delta, m_delta: double[Q]; flags: u32[Q], nullable.  CSTONE_E_ARG with nothing written: bad real_bits, bad
+     *            edges, edges[0] != 0, rho_threshold <= 0 or NaN, a null sums / r_delta / m_delta while num_queries > 0.
+     *            Asynchronous.
+     *
+     * domain_sphere_profiles : sphere_profiles on the octree, the box and [start_index, end_index) of the domain's last
+     *            sync; x, y, z, w laid out like the sync's results.  CSTONE_E_ARG before the first sync.
+     *
+     * domain_mr_sphere_profiles : COLLECTIVE.  Every rank passes the same num_queries, num_bins, edges, centres and scales
+     *            (the all-gathered catalogue, say) and gets the profiles over the particles of ALL ranks.  Each rank bins
+     *            its ASSIGNED range only, on its own octree: the halos are other ranks' assigned particles, so nothing is
+     *            counted twice and the halos need no particular reach.  Refused with CSTONE_E_ARG on every rank before any
+     *            collective, nothing written: no sync yet, bad edges, bad mass_bits with a w.  Then ONE all_gather of
+     *            {status, num_queries, num_bins, w given} per rank: rank-local trouble -- a null array with particles
+     *            present, no memory for the operand, a num_queries or num_bins that differs between ranks, a w on some
+     *            ranks with particles and none on others -- makes every rank return an error together, before the reduction
+     *            and with nothing written.  Then ONE all_reduce (f64, sum) over a single buffer with the counts, as doubles
+     *            (exact below 2^53; cstone_hip_comm_ops has no 64-bit integer type), and the sums; the counts are converted
+     *            back on the device.  TOO_WIDE follows from data every rank has.  COUNTS do not depend on the number of
+     *            ranks; SUMS across ranks depend on the collective's order of addition (every rank receives what the
+     *            collective delivers to it; RCCL and gloo deliver the same bits everywhere).  On a communicator of ONE rank
+     *            there is no collective and the bits are those of sphere_profiles on the same arrays.  A rank without
+     *            particles may pass null particle arrays.
+     * ------------------------------------------------------------------------------------------- */
+#define CSTONE_SPHERE_MAX_BINS 64
+#define CSTONE_SPHERE_TOO_WIDE 0x1u
+#define CSTONE_SO_NOT_REACHED 0x2u
+#define CSTONE_SO_UNRESOLVED 0x4u
+    int cstone_hip_sphere_profiles(cstone_hip_ctx* ctx, int real_bits, int mass_bits, const void* x, const void* y,
+                                   const void* z, const void* w, uint32_t first, uint32_t last, const cstone_box* box_host,
+                                   const int32_t* child_offsets, const int32_t* internal_to_leaf, const uint32_t* layout,
+                                   const void* centers, const void* sizes, const void* query_centers,
+                                   const void* query_scale, uint32_t num_queries, const double* edges_host, int num_bins,
+                                   uint64_t* counts, double* sums, uint32_t* flags);
+    int cstone_hip_spherical_overdensity(cstone_hip_ctx* ctx, int real_bits, const void* query_scale, uint32_t num_queries,
+                                         const double* edges_host, int num_bins, const double* sums,
+                                         const uint32_t* profile_flags, double rho_threshold, double* r_delta,
+                                         double* m_delta, uint32_t* flags);
+    int cstone_hip_domain_sphere_profiles(cstone_hip_domain* dom, const void* x, const void* y, const void* z, const void* w,
+                                          int mass_bits, const void* query_centers, const void* query_scale,
+                                          uint32_t num_queries, const double* edges_host, int num_bins, uint64_t* counts,
+                                          double* sums, uint32_t* flags);
+    int cstone_hip_domain_mr_sphere_profiles(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z,
+                                             const void* w, int mass_bits, const void* query_centers,
+                                             const void* query_scale, uint32_t num_queries, const double* edges_host,
+                                             int num_bins, uint64_t* counts, double* sums, uint32_t* flags);
+
 #ifdef __cplusplus
 }
 #endif
