@@ -653,366 +653,59 @@ public:
      *  first quiet round; the group sizes through one exchange of (label, count) pairs with the owners of the labels.
      *  Works on buffers of the domain and copies to the caller's arrays at the very end: a refused call writes nothing.
      *  Whatever is the same on every rank is refused before the first collective; rank-local trouble rides in the status
-     *  word of the all-gather, so that everybody returns from the same point. */
+     *  word of the all-gather, so that everybody returns from the same point.  A list of stages that share one FofState. */
     int friendsOfFriends(const void* x, const void* y, const void* z, double b, uint32_t maxRounds, uint64_t* labels,
                          uint64_t* groupSizes, uint64_t* numGroups, uint32_t* rounds) override
     {
-        if (firstCall_) return fail(ctx_, CSTONE_E_ARG, "domain_mr_fof: no sync yet");
-        if (!(b > 0.0)) return fail(ctx_, CSTONE_E_ARG, "domain_mr_fof: linking length %g is not > 0", b); // (NaN too)
-        for (int d = 0; d < 3; ++d)
-        {
-            const double len = view_.box.lim[2 * d + 1] - view_.box.lim[2 * d];
-            if (view_.box.bc[d] == 1 && !(b < 0.5 * len))
-                return fail(ctx_, CSTONE_E_ARG, "domain_mr_fof: linking length %g is not below half the periodic edge %g", b, len);
-        }
-        if (maxRounds == 0) maxRounds = CSTONE_FOF_MR_DEFAULT_ROUNDS;
-        const uint32_t si = view_.start_index, ei = view_.end_index, nh = view_.num_particles_with_halos, na = ei - si;
-        const size_t nh1 = std::max<uint32_t>(nh, 1);
-
-        // ---- rank-local trouble: collected, not returned.  The local components are made here, in front of the
-        //      all-gather (they need nothing from the other ranks), so that their failure is part of the agreement too
-        enum : uint64_t { FINE = 0, NULL_ARRAY = 1, STALE_SYNC = 2, NO_MEMORY = 3, LOCAL_STEP = 4 };
-        uint64_t trouble = FINE;
-        if (nh && (!x || !y || !z || !labels)) trouble = NULL_ARRAY;
-        else if (viewSync_ != syncs_) trouble = STALE_SYNC; // the last sync was abandoned: tree and radii are not the view's
-        if (!trouble && (fofComp_.ensure(ctx_, nh1 * 4) || fofLabels_.ensure(ctx_, nh1 * 8) || fofScal_.ensure(ctx_, 4096) ||
-                         (groupSizes && (fofSizes_.ensure(ctx_, nh1 * 8) || fofWork_.ensure(ctx_, fofWorkBytes(nh, na))))))
-            trouble = NO_MEMORY;
-        uint32_t* comp = fofComp_.as<uint32_t>();
-        if (!trouble && nh)
-        {
-            cstone_hip_domain_mr_octree t;
-            if (octree(&t) ||
-                cstone_hip_friends_of_friends(ctx_, rb, x, y, z, 0, nh, &view_.box, t.child_offsets, t.internal_to_leaf, t.layout,
-                                              t.centers, t.sizes, b, comp, nullptr, nullptr))
-                trouble = LOCAL_STEP;
-        }
-
-        // ---- ONE all-gather: assigned count, smallest halo radius of a non-empty assigned leaf, status, sizes wanted
-        const uint64_t INF_BITS = 0x7f800000u;
-        std::vector<uint64_t> rows(4 * size_t(P_));
-        const uint64_t row[4] = {na, INF_BITS, trouble, groupSizes ? 1u : 0u};
-        if (P_ > 1)
-        {
-            CS_TRY(cstone_hip_upload(ctx_, gatherRow(), row, sizeof row));
-            if (!trouble) // (low word of the second entry: the radii are floats)
-                fofMinRadius(ctx_, useLet_ ? let_->haloRadii() : radii_.as<float>(), view_.focus_leaf_counts, view_.start_cell,
-                             view_.end_cell, reinterpret_cast<uint32_t*>(gatherRow() + 1));
-            CS_TRY(callComm(comm_.all_gather(comm_.user, gatherRow(), gatherRecv(), sizeof row), "all_gather (fof)"));
-            CS_TRY(copyToHost(ctx_, rows.data(), gatherRecv(), rows.size() * 8));
-        }
-        else { std::copy(row, row + 4, rows.begin()); }
-        for (int p = 0; p < P_; ++p)
-        {
-            const uint64_t st = rows[4 * size_t(p) + 2];
-            if (st == FINE) continue;
-            if (p != rank_) return fail(ctx_, CSTONE_E_INTERNAL, "domain_mr_fof: rank %d reported a failure (refused on every rank)", p);
-            static const char* const why[] = {"", "null array", "the last sync was abandoned", "out of device memory",
-                                              "the local group finder failed"};
-            return fail(ctx_, st == NO_MEMORY ? CSTONE_E_HIP : st == LOCAL_STEP ? CSTONE_E_INTERNAL : CSTONE_E_ARG,
-                        "domain_mr_fof: %s (refused on every rank)", why[st]);
-        }
-        std::vector<uint64_t> offset(size_t(P_) + 1, 0);
-        bool wantSizes = false;
-        for (int p = 0; p < P_; ++p)
-        {
-            // the cover condition, against the very f32 radii the halo discovery of the last sync used.  One rank: every
-            // particle is on the rank, there is nothing to cover
-            float radius;
-            const uint32_t bits = uint32_t(rows[4 * size_t(p) + 1]);
-            std::memcpy(&radius, &bits, sizeof radius);
-            if (P_ > 1 && !(b <= double(radius)))
-                return fail(ctx_, CSTONE_E_ARG,
-                            "domain_mr_fof: linking length %g exceeds the halo radius %g of a leaf of rank %d: a friend may "
-                            "be missing among the halos (refused on every rank)",
-                            b, double(radius), p);
-            offset[p + 1] = offset[p] + rows[4 * size_t(p)];
-            wantSizes     = wantSizes || rows[4 * size_t(p) + 3] != 0;
-        }
-        const uint64_t firstId = offset[rank_];
-
-        // ---- ids: the position in the global SFC order; halos carry their owner's
-        uint64_t* lab = fofLabels_.as<uint64_t>();
-        CS_TRY(cstone_hip_sequence_u64(ctx_, lab + si, na, firstId));
-        CS_TRY(exchangeHalos(lab, 8));
-
-        // ---- rounds
-        uint32_t* changedDev = fofScal_.as<uint32_t>(); // [0]: changed, [1]: groups owned, byte 8: their sum over the ranks
-        uint32_t made = 0, any = 1;
-        while (any && made < maxRounds)
-        {
-            CS_HIP(ctx_, hipMemsetAsync(changedDev, 0, 8, ctx_->stream));
-            CS_TRY(cstone_hip_fof_lower_labels(ctx_, comp, nh, si, ei, lab, changedDev));
-            ++made;
-            CS_TRY(exchangeHalos(lab, 8));
-            if (P_ > 1)
-            {
-                fofClampFlag(ctx_, changedDev); // (the sum of the counts themselves could wrap to 0)
-                CS_TRY(callComm(comm_.all_reduce(comm_.user, changedDev, 1, 1, 0), "all_reduce (fof round)"));
-            }
-            CS_TRY(copyToHost(ctx_, &any, changedDev, 4));
-        }
-        if (any)
-            return fail(ctx_, CSTONE_E_INTERNAL, "domain_mr_fof: labels still changing after %u rounds (max_rounds)", made);
-
-        // ---- number of groups: every group is counted by the owner of its lowest member.  Exact: an f64 sum below 2^53
-        fofCountOwn(ctx_, lab + si, na, firstId, changedDev + 1);
-        uint32_t own = 0;
-        CS_TRY(copyToHost(ctx_, &own, changedDev + 1, 4));
-        double groups = double(own);
-        if (P_ > 1)
-        {
-            double* sum = reinterpret_cast<double*>(fofScal_.as<char>() + 8);
-            CS_TRY(cstone_hip_upload(ctx_, sum, &groups, 8));
-            CS_TRY(callComm(comm_.all_reduce(comm_.user, sum, 1, 0, 0), "all_reduce (fof groups)"));
-            CS_TRY(copyToHost(ctx_, &groups, sum, 8));
-        }
-
-        if (wantSizes) CS_TRY(fofGroupSizes(offset, comp, lab));
-        CS_TRY(cstone_hip_ctx_sync(ctx_)); // the sticky device-side error word
-        if (nh) CS_HIP(ctx_, hipMemcpyAsync(labels, lab, size_t(nh) * 8, hipMemcpyDeviceToDevice, ctx_->stream));
-        if (nh && groupSizes)
-            CS_HIP(ctx_, hipMemcpyAsync(groupSizes, fofSizes_.p, size_t(nh) * 8, hipMemcpyDeviceToDevice, ctx_->stream));
-        if (numGroups) *numGroups = uint64_t(groups);
-        if (rounds) *rounds = made;
-        fofOffset_     = offset; // the id ranges these labels were made with (fofCatalog)
-        fofOffsetSync_ = syncs_;
-        return CSTONE_OK;
+        FofState s{x, y, z, b, maxRounds, labels, groupSizes, numGroups, rounds};
+        CS_TRY(fofRefuseEverywhere(s));
+        fofLocalComponents(s);
+        CS_TRY(fofAgree(s));
+        CS_TRY(fofAssignIds(s));
+        CS_TRY(fofRounds(s));
+        CS_TRY(fofCountGroups(s));
+        if (s.wantSizes) CS_TRY(fofGroupSizes(s.offset, fofComp_.as<uint32_t>(), fofLabels_.as<uint64_t>()));
+        return fofHandOut(s);
     }
 
     /*! The group catalogue across ranks (cstone_hip_domain_mr_fof_catalog; the rule and the method: include/cstone_hip.h,
      *  DESIGN.md section 5f): one partial per distinct label of the assigned range about its first member, the partials
      *  to the owners of the labels, the owner's combine in (label, source rank) order, filter and finish.  Two
      *  collectives: the all-gather of the counts per owner, with the status of the local steps on board, and the
-     *  all_to_all_v of the records.  The capacity is judged behind them. */
+     *  all_to_all_v of the records.  The capacity is judged behind them.  A list of stages that share one CatalogState. */
     int fofCatalog(const void* x, const void* y, const void* z, const void* m, int massBits, const void* vx, const void* vy,
                    const void* vz, const uint64_t* labels, uint64_t minMembers, size_t capacity, uint64_t* groupLabels,
                    uint64_t* groupSizes, void* mass, void* center, void* velocity, void* radius, uint32_t* flags,
                    uint32_t* numGroupsHost) override
     {
-        // ---- what is the same on every rank: refused before any collective
-        if (firstCall_) return fail(ctx_, CSTONE_E_ARG, "domain_mr_fof_catalog: no sync yet");
-        if (fofOffsetSync_ != syncs_ || fofOffset_.size() != size_t(P_) + 1)
-            return fail(ctx_, CSTONE_E_ARG, "domain_mr_fof_catalog: no domain_mr_fof since the last sync");
-        const int nv = (vx ? 1 : 0) + (vy ? 1 : 0) + (vz ? 1 : 0);
-        if ((massBits != 32 && massBits != 64) || (nv != 0 && nv != 3) || !numGroupsHost)
-            return fail(ctx_, CSTONE_E_ARG, "domain_mr_fof_catalog: bad argument");
-        if (minMembers == 0) minMembers = 1;
-        const uint32_t si = view_.start_index, ei = view_.end_index, na = ei - si;
-        const std::vector<uint64_t>& offset = fofOffset_;
-        const uint64_t total = offset[P_], firstId = offset[rank_];
-
-        // ---- rank-local trouble and the local steps: collected, not returned
-        enum : uint64_t { FINE = 0, NULL_ARRAY = 1, NO_MEMORY = 2, BAD_LABEL = 3, LOCAL_STEP = 4 };
-        uint64_t trouble = FINE;
-        if (na && (!x || !y || !z || !m || !labels || !groupLabels || !groupSizes || !mass || !center || (nv == 3 && !velocity)))
-            trouble = NULL_ARRAY;
-        else if (na >= (1u << 30)) trouble = LOCAL_STEP;
-        const size_t n1        = std::max<uint32_t>(na, 1);
-        const size_t tempBytes = cstone_hip_sort_pairs_temp_bytes(64, n1);
-        size_t at              = 0;
-        auto take              = [&](size_t bytes) { const size_t here = at; at += alignUp(bytes); return here; };
-        const size_t oKeys = take(n1 * 8), oKeysAlt = take(n1 * 8), oVal = take(n1 * 4), oValAlt = take(n1 * 4),
-                     oTemp = take(tempBytes + 256), oWork = take((2 * n1 + 64) * 4), oStart = take((n1 + 1) * 4),
-                     oRunLabels = take(n1 * 8);
-        // the owners' first ids and the bounds of their records: sized by the number of ranks
-        const size_t oFirstIds = 256, oBounds = oFirstIds + alignUp(size_t(P_) * 8), scalBytes = oBounds + alignUp((size_t(P_) + 1) * 4);
-        if (!trouble && (catWork_.ensure(ctx_, at) || catPart_.ensure(ctx_, sizeof(FofPartial)) || catScal_.ensure(ctx_, scalBytes)))
-            trouble = NO_MEMORY;
-        char* w = catWork_.as<char>();
-        uint32_t runs[2] = {0, 0}; // distinct labels here, labels outside [0, total)
-        std::vector<uint64_t> sendCounts(P_, 0), recvCounts(P_, 0);
-        auto localSteps = [&]() -> int
-        {
-            auto* keys = reinterpret_cast<uint64_t*>(w + oKeys);
-            auto* values = reinterpret_cast<uint32_t*>(w + oVal);
-            auto* runStart = reinterpret_cast<uint32_t*>(w + oStart);
-            auto* runLabels = reinterpret_cast<uint64_t*>(w + oRunLabels);
-            CS_HIP(ctx_, hipMemcpyAsync(keys, labels + si, size_t(na) * 8, hipMemcpyDeviceToDevice, ctx_->stream));
-            CS_TRY(cstone_hip_sequence_u32(ctx_, values, na, si));
-            // stable: the members of a label stay in ascending order, its first member is its lowest index
-            CS_TRY(cstone_hip_sort_pairs(ctx_, 64, keys, values, na, w + oKeysAlt, reinterpret_cast<uint32_t*>(w + oValAlt),
-                                         w + oTemp, tempBytes));
-            CS_TRY(fofRunsU64(ctx_, keys, na, total, reinterpret_cast<uint32_t*>(w + oWork), runStart, runLabels, runs));
-            if (runs[1]) return CSTONE_OK; // (reported as BAD_LABEL)
-            if (catPart_.ensure(ctx_, size_t(runs[0]) * sizeof(FofPartial))) return CSTONE_E_HIP;
-            CS_TRY(fofPropsReduce(ctx_, rb, massBits, x, y, z, m, vx, vy, vz, view_.box, runStart, values, runs[0], FofGroupOut{},
-                                  catPart_.as<FofPartial>(), keys));
-            sendCounts[0] = runs[0];
-            if (P_ > 1)
-            {
-                uint64_t* firstIds  = reinterpret_cast<uint64_t*>(catScal_.as<char>() + oFirstIds);
-                uint32_t* boundsDev = reinterpret_cast<uint32_t*>(catScal_.as<char>() + oBounds);
-                std::vector<uint32_t> bounds(size_t(P_) + 1, runs[0]);
-                CS_TRY(cstone_hip_upload(ctx_, firstIds, offset.data(), size_t(P_) * 8));
-                CS_TRY(cstone_hip_lower_bound_u32(ctx_, 64, runLabels, runs[0], firstIds, P_, boundsDev));
-                CS_TRY(copyToHost(ctx_, bounds.data(), boundsDev, size_t(P_) * 4));
-                for (int p = 0; p < P_; ++p)
-                    sendCounts[p] = bounds[p + 1] - bounds[p];
-            }
-            return CSTONE_OK;
-        };
-        if (!trouble && na)
-        {
-            const int rc = localSteps();
-            if (rc != CSTONE_OK) trouble = rc == CSTONE_E_HIP ? NO_MEMORY : LOCAL_STEP;
-            else if (runs[1]) trouble = BAD_LABEL;
-            if (trouble) std::fill(sendCounts.begin(), sendCounts.end(), uint64_t(0));
-        }
-
-        // ---- collective 1: the counts per owner and the status
-        const size_t rowLen = size_t(P_) + 1;
-        std::vector<uint64_t> rows(rowLen * P_), row(sendCounts);
-        row.push_back(trouble);
-        if (P_ > 1)
-        {
-            CS_TRY(cstone_hip_upload(ctx_, gatherRow(), row.data(), rowLen * 8));
-            CS_TRY(callComm(comm_.all_gather(comm_.user, gatherRow(), gatherRecv(), rowLen * 8), "all_gather (fof catalogue)"));
-            CS_TRY(copyToHost(ctx_, rows.data(), gatherRecv(), rows.size() * 8));
-        }
-        else { rows = row; }
-        for (int p = 0; p < P_; ++p)
-        {
-            const uint64_t st = rows[rowLen * p + P_];
-            if (st == FINE) continue;
-            if (p != rank_)
-                return fail(ctx_, CSTONE_E_INTERNAL, "domain_mr_fof_catalog: rank %d reported a failure (refused on every rank)", p);
-            static const char* const why[] = {"", "null array", "out of device memory", "a label outside [0, total)",
-                                              "a local step failed"};
-            return fail(ctx_, st == NO_MEMORY ? CSTONE_E_HIP : st == LOCAL_STEP ? CSTONE_E_INTERNAL : CSTONE_E_ARG,
-                        "domain_mr_fof_catalog: %s (refused on every rank)", why[st]);
-        }
-        uint64_t numRecv = 0;
-        for (int p = 0; p < P_; ++p)
-            numRecv += recvCounts[p] = rows[rowLen * p + rank_];
-        if (numRecv >= (uint64_t(1) << 30))
-            return fail(ctx_, CSTONE_E_CAPACITY, "domain_mr_fof_catalog: %llu records for one owner", (unsigned long long)numRecv);
-
-        // ---- collective 2: the records to the owners.  How much arrives is known only now, behind the one agreement: a
-        //      rank whose receive buffer cannot be had (or whose share exceeds 2^30 records) returns ALONE, and the others
-        //      then wait in the all_to_all_v -- as in the size protocol of friendsOfFriends
-        const size_t r1 = std::max<uint64_t>(numRecv, 1), tempR = cstone_hip_sort_pairs_temp_bytes(64, r1);
-        at = 0;
-        const size_t oRec = take(r1 * sizeof(FofPartial)), oKeysR = take(r1 * 8), oKeysAltR = take(r1 * 8), oOrd = take(r1 * 4),
-                     oOrdAlt = take(r1 * 4), oTempR = take(tempR + 256), oWorkR = take((2 * r1 + 64) * 4),
-                     oStartR = take((r1 + 1) * 4), oComb = take(r1 * sizeof(FofPartial)), oKeep = take(r1 * 4),
-                     oPos = take(r1 * 4), oTotal = take(256);
-        CS_TRY(catRecv_.ensure(ctx_, at));
-        char* q       = catRecv_.as<char>();
-        auto* records = reinterpret_cast<FofPartial*>(q + oRec);
-        CS_TRY(fofAllToAll(catPart_.p, sendCounts, records, recvCounts, sizeof(FofPartial), "all_to_all_v (fof catalogue)"));
-        *numGroupsHost = 0;
-        if (numRecv == 0) return CSTONE_OK;
-
-        // ---- the owner: stable sort by label (the records arrive by source rank), combine, filter, finish
-        auto* keysR = reinterpret_cast<uint64_t*>(q + oKeysR);
-        auto* order = reinterpret_cast<uint32_t*>(q + oOrd);
-        auto* runStartR = reinterpret_cast<uint32_t*>(q + oStartR);
-        auto* combined = reinterpret_cast<FofPartial*>(q + oComb);
-        auto* keep = reinterpret_cast<uint32_t*>(q + oKeep);
-        auto* pos = reinterpret_cast<uint32_t*>(q + oPos);
-        auto* totalDev = reinterpret_cast<uint32_t*>(q + oTotal);
-        fofPartialLabels(ctx_, records, uint32_t(numRecv), keysR);
-        CS_TRY(cstone_hip_sequence_u32(ctx_, order, numRecv, 0));
-        CS_TRY(cstone_hip_sort_pairs(ctx_, 64, keysR, order, numRecv, q + oKeysAltR, reinterpret_cast<uint32_t*>(q + oOrdAlt),
-                                     q + oTempR, tempR));
-        uint32_t ownRuns[2] = {0, 0};
-        CS_TRY(fofRunsU64(ctx_, keysR, uint32_t(numRecv), ~uint64_t(0), reinterpret_cast<uint32_t*>(q + oWorkR), runStartR,
-                          nullptr, ownRuns));
-        CS_TRY(fofCombinePartials(ctx_, rb, x, y, z, view_.box, records, order, runStartR, ownRuns[0], firstId, si, na,
-                                  minMembers, combined, keep));
-        CS_TRY(arenaReserve(ctx_, scanArenaBytes(ownRuns[0]) + 1024));
-        const int scanned = scanU32(ctx_, keep, pos, ownRuns[0], 0u, false, totalDev);
-        arenaReset(ctx_);
-        CS_TRY(scanned);
-        uint32_t kept = 0;
-        CS_TRY(copyToHost(ctx_, &kept, totalDev, 4));
-        CS_TRY(cstone_hip_ctx_sync(ctx_)); // the sticky device-side error word (a record whose label is not mine)
-        *numGroupsHost = kept;
-        if (kept > capacity)
-            return fail(ctx_, CSTONE_E_CAPACITY, "domain_mr_fof_catalog: %u groups, capacity %zu", kept, capacity);
-        return fofFinishCombined(ctx_, rb, nv == 3, view_.box, combined, keep, pos, ownRuns[0],
-                                 FofGroupOut{mass, center, velocity, radius, flags, groupLabels, groupSizes});
+        CatalogState s{x, y, z, m, massBits, vx, vy, vz, labels, minMembers, capacity, groupLabels, groupSizes, mass, center,
+                       velocity, radius, flags, numGroupsHost};
+        CS_TRY(catalogRefuseEverywhere(s));
+        catalogLocalTrouble(s);
+        catalogLocalSteps(s);
+        CS_TRY(catalogAgree(s));
+        CS_TRY(catalogExchange(s));
+        if (s.numRecv == 0) return CSTONE_OK;
+        CS_TRY(catalogCombine(s));
+        return catalogFinish(s);
     }
 
     /*! Sphere profiles over the particles of all ranks (cstone_hip_domain_mr_sphere_profiles; the rule: include/
      *  cstone_hip.h).  Every rank bins its assigned range on its own octree into the caller's arrays; one all-gather of
-     *  {status, Q, NB, w given} lets every rank fail together; one all-reduce of {counts as doubles, sums} follows. */
+     *  {status, Q, NB, w given} lets every rank fail together; one all-reduce of {counts as doubles, sums} follows.  A list
+     *  of stages that share one ProfilesState. */
     int sphereProfiles(const void* x, const void* y, const void* z, const void* w, int massBits, const void* queryCenters,
                        const void* queryScale, uint32_t numQueries, const double* edgesHost, int numBins, uint64_t* counts,
                        double* sums, uint32_t* flags) override
     {
-        // ---- what is the same on every rank: refused before any collective
-        if (firstCall_) return fail(ctx_, CSTONE_E_ARG, "domain_mr_sphere_profiles: no sync yet");
-        if (!sphereEdgesOk(edgesHost, numBins)) return fail(ctx_, CSTONE_E_ARG, "domain_mr_sphere_profiles: bad edges");
-        if (w && massBits != 32 && massBits != 64) return fail(ctx_, CSTONE_E_ARG, "domain_mr_sphere_profiles: bad mass_bits");
-        const uint32_t si = view_.start_index, ei = view_.end_index, na = ei - si;
-        cstone_hip_domain_mr_octree t{};
-        if (P_ == 1)
-        {
-            if (numQueries == 0) return CSTONE_OK;
-            CS_TRY(octree(&t));
-            return cstone_hip_sphere_profiles(ctx_, rb, massBits, x, y, z, w, si, ei, &view_.box, t.child_offsets,
-                                              t.internal_to_leaf, t.layout, t.centers, t.sizes, queryCenters, queryScale,
-                                              numQueries, edgesHost, numBins, counts, sums, flags);
-        }
-
-        // ---- rank-local trouble: collected, not returned
-        enum : uint64_t { FINE = 0, NULL_ARRAY = 1, NO_MEMORY = 2, LOCAL_STEP = 3, MISMATCH = 4 };
-        enum : uint64_t { W_NONE = 0, W_GIVEN = 1, W_ANY = 2 }; // a rank without particles goes with the others
-        const size_t cells = size_t(numQueries) * size_t(numBins);
-        uint64_t trouble   = FINE;
-        if (numQueries && (!queryCenters || !counts || (w && !sums) || (na && (!x || !y || !z)))) trouble = NULL_ARRAY;
-        else if (sphereBuf_.ensure(ctx_, std::max<size_t>(2 * cells * sizeof(double), 256))) trouble = NO_MEMORY;
-        else if (na && octree(&t)) trouble = LOCAL_STEP;
-        const uint64_t row[4] = {trouble, numQueries, uint64_t(numBins), na ? (w ? W_GIVEN : W_NONE) : (w ? W_GIVEN : W_ANY)};
-        std::vector<uint64_t> rows(4 * size_t(P_));
-        CS_TRY(cstone_hip_upload(ctx_, gatherRow(), row, sizeof row));
-        CS_TRY(callComm(comm_.all_gather(comm_.user, gatherRow(), gatherRecv(), sizeof row), "all_gather (sphere profiles)"));
-        CS_TRY(copyToHost(ctx_, rows.data(), gatherRecv(), rows.size() * 8));
-        uint64_t wMode = W_ANY;
-        for (int p = 0; p < P_; ++p)
-        {
-            const uint64_t* r = rows.data() + 4 * size_t(p);
-            uint64_t st       = r[0];
-            if (st == FINE && (r[1] != rows[1] || r[2] != rows[2])) st = MISMATCH;
-            if (st == FINE && r[3] != W_ANY)
-            {
-                if (wMode == W_ANY) wMode = r[3];
-                else if (wMode != r[3]) st = MISMATCH;
-            }
-            if (st == FINE) continue;
-            if (st == MISMATCH)
-                return fail(ctx_, CSTONE_E_ARG,
-                            "domain_mr_sphere_profiles: the ranks disagree on num_queries, num_bins or whether there is a w "
-                            "(rank %d; refused on every rank)", p);
-            if (p != rank_)
-                return fail(ctx_, CSTONE_E_INTERNAL, "domain_mr_sphere_profiles: rank %d reported a failure (refused on every rank)", p);
-            static const char* const why[] = {"", "null array", "out of device memory", "no octree"};
-            return fail(ctx_, st == NO_MEMORY ? CSTONE_E_HIP : st == LOCAL_STEP ? CSTONE_E_INTERNAL : CSTONE_E_ARG,
-                        "domain_mr_sphere_profiles: %s (refused on every rank)", why[st]);
-        }
+        ProfilesState s{x, y, z, w, massBits, queryCenters, queryScale, numQueries, edgesHost, numBins, counts, sums, flags};
+        CS_TRY(profilesRefuseEverywhere(s));
+        if (P_ == 1) return profilesOnOneRank(s);
+        profilesLocalTrouble(s);
+        CS_TRY(profilesAgree(s));
         if (numQueries == 0) return CSTONE_OK;
-        const bool globalW = wMode == W_GIVEN;
-
-        // ---- the local profiles, into the caller's arrays.  A rank without particles has nothing to read: its empty
-        //      range zeroes the rows and sets the flags, and the operand itself stands in for the arrays it may not have
-        const void* dummy = sphereBuf_.p;
-        auto nz           = [&](const void* ptr) { return ptr ? ptr : dummy; };
-        CS_TRY(cstone_hip_sphere_profiles(ctx_, rb, massBits, nz(x), nz(y), nz(z), w, si, ei, &view_.box,
-                                          static_cast<const int32_t*>(nz(t.child_offsets)),
-                                          static_cast<const int32_t*>(nz(t.internal_to_leaf)),
-                                          static_cast<const uint32_t*>(nz(t.layout)), nz(t.centers), nz(t.sizes), queryCenters,
-                                          queryScale, numQueries, edgesHost, numBins, counts, sums, flags));
-        // ---- one all-reduce: {counts as doubles, sums}
-        double* buf = sphereBuf_.as<double>();
-        if (globalW && !w) CS_HIP(ctx_, hipMemsetAsync(buf + cells, 0, cells * sizeof(double), ctx_->stream));
-        spherePackRows(ctx_, counts, w ? sums : nullptr, cells, buf);
-        CS_TRY(callComm(comm_.all_reduce(comm_.user, buf, (globalW ? 2 : 1) * cells, 0, 0), "all_reduce (sphere profiles)"));
-        sphereUnpackRows(ctx_, buf, cells, counts, globalW ? sums : nullptr);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess)
-            return fail(ctx_, CSTONE_E_HIP, "domain_mr_sphere_profiles: %s", hipGetErrorString(e));
-        return CSTONE_OK;
+        CS_TRY(profilesLocal(s));
+        return profilesReduce(s);
     }
 
     int multipoles(const void** out, int32_t* numNodes) override
@@ -1987,15 +1680,10 @@ private:
     int countMatrix(const std::vector<uint64_t>& mine, std::vector<uint64_t>& matrix)
     {
         matrix.assign(size_t(P_) * P_, 0);
-        if (P_ == 1)
-        {
-            matrix[0] = mine[0];
-            return CSTONE_OK;
-        }
-        uint64_t *send = gatherRow(), *recv = gatherRecv();
-        CS_HIP(ctx_, hipMemcpyAsync(send, mine.data(), size_t(P_) * 8, hipMemcpyHostToDevice, ctx_->stream));
-        CS_TRY(callComm(comm_.all_gather(comm_.user, send, recv, size_t(P_) * 8), "all_gather (counts)"));
-        return copyToHost(ctx_, matrix.data(), recv, size_t(P_) * P_ * 8);
+        if (P_ == 1) matrix[0] = mine[0];
+        // (staged by the runtime's copy, not by stageRow: the owner-side sync keeps its sequence of calls)
+        else CS_HIP(ctx_, hipMemcpyAsync(gatherRow(), mine.data(), size_t(P_) * 8, hipMemcpyHostToDevice, ctx_->stream));
+        return gatherRows(P_, "all_gather (counts)", matrix);
     }
 
     // ---- C1
@@ -2296,30 +1984,81 @@ private:
         return cstone_hip_node_centers(ctx_, curve_, kb, rb, nsPrefixes_.p, M, &box_, nsCenters_.p, nsSizes_.p);
     }
 
-    // ---- group sizes of friendsOfFriends().  The slices of fofWork_ for nh particles of which na are assigned:
-    struct FofSlices
+    // ---- What the collective analyses (friendsOfFriends, fofCatalog, sphereProfiles) share: DESIGN.md, section 5f,
+    //      "The agreement the collective analyses share"
+
+    //! Rank-local trouble of an analysis, the status word of its all-gather; also the order of every call's table of texts
+    enum Trouble : uint64_t { FINE, NULL_ARRAY, STALE_SYNC, NO_MEMORY, BAD_LABEL, LOCAL_STEP, MISMATCH, NUM_TROUBLES };
+    static int troubleCode(uint64_t t) { return t == NO_MEMORY ? CSTONE_E_HIP : t == LOCAL_STEP ? CSTONE_E_INTERNAL : CSTONE_E_ARG; }
+
+    /*! The agreement: every rank scans the same gathered rows (stride words each, the status at word `status`) and the first
+     *  rank in trouble decides, so all ranks return from here or none does -- that rank with its own text and code, the
+     *  others with "reported a failure".  MISMATCH is nobody's own: the caller derives it from the rows, it is the same
+     *  refusal on every rank and names the first rank that differs. */
+    int agree(const char* call, const std::vector<uint64_t>& rows, size_t stride, size_t status, const char* const* why)
     {
-        size_t count, keys, keysAlt, values, valuesAlt, temp, tempBytes, pairs, answers, componentTotals, totals, end;
-    };
-    static FofSlices fofSlices(uint32_t nh, uint32_t na)
-    {
-        const size_t n = std::max<uint32_t>(nh, 1);
-        FofSlices s{};
-        size_t at   = 0;
-        auto take   = [&](size_t bytes) { const size_t here = at; at += alignUp(bytes); return here; };
-        s.count     = take(n * 4);
-        s.keys      = take(n * 8), s.keysAlt = take(n * 8);
-        s.values    = take(n * 4), s.valuesAlt = take(n * 4);
-        s.tempBytes = cstone_hip_sort_pairs_temp_bytes(64, n);
-        s.temp      = take(s.tempBytes + 256);
-        s.pairs     = take(n * sizeof(FofPair));
-        s.answers   = take(n * 8);
-        s.componentTotals = take(n * 8);
-        s.totals    = take(size_t(std::max<uint32_t>(na, 1)) * 8);
-        s.end       = at;
-        return s;
+        for (int p = 0; p < P_; ++p)
+        {
+            const uint64_t st = rows[stride * p + status];
+            if (st == FINE) continue;
+            if (st == MISMATCH) return fail(ctx_, troubleCode(st), "%s: %s (rank %d; refused on every rank)", call, why[st], p);
+            if (p != rank_) return fail(ctx_, CSTONE_E_INTERNAL, "%s: rank %d reported a failure (refused on every rank)", call, p);
+            return fail(ctx_, troubleCode(st), "%s: %s (refused on every rank)", call, why[st]);
+        }
+        return CSTONE_OK;
     }
-    static size_t fofWorkBytes(uint32_t nh, uint32_t na) { return fofSlices(nh, na).end; }
+
+    //! The row gather, first half: my row of `words` 64-bit words to gatherRow() (one rank: it is all of rows already)
+    int stageRow(const uint64_t* row, size_t words, std::vector<uint64_t>& rows)
+    {
+        rows.assign(row, row + words);
+        rows.resize(words * P_);
+        return P_ > 1 ? cstone_hip_upload(ctx_, gatherRow(), row, words * 8) : CSTONE_OK;
+    }
+
+    //! ... second half: what is staged at gatherRow() on every rank (a kernel may have added to it) to rows, on the host
+    int gatherRows(size_t words, const char* what, std::vector<uint64_t>& rows)
+    {
+        if (P_ == 1) return CSTONE_OK;
+        CS_TRY(callComm(comm_.all_gather(comm_.user, gatherRow(), gatherRecv(), words * 8), what));
+        return copyToHost(ctx_, rows.data(), gatherRecv(), rows.size() * 8);
+    }
+
+    //! recvCounts[p] = what rank p has for me: column rank_ of the gathered count rows (stride words each); their sum
+    uint64_t recvColumn(const std::vector<uint64_t>& rows, size_t stride, std::vector<uint64_t>& recvCounts) const
+    {
+        uint64_t numRecv = 0;
+        recvCounts.assign(P_, 0);
+        for (int p = 0; p < P_; ++p)
+            numRecv += recvCounts[p] = rows[stride * p + rank_];
+        return numRecv;
+    }
+
+    //! sendCounts[p] = how many of the n ascending labels owner p holds, whose ids start at offset[p]: the lower bounds of
+    //! the owners' first ids.  firstIds (P words) and boundsDev (P + 1 u32) are the caller's device scratch
+    int countsPerOwner(const uint64_t* labels, uint32_t n, const std::vector<uint64_t>& offset, uint64_t* firstIds,
+                       uint32_t* boundsDev, std::vector<uint64_t>& sendCounts)
+    {
+        sendCounts.assign(P_, 0);
+        sendCounts[0] = n;
+        if (P_ == 1) return CSTONE_OK;
+        std::vector<uint32_t> bounds(size_t(P_) + 1, n);
+        CS_TRY(cstone_hip_upload(ctx_, firstIds, offset.data(), size_t(P_) * 8));
+        CS_TRY(cstone_hip_lower_bound_u32(ctx_, 64, labels, n, firstIds, P_, boundsDev));
+        CS_TRY(copyToHost(ctx_, bounds.data(), boundsDev, size_t(P_) * 4));
+        for (int p = 0; p < P_; ++p)
+            sendCounts[p] = bounds[p + 1] - bounds[p];
+        return CSTONE_OK;
+    }
+
+    //! the slices of a work buffer, one behind the other on 256-byte boundaries; at: the bytes handed out so far
+    struct Slicer
+    {
+        size_t at = 0;
+        size_t take(size_t bytes) { return std::exchange(at, at + alignUp(bytes)); }
+    };
+    template<class V>
+    static V* sliceOf(const DevBuf& buf, size_t byte) { return reinterpret_cast<V*>(buf.as<char>() + byte); }
 
     //! what an all_to_all_v does, also on one rank (where the one segment is copied)
     int fofAllToAll(const void* send, const std::vector<uint64_t>& sendCounts, void* recv, const std::vector<uint64_t>& recvCounts,
@@ -2337,6 +2076,165 @@ private:
         return callComm(comm_.all_to_all_v(comm_.user, send, sb.data(), recv, rbv.data()), what);
     }
 
+    // ---- friendsOfFriends(), stage by stage
+
+    //! What the stages of one friendsOfFriends() share: the caller's arguments and what the stages before have decided
+    struct FofState
+    {
+        const void *x, *y, *z;
+        double b;
+        uint32_t maxRounds;
+        uint64_t *labels, *groupSizes, *numGroups;
+        uint32_t* rounds;
+        uint32_t si = 0, ei = 0, nh = 0, na = 0; // the view's: assigned [si, ei) of nh present, na = ei - si
+        uint64_t trouble = FINE;
+        std::vector<uint64_t> offset; // P + 1 bounds of the ranks' id ranges: global ids are positions in the SFC order
+        bool wantSizes = false;       // some rank asked for the sizes
+        uint32_t made  = 0;           // rounds made
+        double groups  = 0;           // groups over all ranks
+    };
+
+    //! what is the same on every rank: refused before any collective
+    int fofRefuseEverywhere(FofState& s)
+    {
+        if (firstCall_) return fail(ctx_, CSTONE_E_ARG, "domain_mr_fof: no sync yet");
+        if (!(s.b > 0.0)) return fail(ctx_, CSTONE_E_ARG, "domain_mr_fof: linking length %g is not > 0", s.b); // (NaN too)
+        for (int d = 0; d < 3; ++d)
+        {
+            const double len = view_.box.lim[2 * d + 1] - view_.box.lim[2 * d];
+            if (view_.box.bc[d] == 1 && !(s.b < 0.5 * len))
+                return fail(ctx_, CSTONE_E_ARG, "domain_mr_fof: linking length %g is not below half the periodic edge %g", s.b, len);
+        }
+        if (s.maxRounds == 0) s.maxRounds = CSTONE_FOF_MR_DEFAULT_ROUNDS;
+        s.si = view_.start_index, s.ei = view_.end_index, s.nh = view_.num_particles_with_halos, s.na = s.ei - s.si;
+        return CSTONE_OK;
+    }
+
+    //! rank-local trouble: collected, not returned.  The local components are made here, in front of the all-gather (they
+    //! need nothing from the other ranks), so that their failure is part of the agreement too
+    void fofLocalComponents(FofState& s)
+    {
+        const size_t nh1 = std::max<uint32_t>(s.nh, 1);
+        if (s.nh && (!s.x || !s.y || !s.z || !s.labels)) s.trouble = NULL_ARRAY;
+        else if (viewSync_ != syncs_) s.trouble = STALE_SYNC; // the last sync was abandoned: tree and radii are not the view's
+        if (!s.trouble && (fofComp_.ensure(ctx_, nh1 * 4) || fofLabels_.ensure(ctx_, nh1 * 8) || fofScal_.ensure(ctx_, 4096) ||
+                           (s.groupSizes && (fofSizes_.ensure(ctx_, nh1 * 8) || fofWork_.ensure(ctx_, fofSlices(s.nh, s.na).end)))))
+            s.trouble = NO_MEMORY;
+        if (s.trouble || !s.nh) return;
+        cstone_hip_domain_mr_octree t;
+        if (octree(&t) ||
+            cstone_hip_friends_of_friends(ctx_, rb, s.x, s.y, s.z, 0, s.nh, &view_.box, t.child_offsets, t.internal_to_leaf, t.layout,
+                                          t.centers, t.sizes, s.b, fofComp_.as<uint32_t>(), nullptr, nullptr))
+            s.trouble = LOCAL_STEP;
+    }
+
+    //! ONE all-gather: assigned count, smallest halo radius of a non-empty assigned leaf, status, sizes wanted; behind the
+    //! agreement the cover condition and the id ranges
+    int fofAgree(FofState& s)
+    {
+        const uint64_t INF_BITS = 0x7f800000u;
+        const uint64_t row[4]   = {s.na, INF_BITS, s.trouble, s.groupSizes ? 1u : 0u};
+        std::vector<uint64_t> rows;
+        CS_TRY(stageRow(row, 4, rows));
+        if (P_ > 1 && !s.trouble) // (low word of the second entry: the radii are floats)
+            fofMinRadius(ctx_, useLet_ ? let_->haloRadii() : radii_.as<float>(), view_.focus_leaf_counts, view_.start_cell,
+                         view_.end_cell, reinterpret_cast<uint32_t*>(gatherRow() + 1));
+        CS_TRY(gatherRows(4, "all_gather (fof)", rows));
+        static const char* const why[NUM_TROUBLES] = {"", "null array", "the last sync was abandoned", "out of device memory", "",
+                                                      "the local group finder failed"};
+        CS_TRY(agree("domain_mr_fof", rows, 4, 2, why));
+        s.offset.assign(size_t(P_) + 1, 0);
+        for (int p = 0; p < P_; ++p)
+        {
+            // the cover condition, against the very f32 radii the halo discovery of the last sync used.  One rank: every
+            // particle is on the rank, there is nothing to cover
+            float radius;
+            const uint32_t bits = uint32_t(rows[4 * size_t(p) + 1]);
+            std::memcpy(&radius, &bits, sizeof radius);
+            if (P_ > 1 && !(s.b <= double(radius)))
+                return fail(ctx_, CSTONE_E_ARG,
+                            "domain_mr_fof: linking length %g exceeds the halo radius %g of a leaf of rank %d: a friend may "
+                            "be missing among the halos (refused on every rank)",
+                            s.b, double(radius), p);
+            s.offset[p + 1] = s.offset[p] + rows[4 * size_t(p)];
+            s.wantSizes     = s.wantSizes || rows[4 * size_t(p) + 3] != 0;
+        }
+        return CSTONE_OK;
+    }
+
+    //! ids: the position in the global SFC order; halos carry their owner's
+    int fofAssignIds(FofState& s)
+    {
+        CS_TRY(cstone_hip_sequence_u64(ctx_, fofLabels_.as<uint64_t>() + s.si, s.na, s.offset[rank_]));
+        return exchangeHalos(fofLabels_.p, 8);
+    }
+
+    //! rounds of { lower the labels, exchange their halos, all-reduce "somebody changed" } up to the first quiet one
+    int fofRounds(FofState& s)
+    {
+        uint64_t* lab        = fofLabels_.as<uint64_t>();
+        uint32_t* changedDev = fofScal_.as<uint32_t>(); // [0]: changed, [1]: groups owned, byte 8: their sum over the ranks
+        uint32_t any         = 1;
+        while (any && s.made < s.maxRounds)
+        {
+            CS_HIP(ctx_, hipMemsetAsync(changedDev, 0, 8, ctx_->stream));
+            CS_TRY(cstone_hip_fof_lower_labels(ctx_, fofComp_.as<uint32_t>(), s.nh, s.si, s.ei, lab, changedDev));
+            ++s.made;
+            CS_TRY(exchangeHalos(lab, 8));
+            if (P_ > 1)
+            {
+                fofClampFlag(ctx_, changedDev); // (the sum of the counts themselves could wrap to 0)
+                CS_TRY(callComm(comm_.all_reduce(comm_.user, changedDev, 1, 1, 0), "all_reduce (fof round)"));
+            }
+            CS_TRY(copyToHost(ctx_, &any, changedDev, 4));
+        }
+        if (any)
+            return fail(ctx_, CSTONE_E_INTERNAL, "domain_mr_fof: labels still changing after %u rounds (max_rounds)", s.made);
+        return CSTONE_OK;
+    }
+
+    //! number of groups: every group is counted by the owner of its lowest member.  Exact: an f64 sum below 2^53
+    int fofCountGroups(FofState& s)
+    {
+        uint32_t* ownDev = fofScal_.as<uint32_t>() + 1;
+        fofCountOwn(ctx_, fofLabels_.as<uint64_t>() + s.si, s.na, s.offset[rank_], ownDev);
+        uint32_t own = 0;
+        CS_TRY(copyToHost(ctx_, &own, ownDev, 4));
+        s.groups = double(own);
+        if (P_ > 1)
+        {
+            double* sum = sliceOf<double>(fofScal_, 8);
+            CS_TRY(cstone_hip_upload(ctx_, sum, &s.groups, 8));
+            CS_TRY(callComm(comm_.all_reduce(comm_.user, sum, 1, 0, 0), "all_reduce (fof groups)"));
+            CS_TRY(copyToHost(ctx_, &s.groups, sum, 8));
+        }
+        return CSTONE_OK;
+    }
+
+    //! the domain's buffers to the caller's arrays, at the very end: a refused call has written nothing
+    int fofHandOut(FofState& s)
+    {
+        CS_TRY(cstone_hip_ctx_sync(ctx_)); // the sticky device-side error word
+        if (s.nh) CS_HIP(ctx_, hipMemcpyAsync(s.labels, fofLabels_.p, size_t(s.nh) * 8, hipMemcpyDeviceToDevice, ctx_->stream));
+        if (s.nh && s.groupSizes)
+            CS_HIP(ctx_, hipMemcpyAsync(s.groupSizes, fofSizes_.p, size_t(s.nh) * 8, hipMemcpyDeviceToDevice, ctx_->stream));
+        if (s.numGroups) *s.numGroups = uint64_t(s.groups);
+        if (s.rounds) *s.rounds = s.made;
+        fofOffset_     = s.offset; // the id ranges these labels were made with (fofCatalog)
+        fofOffsetSync_ = syncs_;
+        return CSTONE_OK;
+    }
+
+    //! the slices of fofWork_ (fofGroupSizes) for nh particles of which na are assigned
+    struct FofSlices { size_t count, keys, keysAlt, values, valuesAlt, temp, tempBytes, pairs, answers, componentTotals, totals, end; };
+    static FofSlices fofSlices(uint32_t nh, uint32_t na)
+    {
+        const size_t n = std::max<uint32_t>(nh, 1), tempBytes = cstone_hip_sort_pairs_temp_bytes(64, n);
+        Slicer w; // (a braced list is evaluated from left to right)
+        return {w.take(n * 4), w.take(n * 8), w.take(n * 8), w.take(n * 4), w.take(n * 4), w.take(tempBytes + 256), tempBytes,
+                w.take(n * sizeof(FofPair)), w.take(n * 8), w.take(n * 8), w.take(size_t(std::max<uint32_t>(na, 1)) * 8), w.at};
+    }
+
     /*! fofSizes_[k] = members of k's group over all ranks.  Every local component with an assigned member sends (label,
      *  assigned members) to the owner of the label -- sorted by label the pairs of one owner are contiguous, owners hold
      *  contiguous id ranges in rank order --, the owner adds them up per own particle and answers every pair with the
@@ -2344,53 +2242,316 @@ private:
     int fofGroupSizes(const std::vector<uint64_t>& offset, const uint32_t* comp, const uint64_t* lab)
     {
         const uint32_t si = view_.start_index, ei = view_.end_index, nh = view_.num_particles_with_halos, na = ei - si;
-        CS_TRY(fofSizes_.ensure(ctx_, size_t(std::max<uint32_t>(nh, 1)) * 8));
-        CS_TRY(fofWork_.ensure(ctx_, fofWorkBytes(nh, na)));
         const FofSlices s = fofSlices(nh, na);
-        char* w           = fofWork_.as<char>();
-        auto* count = reinterpret_cast<uint32_t*>(w + s.count);
-        auto* keys = reinterpret_cast<uint64_t*>(w + s.keys);
-        auto* values = reinterpret_cast<uint32_t*>(w + s.values);
-        auto* pairs = reinterpret_cast<FofPair*>(w + s.pairs);
-        auto* answers = reinterpret_cast<uint64_t*>(w + s.answers);
-        auto* componentTotals = reinterpret_cast<uint64_t*>(w + s.componentTotals);
-        auto* totals = reinterpret_cast<uint64_t*>(w + s.totals);
+        CS_TRY(fofSizes_.ensure(ctx_, size_t(std::max<uint32_t>(nh, 1)) * 8));
+        CS_TRY(fofWork_.ensure(ctx_, s.end));
+        auto* count = sliceOf<uint32_t>(fofWork_, s.count);
+        auto* keys = sliceOf<uint64_t>(fofWork_, s.keys);
+        auto* values = sliceOf<uint32_t>(fofWork_, s.values);
+        auto* pairs = sliceOf<FofPair>(fofWork_, s.pairs);
+        auto* answers = sliceOf<uint64_t>(fofWork_, s.answers);
 
         uint32_t numPairs = 0;
         CS_TRY(fofComponentPairs(ctx_, comp, nh, si, ei, lab, count, keys, values, &numPairs));
         if (numPairs)
-            CS_TRY(cstone_hip_sort_pairs(ctx_, 64, keys, values, numPairs, w + s.keysAlt, reinterpret_cast<uint32_t*>(w + s.valuesAlt),
-                                         w + s.temp, s.tempBytes));
+            CS_TRY(cstone_hip_sort_pairs(ctx_, 64, keys, values, numPairs, sliceOf<char>(fofWork_, s.keysAlt),
+                                         sliceOf<uint32_t>(fofWork_, s.valuesAlt), sliceOf<char>(fofWork_, s.temp), s.tempBytes));
         fofPackPairs(ctx_, keys, values, count, numPairs, pairs);
 
-        // pairs per owner: the lower bounds of the owners' first ids in the sorted labels
-        std::vector<uint64_t> sendCounts(P_, 0), recvCounts(P_, 0), matrix;
-        sendCounts[0] = numPairs;
-        if (P_ > 1)
-        {
-            uint64_t* firstIds = reinterpret_cast<uint64_t*>(fofScal_.as<char>() + 256);
-            uint32_t* boundsDev = reinterpret_cast<uint32_t*>(fofScal_.as<char>() + 2048);
-            std::vector<uint32_t> bounds(size_t(P_) + 1, numPairs);
-            CS_TRY(cstone_hip_upload(ctx_, firstIds, offset.data(), size_t(P_) * 8));
-            CS_TRY(cstone_hip_lower_bound_u32(ctx_, 64, keys, numPairs, firstIds, P_, boundsDev));
-            CS_TRY(copyToHost(ctx_, bounds.data(), boundsDev, size_t(P_) * 4));
-            for (int p = 0; p < P_; ++p)
-                sendCounts[p] = bounds[p + 1] - bounds[p];
-        }
-        CS_TRY(countMatrix(sendCounts, matrix)); // the counts travel first
-        uint64_t numRecv = 0;
-        for (int p = 0; p < P_; ++p)
-            numRecv += recvCounts[p] = matrix[size_t(p) * P_ + rank_];
+        // pairs per owner, the counts travel first
+        std::vector<uint64_t> sendCounts, recvCounts, matrix;
+        CS_TRY(countsPerOwner(keys, numPairs, offset, sliceOf<uint64_t>(fofScal_, 256), sliceOf<uint32_t>(fofScal_, 2048), sendCounts));
+        CS_TRY(countMatrix(sendCounts, matrix));
+        const uint64_t numRecv = recvColumn(matrix, P_, recvCounts);
         if (numRecv >= (uint64_t(1) << 32)) return fail(ctx_, CSTONE_E_CAPACITY, "domain_mr_fof: %llu pairs for one owner", (unsigned long long)numRecv);
-        CS_TRY(fofRecv_.ensure(ctx_, alignUp(std::max<uint64_t>(numRecv, 1) * sizeof(FofPair)) + std::max<uint64_t>(numRecv, 1) * 8));
+        const size_t pairBytes = alignUp(std::max<uint64_t>(numRecv, 1) * sizeof(FofPair));
+        CS_TRY(fofRecv_.ensure(ctx_, pairBytes + std::max<uint64_t>(numRecv, 1) * 8));
         auto* pairsRecv  = fofRecv_.as<FofPair>();
-        auto* answersOut = reinterpret_cast<uint64_t*>(fofRecv_.as<char>() + alignUp(std::max<uint64_t>(numRecv, 1) * sizeof(FofPair)));
+        auto* answersOut = sliceOf<uint64_t>(fofRecv_, pairBytes);
         CS_TRY(fofAllToAll(pairs, sendCounts, pairsRecv, recvCounts, sizeof(FofPair), "all_to_all_v (fof pairs)"));
-        CS_TRY(fofOwnerTotals(ctx_, pairsRecv, uint32_t(numRecv), offset[rank_], na, totals, answersOut));
+        CS_TRY(fofOwnerTotals(ctx_, pairsRecv, uint32_t(numRecv), offset[rank_], na, sliceOf<uint64_t>(fofWork_, s.totals), answersOut));
         CS_TRY(fofAllToAll(answersOut, recvCounts, answers, sendCounts, 8, "all_to_all_v (fof totals)"));
-        fofSizesFromAnswers(ctx_, values, answers, numPairs, comp, si, ei, componentTotals, fofSizes_.as<uint64_t>());
+        fofSizesFromAnswers(ctx_, values, answers, numPairs, comp, si, ei, sliceOf<uint64_t>(fofWork_, s.componentTotals),
+                            fofSizes_.as<uint64_t>());
         CS_HIP(ctx_, hipGetLastError());
         return exchangeHalos(fofSizes_.p, 8);
+    }
+
+    // ---- fofCatalog(), stage by stage
+
+    //! the slices of catWork_ for the sender's n labels, and those of catRecv_ for the owner's n records
+    struct CatSendSlices { size_t keys, keysAlt, values, valuesAlt, temp, tempBytes, work, runStart, runLabels, end; };
+    static CatSendSlices catSendSlices(size_t n)
+    {
+        const size_t tempBytes = cstone_hip_sort_pairs_temp_bytes(64, n);
+        Slicer w;
+        return {w.take(n * 8), w.take(n * 8), w.take(n * 4), w.take(n * 4), w.take(tempBytes + 256), tempBytes,
+                w.take((2 * n + 64) * 4), w.take((n + 1) * 4), w.take(n * 8), w.at};
+    }
+    struct CatOwnerSlices
+    {
+        size_t records, keys, keysAlt, order, orderAlt, temp, tempBytes, work, runStart, combined, keep, pos, total, end;
+    };
+    static CatOwnerSlices catOwnerSlices(size_t n)
+    {
+        const size_t tempBytes = cstone_hip_sort_pairs_temp_bytes(64, n);
+        Slicer w;
+        return {w.take(n * sizeof(FofPartial)), w.take(n * 8), w.take(n * 8), w.take(n * 4), w.take(n * 4), w.take(tempBytes + 256),
+                tempBytes, w.take((2 * n + 64) * 4), w.take((n + 1) * 4), w.take(n * sizeof(FofPartial)), w.take(n * 4),
+                w.take(n * 4), w.take(256), w.at};
+    }
+    //! catScal_: the owners' first ids at byte 256, behind them the bounds of their records -- sized by the number of ranks
+    size_t catBoundsAt() const { return 256 + alignUp(size_t(P_) * 8); }
+
+    //! What the stages of one fofCatalog() share: the caller's arguments and what the stages before have decided
+    struct CatalogState
+    {
+        const void *x, *y, *z, *m;
+        int massBits;
+        const void *vx, *vy, *vz;
+        const uint64_t* labels;
+        uint64_t minMembers;
+        size_t capacity;
+        uint64_t *groupLabels, *groupSizes;
+        void *mass, *center, *velocity, *radius;
+        uint32_t *flags, *numGroupsHost;
+        int nv = 0;                    // velocity components given: 0 or 3
+        uint32_t si = 0, ei = 0, na = 0;
+        uint64_t trouble = FINE;
+        CatSendSlices snd{};
+        uint32_t runs[2] = {0, 0};     // distinct labels here, labels outside [0, total)
+        std::vector<uint64_t> sendCounts, recvCounts; // records per owner, records per source rank
+        uint64_t numRecv = 0;
+        CatOwnerSlices own{};
+        uint32_t ownRuns = 0;          // distinct labels among the records: groups before the filter
+    };
+
+    //! what is the same on every rank: refused before any collective
+    int catalogRefuseEverywhere(CatalogState& s)
+    {
+        if (firstCall_) return fail(ctx_, CSTONE_E_ARG, "domain_mr_fof_catalog: no sync yet");
+        if (fofOffsetSync_ != syncs_ || fofOffset_.size() != size_t(P_) + 1)
+            return fail(ctx_, CSTONE_E_ARG, "domain_mr_fof_catalog: no domain_mr_fof since the last sync");
+        s.nv = (s.vx ? 1 : 0) + (s.vy ? 1 : 0) + (s.vz ? 1 : 0);
+        if ((s.massBits != 32 && s.massBits != 64) || (s.nv != 0 && s.nv != 3) || !s.numGroupsHost)
+            return fail(ctx_, CSTONE_E_ARG, "domain_mr_fof_catalog: bad argument");
+        if (s.minMembers == 0) s.minMembers = 1;
+        s.si = view_.start_index, s.ei = view_.end_index, s.na = s.ei - s.si;
+        return CSTONE_OK;
+    }
+
+    //! rank-local trouble: collected, not returned
+    void catalogLocalTrouble(CatalogState& s)
+    {
+        if (s.na && (!s.x || !s.y || !s.z || !s.m || !s.labels || !s.groupLabels || !s.groupSizes || !s.mass || !s.center ||
+                     (s.nv == 3 && !s.velocity)))
+            s.trouble = NULL_ARRAY;
+        else if (s.na >= (1u << 30)) s.trouble = LOCAL_STEP;
+        s.snd = catSendSlices(std::max<uint32_t>(s.na, 1));
+        if (!s.trouble && (catWork_.ensure(ctx_, s.snd.end) || catPart_.ensure(ctx_, sizeof(FofPartial)) ||
+                           catScal_.ensure(ctx_, catBoundsAt() + alignUp((size_t(P_) + 1) * 4))))
+            s.trouble = NO_MEMORY;
+        s.sendCounts.assign(P_, 0);
+    }
+
+    //! the local steps: their failure is trouble too, and a rank in trouble sends nothing
+    void catalogLocalSteps(CatalogState& s)
+    {
+        if (s.trouble || !s.na) return;
+        const int rc = catalogPartials(s);
+        if (rc != CSTONE_OK) s.trouble = rc == CSTONE_E_HIP ? NO_MEMORY : LOCAL_STEP;
+        else if (s.runs[1]) s.trouble = BAD_LABEL;
+        if (s.trouble) std::fill(s.sendCounts.begin(), s.sendCounts.end(), uint64_t(0));
+    }
+
+    //! ... one partial per distinct label of the assigned range, in label order, and how many of them each owner gets
+    int catalogPartials(CatalogState& s)
+    {
+        auto* keys = sliceOf<uint64_t>(catWork_, s.snd.keys);
+        auto* values = sliceOf<uint32_t>(catWork_, s.snd.values);
+        auto* runStart = sliceOf<uint32_t>(catWork_, s.snd.runStart);
+        auto* runLabels = sliceOf<uint64_t>(catWork_, s.snd.runLabels);
+        CS_HIP(ctx_, hipMemcpyAsync(keys, s.labels + s.si, size_t(s.na) * 8, hipMemcpyDeviceToDevice, ctx_->stream));
+        CS_TRY(cstone_hip_sequence_u32(ctx_, values, s.na, s.si));
+        // stable: the members of a label stay in ascending order, its first member is its lowest index
+        CS_TRY(cstone_hip_sort_pairs(ctx_, 64, keys, values, s.na, sliceOf<char>(catWork_, s.snd.keysAlt),
+                                     sliceOf<uint32_t>(catWork_, s.snd.valuesAlt), sliceOf<char>(catWork_, s.snd.temp), s.snd.tempBytes));
+        CS_TRY(fofRunsU64(ctx_, keys, s.na, fofOffset_[P_], sliceOf<uint32_t>(catWork_, s.snd.work), runStart, runLabels, s.runs));
+        if (s.runs[1]) return CSTONE_OK; // (reported as BAD_LABEL)
+        if (catPart_.ensure(ctx_, size_t(s.runs[0]) * sizeof(FofPartial))) return CSTONE_E_HIP;
+        CS_TRY(fofPropsReduce(ctx_, rb, s.massBits, s.x, s.y, s.z, s.m, s.vx, s.vy, s.vz, view_.box, runStart, values, s.runs[0],
+                              FofGroupOut{}, catPart_.as<FofPartial>(), keys));
+        return countsPerOwner(runLabels, s.runs[0], fofOffset_, sliceOf<uint64_t>(catScal_, 256),
+                              sliceOf<uint32_t>(catScal_, catBoundsAt()), s.sendCounts);
+    }
+
+    //! collective 1: the counts per owner and the status; behind the agreement what arrives here
+    int catalogAgree(CatalogState& s)
+    {
+        std::vector<uint64_t> rows, row(s.sendCounts);
+        row.push_back(s.trouble);
+        CS_TRY(stageRow(row.data(), row.size(), rows));
+        CS_TRY(gatherRows(row.size(), "all_gather (fof catalogue)", rows));
+        static const char* const why[NUM_TROUBLES] = {"", "null array", "", "out of device memory", "a label outside [0, total)",
+                                                      "a local step failed"};
+        CS_TRY(agree("domain_mr_fof_catalog", rows, row.size(), P_, why));
+        s.numRecv = recvColumn(rows, row.size(), s.recvCounts);
+        if (s.numRecv >= (uint64_t(1) << 30))
+            return fail(ctx_, CSTONE_E_CAPACITY, "domain_mr_fof_catalog: %llu records for one owner", (unsigned long long)s.numRecv);
+        return CSTONE_OK;
+    }
+
+    //! collective 2: the records to the owners.  How much arrives is known only now, behind the one agreement: a rank whose
+    //! receive buffer cannot be had (or whose share exceeds 2^30 records) returns ALONE, and the others then wait in the
+    //! all_to_all_v -- as in the size protocol of friendsOfFriends
+    int catalogExchange(CatalogState& s)
+    {
+        s.own = catOwnerSlices(std::max<uint64_t>(s.numRecv, 1));
+        CS_TRY(catRecv_.ensure(ctx_, s.own.end));
+        CS_TRY(fofAllToAll(catPart_.p, s.sendCounts, sliceOf<FofPartial>(catRecv_, s.own.records), s.recvCounts, sizeof(FofPartial),
+                           "all_to_all_v (fof catalogue)"));
+        *s.numGroupsHost = 0;
+        return CSTONE_OK;
+    }
+
+    //! the owner: stable sort by label (the records arrive by source rank), combine, filter
+    int catalogCombine(CatalogState& s)
+    {
+        auto* records = sliceOf<FofPartial>(catRecv_, s.own.records);
+        auto* keys = sliceOf<uint64_t>(catRecv_, s.own.keys);
+        auto* order = sliceOf<uint32_t>(catRecv_, s.own.order);
+        auto* runStart = sliceOf<uint32_t>(catRecv_, s.own.runStart);
+        auto* keep = sliceOf<uint32_t>(catRecv_, s.own.keep);
+        fofPartialLabels(ctx_, records, uint32_t(s.numRecv), keys);
+        CS_TRY(cstone_hip_sequence_u32(ctx_, order, s.numRecv, 0));
+        CS_TRY(cstone_hip_sort_pairs(ctx_, 64, keys, order, s.numRecv, sliceOf<char>(catRecv_, s.own.keysAlt),
+                                     sliceOf<uint32_t>(catRecv_, s.own.orderAlt), sliceOf<char>(catRecv_, s.own.temp), s.own.tempBytes));
+        uint32_t ownRuns[2] = {0, 0};
+        CS_TRY(fofRunsU64(ctx_, keys, uint32_t(s.numRecv), ~uint64_t(0), sliceOf<uint32_t>(catRecv_, s.own.work), runStart, nullptr,
+                          ownRuns));
+        s.ownRuns = ownRuns[0];
+        CS_TRY(fofCombinePartials(ctx_, rb, s.x, s.y, s.z, view_.box, records, order, runStart, s.ownRuns, fofOffset_[rank_], s.si,
+                                  s.na, s.minMembers, sliceOf<FofPartial>(catRecv_, s.own.combined), keep));
+        CS_TRY(arenaReserve(ctx_, scanArenaBytes(s.ownRuns) + 1024));
+        const int scanned = scanU32(ctx_, keep, sliceOf<uint32_t>(catRecv_, s.own.pos), s.ownRuns, 0u, false,
+                                    sliceOf<uint32_t>(catRecv_, s.own.total));
+        arenaReset(ctx_);
+        return scanned;
+    }
+
+    //! finish: how many groups are kept, the capacity judged behind both collectives, the kept groups to the caller's arrays
+    int catalogFinish(CatalogState& s)
+    {
+        uint32_t kept = 0;
+        CS_TRY(copyToHost(ctx_, &kept, sliceOf<uint32_t>(catRecv_, s.own.total), 4));
+        CS_TRY(cstone_hip_ctx_sync(ctx_)); // the sticky device-side error word (a record whose label is not mine)
+        *s.numGroupsHost = kept;
+        if (kept > s.capacity)
+            return fail(ctx_, CSTONE_E_CAPACITY, "domain_mr_fof_catalog: %u groups, capacity %zu", kept, s.capacity);
+        return fofFinishCombined(ctx_, rb, s.nv == 3, view_.box, sliceOf<FofPartial>(catRecv_, s.own.combined),
+                                 sliceOf<uint32_t>(catRecv_, s.own.keep), sliceOf<uint32_t>(catRecv_, s.own.pos), s.ownRuns,
+                                 FofGroupOut{s.mass, s.center, s.velocity, s.radius, s.flags, s.groupLabels, s.groupSizes});
+    }
+
+    // ---- sphereProfiles(), stage by stage
+
+    //! What the stages of one sphereProfiles() share: the caller's arguments and what the stages before have decided
+    struct ProfilesState
+    {
+        const void *x, *y, *z, *w;
+        int massBits;
+        const void *queryCenters, *queryScale;
+        uint32_t numQueries;
+        const double* edgesHost;
+        int numBins;
+        uint64_t* counts;
+        double* sums;
+        uint32_t* flags;
+        uint32_t si = 0, ei = 0, na = 0;
+        size_t cells     = 0; // numQueries x numBins
+        uint64_t trouble = FINE;
+        cstone_hip_domain_mr_octree t{}; // my octree; all null on a rank without particles
+        bool globalW = false;            // some rank with particles has a w: the sums take part in the all-reduce
+    };
+
+    //! what is the same on every rank: refused before any collective
+    int profilesRefuseEverywhere(ProfilesState& s)
+    {
+        if (firstCall_) return fail(ctx_, CSTONE_E_ARG, "domain_mr_sphere_profiles: no sync yet");
+        if (!sphereEdgesOk(s.edgesHost, s.numBins)) return fail(ctx_, CSTONE_E_ARG, "domain_mr_sphere_profiles: bad edges");
+        if (s.w && s.massBits != 32 && s.massBits != 64) return fail(ctx_, CSTONE_E_ARG, "domain_mr_sphere_profiles: bad mass_bits");
+        s.si = view_.start_index, s.ei = view_.end_index, s.na = s.ei - s.si;
+        s.cells = size_t(s.numQueries) * size_t(s.numBins);
+        return CSTONE_OK;
+    }
+
+    //! one rank: the single-rank call on my octree, no agreement and no operand
+    int profilesOnOneRank(ProfilesState& s)
+    {
+        if (s.numQueries == 0) return CSTONE_OK;
+        CS_TRY(octree(&s.t));
+        return cstone_hip_sphere_profiles(ctx_, rb, s.massBits, s.x, s.y, s.z, s.w, s.si, s.ei, &view_.box, s.t.child_offsets,
+                                          s.t.internal_to_leaf, s.t.layout, s.t.centers, s.t.sizes, s.queryCenters, s.queryScale,
+                                          s.numQueries, s.edgesHost, s.numBins, s.counts, s.sums, s.flags);
+    }
+
+    //! rank-local trouble: collected, not returned
+    void profilesLocalTrouble(ProfilesState& s)
+    {
+        if (s.numQueries && (!s.queryCenters || !s.counts || (s.w && !s.sums) || (s.na && (!s.x || !s.y || !s.z))))
+            s.trouble = NULL_ARRAY;
+        else if (sphereBuf_.ensure(ctx_, std::max<size_t>(2 * s.cells * sizeof(double), 256))) s.trouble = NO_MEMORY;
+        else if (s.na && octree(&s.t)) s.trouble = LOCAL_STEP;
+    }
+
+    //! one all-gather of {status, Q, NB, w given}: every rank fails together, also where the ranks disagree on the last three
+    int profilesAgree(ProfilesState& s)
+    {
+        enum : uint64_t { W_NONE = 0, W_GIVEN = 1, W_ANY = 2 }; // a rank without particles goes with the others
+        const uint64_t row[4] = {s.trouble, s.numQueries, uint64_t(s.numBins), s.w ? W_GIVEN : s.na ? W_NONE : W_ANY};
+        std::vector<uint64_t> rows;
+        CS_TRY(stageRow(row, 4, rows));
+        CS_TRY(gatherRows(4, "all_gather (sphere profiles)", rows));
+        uint64_t wMode = W_ANY;
+        for (int p = 0; p < P_; ++p)
+        {
+            uint64_t* r = rows.data() + 4 * size_t(p);
+            if (r[0] == FINE && (r[1] != rows[1] || r[2] != rows[2])) r[0] = MISMATCH;
+            if (r[0] != FINE || r[3] == W_ANY) continue;
+            if (wMode == W_ANY) wMode = r[3];
+            else if (wMode != r[3]) r[0] = MISMATCH;
+        }
+        static const char* const why[NUM_TROUBLES] = {"", "null array", "", "out of device memory", "", "no octree",
+                                                      "the ranks disagree on num_queries, num_bins or whether there is a w"};
+        s.globalW = wMode == W_GIVEN;
+        return agree("domain_mr_sphere_profiles", rows, 4, 0, why);
+    }
+
+    //! the local profiles, into the caller's arrays.  A rank without particles has nothing to read: its empty range zeroes
+    //! the rows and sets the flags, and the operand itself stands in for the arrays it may not have
+    int profilesLocal(ProfilesState& s)
+    {
+        const void* dummy = sphereBuf_.p;
+        auto nz           = [&](const void* ptr) { return ptr ? ptr : dummy; };
+        return cstone_hip_sphere_profiles(ctx_, rb, s.massBits, nz(s.x), nz(s.y), nz(s.z), s.w, s.si, s.ei, &view_.box,
+                                          static_cast<const int32_t*>(nz(s.t.child_offsets)),
+                                          static_cast<const int32_t*>(nz(s.t.internal_to_leaf)),
+                                          static_cast<const uint32_t*>(nz(s.t.layout)), nz(s.t.centers), nz(s.t.sizes),
+                                          s.queryCenters, s.queryScale, s.numQueries, s.edgesHost, s.numBins, s.counts, s.sums,
+                                          s.flags);
+    }
+
+    //! one all-reduce: {counts as doubles, sums}
+    int profilesReduce(ProfilesState& s)
+    {
+        double* buf = sphereBuf_.as<double>();
+        if (s.globalW && !s.w) CS_HIP(ctx_, hipMemsetAsync(buf + s.cells, 0, s.cells * sizeof(double), ctx_->stream));
+        spherePackRows(ctx_, s.counts, s.w ? s.sums : nullptr, s.cells, buf);
+        CS_TRY(callComm(comm_.all_reduce(comm_.user, buf, (s.globalW ? 2 : 1) * s.cells, 0, 0), "all_reduce (sphere profiles)"));
+        sphereUnpackRows(ctx_, buf, s.cells, s.counts, s.globalW ? s.sums : nullptr);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess)
+            return fail(ctx_, CSTONE_E_HIP, "domain_mr_sphere_profiles: %s", hipGetErrorString(e));
+        return CSTONE_OK;
     }
 
     cstone_hip_ctx* ctx_;

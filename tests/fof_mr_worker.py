@@ -57,14 +57,14 @@ class Run:
         dom.exchange_halos(r["index"])
         return r
 
-    def raw_call(self, dom, r, b, max_rounds=0):
+    def raw_call(self, dom, r, b, max_rounds=0, null=()):
         """the C entry on arrays filled with a sentinel: (return code, labels and sizes still hold the sentinel)"""
         n = r["x"].numel() if r is not None else 0
         labels = torch.full((n,), SENT, dtype=torch.int64, device="cuda")
         sizes = torch.full((n,), SENT, dtype=torch.int64, device="cuda")
         ptr = (lambda t: t.data_ptr() if n else None)
         ng, rounds = C.c_uint64(12345), C.c_uint32(54321)
-        xyz = [ptr(r[c]) for c in "xyz"] if r is not None else [None] * 3
+        xyz = [ptr(r[c]) if c not in null else None for c in "xyz"] if r is not None else [None] * 3
         rc = self.hip.lib.cstone_hip_domain_mr_fof(dom.h, *xyz, b, max_rounds, ptr(labels), ptr(sizes), C.byref(ng),
                                                    C.byref(rounds))
         dom.coll.error = None
@@ -72,8 +72,8 @@ class Run:
         clean = bool((labels == SENT).all()) and bool((sizes == SENT).all()) and (ng.value, rounds.value) == (12345, 54321)
         return rc, clean
 
-    def refused(self, dom, r, b, what, code=E_ARG, max_rounds=0):
-        rc, clean = self.raw_call(dom, r, b, max_rounds)
+    def refused(self, dom, r, b, what, code=E_ARG, max_rounds=0, null=()):
+        rc, clean = self.raw_call(dom, r, b, max_rounds, null)
         if rc != code:
             self.fail(what, f"returned {rc}, {code} was expected")
         if not clean:
@@ -174,6 +174,10 @@ class Run:
             self.refused(dom, r, 0.5, f"{what}, b of half the periodic edge")
         self.refused(dom, r, float("nan"), f"{what}, a NaN")
         self.refused(dom, r, 0.0, f"{what}, b = 0")
+        # a null x on the last rank only: that rank's own refusal, the others learn of it; nothing is written
+        last = self.rank == self.P - 1
+        self.refused(dom, r, b, f"{what}, a null x on the last rank", code=E_ARG if last else E_INTERNAL,
+                     null=("x",) if last else ())
         if name == "serpentine" and self.P > 1:
             self.refused(dom, r, b, f"{what}, max_rounds = 1", code=E_INTERNAL, max_rounds=1)
         res = dom.fof(r["x"], r["y"], r["z"], b)
