@@ -521,6 +521,7 @@ int cstone_hip_lower_bound_value(cstone_hip_ctx* ctx, int kind, const void* data
                                  uint64_t* index_host)
 {
     if (!ctx || !value_host || !index_host || (n && !data)) return fail(ctx, CSTONE_E_ARG, "lower_bound_value: bad argument");
+    if (kind < 0 || kind > 4) return fail(ctx, CSTONE_E_ARG, "lower_bound_value: kind %d unsupported", kind);
     *index_host = 0;
     if (n == 0) return CSTONE_OK;
     auto* out = reinterpret_cast<unsigned long long*>(ctx->devScalars + 12);

@@ -177,7 +177,9 @@ extern "C"
     int cstone_hip_sequence_u32(cstone_hip_ctx* ctx, uint32_t* out, size_t n, uint32_t init);
 
     /* gatherGpu / scatterGpu (R/primitives/primitives_gpu.h:48-56): dst[i] = src[map[i]] resp.
-     * dst[map[i]] = src[i] for elements of elem_bytes in {1,2,4,8,12,16,24,32} */
+     * dst[map[i]] = src[i] for elements of elem_bytes in {1,2,4,8,12,16,24,32,64} (64: a multipole of 8 doubles); any
+     * other size is CSTONE_E_ARG.  src and dst are aligned as the element type is accessed: to elem_bytes up to 8, to 4
+     * for 12 (Vec3<float>), to 8 for 24 (Vec3<double>), to 16 for 16, 32 and 64; a misaligned array is CSTONE_E_ARG */
     int cstone_hip_gather(cstone_hip_ctx* ctx, int elem_bytes, const uint32_t* map, size_t n, const void* src,
                           void* dst);
     int cstone_hip_scatter(cstone_hip_ctx* ctx, int elem_bytes, const uint32_t* map, size_t n, const void* src,
@@ -197,7 +199,8 @@ extern "C"
     int cstone_hip_merge_positions(cstone_hip_ctx* ctx, int key_bits, const void* a, size_t na, const void* b,
                                    size_t nb, uint32_t offset, uint32_t* pos_a, uint32_t* pos_b);
 
-    /* MinMaxGpu (R/primitives/primitives_gpu.h:58-62): out_host = {min, max} as doubles (exact for float) */
+    /* MinMaxGpu (R/primitives/primitives_gpu.h:58-62): out_host = {min, max} as doubles (exact for float); n >= 1, an
+     * empty range has no extremes and is CSTONE_E_ARG */
     int cstone_hip_minmax(cstone_hip_ctx* ctx, int real_bits, const void* x, size_t n, double* out2_host);
     /* the same for 1..3 equally long arrays (the x, y, z of the bounding box, R/sfc/box_mpi.hpp:40-70) in one launch and
      * one read-back: out_host = {min0, max0, min1, max1, ...} */
@@ -232,7 +235,7 @@ extern "C"
      *                 uint32|uint64
      * gather_ranges : gatherRanges (R/halos/gather_halos_gpu.h): buffer[i] = src[range_offsets[r] + i - range_scan[r]]
      *                 for the range r with range_scan[r] <= i < range_scan[r+1]; indices uint32 | uint64 (index_bits),
-     *                 elements of 1..32 bytes as gather
+     *                 elements of {1,2,4,8,12,16,24,32} bytes: gather's sizes up to 32, 64 is CSTONE_E_ARG here
      * lower_bound_value : lowerBoundGpu, scalar form (:67-68); kind 0 u32, 1 u64, 2 i32, 3 i64, 4 f32
      * sort_keys     : sortGpu (:91-92), ascending keys-only sort (the key buffer of the reference's signature is not
      *                 needed: scratch comes from the context)
