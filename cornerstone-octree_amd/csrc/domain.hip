@@ -144,6 +144,7 @@ struct DomainBase
                                const void* queryScale, uint32_t numQueries, const double* edgesHost, int numBins,
                                uint64_t* counts, double* sums, uint32_t* flags) = 0;
     virtual void stats(cstone_hip_domain_stats* out)     = 0;
+    virtual void leafTableStats(uint32_t* used, uint32_t* rejected) = 0;
 };
 
 template<class K, class T>
@@ -167,11 +168,14 @@ public:
     int sync(void** keysPP, void** xPP, void** yPP, void** zPP, void** hPP, size_t n, void** scratchAll, int numScratch,
              void** props, const int* propBytes, int numProps) override
     {
+        if (n == 0 || (!firstCall_ && n != bufSize_)) earlyTableStale_ = true;
         if (n == 0) return fail(ctx_, CSTONE_E_ARG, "domain_sync: no particles");
         if (!firstCall_ && n != bufSize_)
             return fail(ctx_, CSTONE_E_ARG, "Domain sync: input array sizes are inconsistent (%zu != %u)", n, bufSize_);
         SyncState s{xPP, yPP, zPP, hPP, static_cast<K*>(*keysPP), n, scratchAll, numScratch, props, propBytes, numProps};
         const int rc = runStages(s);
+        // (a leaf table queued for the next sync is not trusted behind a sync that failed, whatever it failed at)
+        if (rc != CSTONE_OK) earlyTableStale_ = true;
         // a sync that failed behind a fork onto the tree stream joins it: nothing of this sync is in flight afterwards
         if (rc != CSTONE_OK && treeInFlight_)
         {
@@ -399,6 +403,11 @@ public:
         out->full_sort_fallbacks = uint32_t(fullSortFallbacks_);
         out->last_movers         = lastMovers_;
     }
+    void leafTableStats(uint32_t* used, uint32_t* rejected) override
+    {
+        *used     = earlyTablesUsed_;
+        *rejected = earlyTablesRejected_;
+    }
 
     float haloSearchExt_ = 1.0f;
 
@@ -578,23 +587,49 @@ private:
         // do): kept selectable, not the default.
         const bool fusedLeafPass = std::getenv("CSTONE_FUSED_LEAF_PASS") != nullptr; // (read per sync: tests switch it)
         const bool carryFields   = s.numScratch >= 4 && fusedLeafPass;
+        // The leaf table: the one the previous sync queued behind its halo search (queueLeafTable) if it was built for
+        // exactly the state this attempt starts from -- the same n and leaves, no failed sync since; a sync that does not
+        // attempt leaves it unused (it would describe a tree and a layout that this sync replaces).  Otherwise the table
+        // is built here, in front of the encode -- always, unless CSTONE_EARLY_LEAF_TABLE=1 (earlyLeafTableOn).
+        const bool tableQueued = earlyTable_;
+        const bool tableFits   = tableQueued && !earlyTableStale_ && attempt && earlyTableN_ == s.n &&
+                               earlyTableLeaves_ == fLeaves_ && earlyLeafTableOn();
+        earlyTable_ = earlyTableStale_ = false;
+        if (tableQueued) ++(tableFits ? earlyTablesUsed_ : earlyTablesRejected_);
         if (!attempt) return CSTONE_OK;
-        CS_TRY(resort_.prepare(ctx_, fTree_.as<K>(), layout_.as<uint32_t>(), fLeaves_, s.n, keysAlt_.as<K>(), true,
-                               carryFields ? rb : 0));
+        if (!s.noHoist) CS_TRY(ensureTreeStream(ctx_));
+        if (tableFits)
+        {
+            // (nothing of this attempt reads the old tree on this stream: the tree stream may start at once)
+            if (!s.noHoist) CS_HIP(ctx_, hipEventRecord(ctx_->evTreeFork, ctx_->stream));
+            CS_TRY(resort_.beginAttempt(ctx_, keysAlt_.as<K>(), carryFields ? rb : 0));
+        }
+        else
+        {
+            CS_TRY(resort_.prepare(ctx_, fTree_.as<K>(), layout_.as<uint32_t>(), fLeaves_, s.n, keysAlt_.as<K>(), true,
+                                   carryFields ? rb : 0));
+            // (fillCompactLeavesKernel was the last reader of the old tree on this stream: the tree stream starts here)
+            if (!s.noHoist) CS_HIP(ctx_, hipEventRecord(ctx_->evTreeFork, ctx_->stream));
+        }
         const ResortArgs<K> ra = resort_.args();
         bool done              = false;
-        if (!s.noHoist)
-        {
-            // (fillCompactLeavesKernel was the last reader of the old tree on this stream: the tree stream starts here)
-            CS_TRY(ensureTreeStream(ctx_));
-            CS_HIP(ctx_, hipEventRecord(ctx_->evTreeFork, ctx_->stream));
-        }
         CS_TRY(computeKeysResort(ctx_, curve_, kb, rb, *s.xPP, *s.yPP, *s.zPP, s.keys, s.n, box_, &ra,
                                  s.speculate ? extentsDev() : nullptr, &done));
         if (!done) return CSTONE_OK;
         CS_TRY(resort_.binMovers(ctx_, tileLeaves));
         // one read-back: the extents (slots 16..27) and what the re-sort found (28..31)
         CS_TRY(copyToPinned(ctx_, ctx_->hostScalars + 16, ctx_->devScalars + 16, 16 * sizeof(int)));
+        // The movers go into their bins behind that copy, while the host looks at what it brought: the kernel reads the
+        // count and the flags itself and needs nothing from the host.  The host then waits for the copy alone, not for the
+        // stream.  Only with CSTONE_EARLY_PLACE=1 (it did not measure as a gain); by default the
+        // movers are placed from the leaf pass's launch sequence, once the host knows the count
+        const bool earlyPlace = switchOn("CSTONE_EARLY_PLACE", "CSTONE_NO_EARLY_PLACE");
+        if (earlyPlace)
+        {
+            if (!ctx_->evReadBack) CS_HIP(ctx_, hipEventCreateWithFlags(&ctx_->evReadBack, hipEventDisableTiming));
+            CS_HIP(ctx_, hipEventRecord(ctx_->evReadBack, ctx_->stream));
+            CS_TRY(resort_.placeMoversEarly(ctx_, lastMovers_));
+        }
         // The device is busy with the encode and the mover bins from here on, and the host has nothing more to queue
         // before it has seen what they found.  The structural half of the focus-tree update follows from the tree and the counts of
         // the previous sync alone, and whatever becomes of the re-sort, this sync needs it: the node ops go to the tree
@@ -611,7 +646,8 @@ private:
                 CS_TRY(forkFocusRebuild(s));
             }
         }
-        CS_HIP(ctx_, hipStreamSynchronize(ctx_->stream));
+        if (earlyPlace) { CS_HIP(ctx_, hipEventSynchronize(ctx_->evReadBack)); }
+        else { CS_HIP(ctx_, hipStreamSynchronize(ctx_->stream)); }
         // (CSTONE_TREE_HOIST_LATE: the node ops on the tree stream have long finished, no wait of its own)
         if (s.opsOnTree && !s.opsTaken) CS_TRY(takeFocusOps(s));
         cstone_box next = box_;
@@ -899,8 +935,40 @@ private:
         CS_HIP(ctx_, hipMemsetAsync(flags_.p, 0, size_t(L) * sizeof(int), ctx_->stream));
         // one rank: every leaf is assigned, no halo leaves: layout = exclusive scan of the leaf counts (layout.hpp:150-165),
         // which is the inclusive scan written above shifted by one.
-        return cstone_hip_find_halos(ctx_, curve_, kb, rb, fPrefixes_.p, fChild_.as<int32_t>(), fItl_.as<int32_t>(),
-                                     fTree_.p, radii_.as<float>(), &box_, 0, L, flags_.as<int32_t>());
+        CS_TRY(cstone_hip_find_halos(ctx_, curve_, kb, rb, fPrefixes_.p, fChild_.as<int32_t>(), fItl_.as<int32_t>(),
+                                     fTree_.p, radii_.as<float>(), &box_, 0, L, flags_.as<int32_t>()));
+        return queueLeafTable(s);
+    }
+
+    //! an experiment that is off unless `on` is set to 1 (and `off`, the switch's first name, is not set)
+    static bool switchOn(const char* on, const char* off)
+    {
+        const char* e = std::getenv(on);
+        return e && e[0] == '1' && std::getenv(off) == nullptr;
+    }
+    static bool earlyLeafTableOn() { return switchOn("CSTONE_EARLY_LEAF_TABLE", "CSTONE_NO_EARLY_LEAF_TABLE"); }
+
+    /*! The leaf table of the NEXT sync's re-sort (resort.hpp, prepareTable).  It follows from the tree, the layout and
+     *  the particle count this sync leaves behind, and the main stream has nothing more to do from here on but wait for
+     *  the gather of x, y, z on the second stream: built here, the table's six small launches are off the next sync's
+     *  critical path, where nothing can run beside them (beside the gather they take 200 us instead of 75).  It stands behind the halo search and with it behind
+     *  countLeaves and radiiOfLeaves, the last readers of the table this sync was re-sorted with; finishSync
+     *  synchronises, so it is complete before the next sync's tree stream may touch the tree.  Queued only when the next
+     *  sync may attempt a re-sort as far as is known now; tryResort decides whether the table still fits.
+     *  OFF by default: the headline did not move by more than its noise; CSTONE_EARLY_LEAF_TABLE=1
+     *  turns it on, read per sync. */
+    int queueLeafTable(const SyncState& s)
+    {
+        earlyTable_ = false;
+        if (!earlyLeafTableOn()) return CSTONE_OK;
+        if (LeafResort<K>::leavesPerTile(bucketFocus_) == 0 || !mayResort(sortMode_) || resortBackoff_ != 0) return CSTONE_OK;
+        if (fLeaves_ <= 0 || layoutLeaves_ != fLeaves_ || s.numAssigned == 0) return CSTONE_OK;
+        CS_TRY(resort_.prepareTable(ctx_, fTree_.as<K>(), layout_.as<uint32_t>(), fLeaves_, s.numAssigned, true));
+        earlyTable_       = true;
+        earlyTableStale_  = false;
+        earlyTableN_      = s.numAssigned;
+        earlyTableLeaves_ = fLeaves_;
+        return CSTONE_OK;
     }
 
     //! updateLayout (domain.hpp:542-604): keys already sit at offset 0; gather the unordered arrays
@@ -1097,6 +1165,13 @@ private:
     LeafResort<K> resort_;
     int resortBackoff_ = 0, resorts_ = 0, resortFallbacks_ = 0;
     bool resortedThisSync_ = false;
+    // the leaf table the last sync queued for this one (queueLeafTable): the state it was built for, and how the tables
+    // built so far fared
+    bool earlyTable_       = false;
+    bool earlyTableStale_  = false; // a sync failed since it was queued
+    size_t earlyTableN_    = 0;
+    int earlyTableLeaves_  = 0;
+    uint32_t earlyTablesUsed_ = 0, earlyTablesRejected_ = 0;
     DevBuf gTree_, gCounts_;
     int gCap_ = 0, gLeaves_ = 0;
     GlobalTreeHost<K> gHost_; // host copies of the global tree and its counts (the host makes its update step)
@@ -1285,6 +1360,13 @@ int cstone_hip_domain_stats_get(cstone_hip_domain* dom, cstone_hip_domain_stats*
 {
     if (!dom || !out) return CSTONE_E_ARG;
     dom->impl->stats(out);
+    return CSTONE_OK;
+}
+
+int cstone_hip_domain_leaf_table_stats(cstone_hip_domain* dom, uint32_t* used, uint32_t* rejected)
+{
+    if (!dom || !used || !rejected) return CSTONE_E_ARG;
+    dom->impl->leafTableStats(used, rejected);
     return CSTONE_OK;
 }
 

@@ -191,6 +191,8 @@ __global__ __launch_bounds__(256) void checkTilesKernel(const uint32_t* __restri
     uint32_t t       = blockIdx.x * 256 + threadIdx.x;
     if (t == 0)
     {
+        // (J of a table that keeps it in a buffer of its own goes to the slot the host reads)
+        if (numCompact != (const uint32_t*)scalars + 2) scalars[2] = int(J);
         scalars[0] = int(inOffset[J + 1] - inOffset[J]);
         if (*moverCount > moverCap) atomicOr(&scalars[1], 4);
     }
@@ -217,6 +219,28 @@ __global__ __launch_bounds__(256) void placeMoversKernel(const K* __restrict__ m
     uint32_t at = inOffset[dest[m]] + slot[m];
     binKeys[at] = moverKeys[m];
     binIdx[at]  = moverIdx[m];
+}
+
+//! placeMoversKernel queued before the host has seen the count: the count and the flags are read here (scalars: [1]
+//! flags, [3] movers), a grid sized by the movers the caller expects strides over the list, and an attempt that failed
+//! places nothing
+template<class K>
+__global__ __launch_bounds__(256) void placeMoversEarlyKernel(const K* __restrict__ moverKeys,
+                                                              const uint32_t* __restrict__ moverIdx,
+                                                              const uint32_t* __restrict__ dest,
+                                                              const uint32_t* __restrict__ slot,
+                                                              const int* __restrict__ scalars, uint32_t moverCap,
+                                                              const uint32_t* __restrict__ inOffset,
+                                                              K* __restrict__ binKeys, uint32_t* __restrict__ binIdx)
+{
+    const uint32_t M = uint32_t(scalars[3]);
+    if (M > moverCap || (scalars[1] & 7)) return;
+    for (uint32_t m = blockIdx.x * 256 + threadIdx.x; m < M; m += gridDim.x * 256)
+    {
+        uint32_t at = inOffset[dest[m]] + slot[m];
+        binKeys[at] = moverKeys[m];
+        binIdx[at]  = moverIdx[m];
+    }
 }
 
 /*! The leaf pass.  A workgroup takes G consecutive (non-empty) leaves of the previous sync.  Its LDS slots:
@@ -1365,8 +1389,8 @@ __global__ __launch_bounds__(256) void placeMarkersKernel(const uint32_t* __rest
 } // namespace
 
 template<class K>
-int LeafResort<K>::prepare(cstone_hip_ctx* ctx, const K* tree, const uint32_t* layout, int numLeaves, size_t n,
-                           K* keysOut, bool expectMovers, int fieldBits)
+int LeafResort<K>::buildTable(cstone_hip_ctx* ctx, const K* tree, const uint32_t* layout, int numLeaves, size_t n,
+                              bool expectMovers, uint32_t* numJ)
 {
     StageTimer timer(ctx, CSTONE_STAGE_RESORT_BINS);
     numLeaves_         = numLeaves;
@@ -1390,43 +1414,69 @@ int LeafResort<K>::prepare(cstone_hip_ctx* ctx, const K* tree, const uint32_t* l
     CS_TRY(moverSlot_.ensure(ctx, cap * 4));
     CS_TRY(binKeys_.ensure(ctx, cap * sizeof(K)));
     CS_TRY(binIdx_.ensure(ctx, cap * 4));
-    if (fieldBits) CS_TRY(hmax_.ensure(ctx, ent * size_t(fieldBits / 8)));
-    carryFields_   = fieldBits != 0;
-    boundaryNodes_ = -1;
+    numJ_ = numJ;
 
-    int* scalars = ctx->devScalars + RESORT_SCALARS;
-    CS_HIP(ctx, hipMemsetAsync(scalars, 0, 4 * sizeof(int), ctx->stream)); // [3]: the mover counter
     hipLaunchKernelGGL(leafStartWordsKernel, gridFor(numLeaves, 256), 256, 0, ctx->stream, layout, numLeaves, uint32_t(n),
                        mask_.as<uint64_t>(), popc_.as<uint32_t>(), uint32_t(words));
-    // rank of every word and, in scalars[2], the number of non-empty leaves
+    // rank of every word and, in *numJ, the number of non-empty leaves
     CS_TRY(arenaReserve(ctx, scanArenaBytes(words)));
-    int rc = scanU32(ctx, popc_.as<uint32_t>(), rank_.as<uint32_t>(), words, 0u, false, (uint32_t*)scalars + 2);
+    int rc = scanU32(ctx, popc_.as<uint32_t>(), rank_.as<uint32_t>(), words, 0u, false, numJ);
     arenaReset(ctx);
     CS_TRY(rc);
     hipLaunchKernelGGL(fillCompactLeavesKernel<K>, gridFor(size_t(numLeaves) + 3, 256), 256, 0, ctx->stream, tree, layout,
-                       numLeaves, mask_.as<uint64_t>(), rank_.as<uint32_t>(), (const uint32_t*)scalars + 2, uint32_t(n),
-                       leafLo_.as<K>(), leafPos_.as<uint32_t>(), outCount_.as<uint32_t>(), incoming_.as<uint32_t>());
+                       numLeaves, mask_.as<uint64_t>(), rank_.as<uint32_t>(), numJ_, uint32_t(n), leafLo_.as<K>(),
+                       leafPos_.as<uint32_t>(), outCount_.as<uint32_t>(), incoming_.as<uint32_t>());
     // many movers expected (the previous sync had them): the coarse table that shortens their searches
     haveCoarse_ = expectMovers;
     constexpr uint32_t cells = (1u << RESORT_COARSE_BITS) + 1;
     CS_TRY(coarse_.ensure(ctx, size_t(cells) * 4)); // (4 MB, once: no allocation in the middle of a run)
     if (haveCoarse_)
     {
-        hipLaunchKernelGGL(coarseLeafTableKernel<K>, gridFor(cells, 256), 256, 0, ctx->stream, leafLo_.as<K>(),
-                           (const uint32_t*)scalars + 2, coarse_.as<uint32_t>());
+        hipLaunchKernelGGL(coarseLeafTableKernel<K>, gridFor(cells, 256), 256, 0, ctx->stream, leafLo_.as<K>(), numJ_,
+                           coarse_.as<uint32_t>());
     }
     CS_HIP(ctx, hipGetLastError());
 
-    args_.keysOut    = keysOut;
     args_.leafStart  = mask_.as<uint64_t>();
     args_.leafRank   = rank_.as<uint32_t>();
     args_.leafLo     = leafLo_.as<K>();
     args_.outCount   = outCount_.as<uint32_t>();
     args_.moverKeys  = moverKeys_.as<K>();
     args_.moverIdx   = moverIdx_.as<uint32_t>();
-    args_.moverCount = (uint32_t*)scalars + 3;
+    args_.moverCount = (uint32_t*)(ctx->devScalars + RESORT_SCALARS) + 3;
     args_.moverCap   = uint32_t(cap);
     return CSTONE_OK;
+}
+
+template<class K>
+int LeafResort<K>::prepareTable(cstone_hip_ctx* ctx, const K* tree, const uint32_t* layout, int numLeaves, size_t n,
+                                bool expectMovers)
+{
+    CS_TRY(tableJ_.ensure(ctx, 4 * sizeof(uint32_t)));
+    return buildTable(ctx, tree, layout, numLeaves, n, expectMovers, tableJ_.as<uint32_t>());
+}
+
+template<class K>
+int LeafResort<K>::beginAttempt(cstone_hip_ctx* ctx, K* keysOut, int fieldBits)
+{
+    if (fieldBits) CS_TRY(hmax_.ensure(ctx, (size_t(numLeaves_) + 3) * size_t(fieldBits / 8)));
+    carryFields_   = fieldBits != 0;
+    boundaryNodes_ = -1;
+    moversPlaced_  = false;
+    // ([2] is J: checkTilesKernel copies it there from the table; [3]: the mover counter)
+    CS_HIP(ctx, hipMemsetAsync(ctx->devScalars + RESORT_SCALARS, 0, 4 * sizeof(int), ctx->stream));
+    args_.keysOut = keysOut;
+    return CSTONE_OK;
+}
+
+template<class K>
+int LeafResort<K>::prepare(cstone_hip_ctx* ctx, const K* tree, const uint32_t* layout, int numLeaves, size_t n,
+                           K* keysOut, bool expectMovers, int fieldBits)
+{
+    // (J in the context's slot: the slots are cleared first, the table's scan writes J behind that)
+    numLeaves_ = numLeaves;
+    CS_TRY(beginAttempt(ctx, keysOut, fieldBits));
+    return buildTable(ctx, tree, layout, numLeaves, n, expectMovers, (uint32_t*)(ctx->devScalars + RESORT_SCALARS) + 2);
 }
 
 template<class K>
@@ -1435,7 +1485,7 @@ int LeafResort<K>::binMovers(cstone_hip_ctx* ctx, int leavesPerTile)
     StageTimer timer(ctx, CSTONE_STAGE_RESORT_BINS);
     int* scalars          = ctx->devScalars + RESORT_SCALARS;
     const uint32_t ent    = uint32_t(numLeaves_) + 3;
-    const uint32_t* numJ  = (const uint32_t*)scalars + 2;
+    const uint32_t* numJ  = numJ_;
     const uint32_t* count = (const uint32_t*)scalars + 3;
     hipLaunchKernelGGL(binMoversKernel<K>, unsigned(ctx->numCu) * 16, 256, 0, ctx->stream, moverKeys_.as<K>(), count,
                        args_.moverCap, leafLo_.as<K>(), numJ, haveCoarse_ ? coarse_.as<uint32_t>() : nullptr,
@@ -1455,10 +1505,29 @@ int LeafResort<K>::binMovers(cstone_hip_ctx* ctx, int leavesPerTile)
 }
 
 template<class K>
+int LeafResort<K>::placeMoversEarly(cstone_hip_ctx* ctx, uint32_t expectedMovers)
+{
+    StageTimer timer(ctx, CSTONE_STAGE_RESORT_BINS);
+    // one list entry per lane when the guess holds, like placeMoversKernel (a fixed grid of numCu * 16 workgroups striding
+    // over 7 * 10^6 movers took 173 us against 137 us: 100 against 86 bytes of HBM traffic per mover); more movers than
+    // guessed take further strides, fewer leave workgroups without work
+    const size_t lanes  = std::min<size_t>(args_.moverCap, std::max<size_t>(size_t(expectedMovers) + expectedMovers / 4,
+                                                                         size_t(ctx->numCu) * 16 * 256));
+    const unsigned grid = unsigned((lanes + 255) / 256);
+    hipLaunchKernelGGL(placeMoversEarlyKernel<K>, grid, 256, 0, ctx->stream, moverKeys_.as<K>(),
+                       moverIdx_.as<uint32_t>(), moverDest_.as<uint32_t>(), moverSlot_.as<uint32_t>(),
+                       ctx->devScalars + RESORT_SCALARS, args_.moverCap, inOffset_.as<uint32_t>(), binKeys_.as<K>(),
+                       binIdx_.as<uint32_t>());
+    CS_HIP(ctx, hipGetLastError());
+    moversPlaced_ = true;
+    return CSTONE_OK;
+}
+
+template<class K>
 int LeafResort<K>::sortLeaves(cstone_hip_ctx* ctx, const K* keysIn, K* keysOut, uint32_t* orderOut, uint32_t numMovers,
                               uint32_t numMarkers, uint32_t J, int leavesPerTile, bool largeQuietTiles)
 {
-    if (numMovers)
+    if (numMovers && !moversPlaced_)
     {
         StageTimer timer(ctx, CSTONE_STAGE_RESORT_BINS);
         hipLaunchKernelGGL(placeMoversKernel<K>, gridFor(numMovers, 256), 256, 0, ctx->stream, moverKeys_.as<K>(),
@@ -1473,7 +1542,7 @@ int LeafResort<K>::sortLeaves(cstone_hip_ctx* ctx, const K* keysIn, K* keysOut, 
         uint32_t* idx = binIdx_.as<uint32_t>() + (numMovers - numMarkers);
         CS_TRY(cstone_hip_sort_keys(ctx, 32, idx, numMarkers));
         hipLaunchKernelGGL(placeMarkersKernel<K>, gridFor(numMarkers, 256), 256, 0, ctx->stream, idx, numMarkers,
-                           layoutNew_.as<uint32_t>(), (const uint32_t*)(ctx->devScalars + RESORT_SCALARS) + 2, keysOut,
+                           layoutNew_.as<uint32_t>(), numJ_, keysOut,
                            orderOut);
     }
     if (J == 0) return CSTONE_OK;
@@ -1545,7 +1614,7 @@ int LeafResort<K>::sortLeavesFields(cstone_hip_ctx* ctx, const K* keysIn, K* key
     auto run = [&](auto tTag) -> int
     {
         using T = decltype(tTag);
-        if (numMovers)
+        if (numMovers && !moversPlaced_)
         {
             StageTimer timer(ctx, CSTONE_STAGE_RESORT_BINS);
             hipLaunchKernelGGL(placeMoversKernel<K>, gridFor(numMovers, 256), 256, 0, ctx->stream, moverKeys_.as<K>(),
@@ -1559,7 +1628,7 @@ int LeafResort<K>::sortLeavesFields(cstone_hip_ctx* ctx, const K* keysIn, K* key
             uint32_t* idx = binIdx_.as<uint32_t>() + (numMovers - numMarkers);
             CS_TRY(cstone_hip_sort_keys(ctx, 32, idx, numMarkers));
             hipLaunchKernelGGL(placeMarkersKernel<K>, gridFor(numMarkers, 256), 256, 0, ctx->stream, idx, numMarkers,
-                               layoutNew_.as<uint32_t>(), (const uint32_t*)(ctx->devScalars + RESORT_SCALARS) + 2,
+                               layoutNew_.as<uint32_t>(), numJ_,
                                keysOut, orderOut);
         }
         if (J == 0) return CSTONE_OK;
@@ -1630,7 +1699,7 @@ int LeafResort<K>::countLeaves(cstone_hip_ctx* ctx, const K* tree, int numNodes,
         boundaryNodes_ = numNodes;
     }
     hipLaunchKernelGGL(bracketedPositionsKernel<K>, gridFor(size_t(numNodes) + 1, 256), 256, 0, ctx->stream, tree,
-                       NodeIdx(numNodes), keys, leafLo_.as<K>(), (const uint32_t*)(ctx->devScalars + RESORT_SCALARS) + 2,
+                       NodeIdx(numNodes), keys, leafLo_.as<K>(), numJ_,
                        haveCoarse_ ? coarse_.as<uint32_t>() : nullptr, layoutNew_.as<uint32_t>(), pos, boundaryLeaf);
     hipLaunchKernelGGL(countsOfPositionsKernel, gridFor(numNodes, 256), 256, 0, ctx->stream, pos, NodeIdx(numNodes),
                        maxCount, counts);

@@ -77,10 +77,24 @@ public:
      *  some 10^5 movers on) */
     int prepare(cstone_hip_ctx* ctx, const K* tree, const uint32_t* layout, int numLeaves, size_t n, K* keysOut,
                 bool expectMovers = false, int fieldBits = 0 /* 32 | 64: the leaf pass will carry x, y, z, h */);
+    /*! prepare() in two halves.  prepareTable: everything that follows from tree, layout, numLeaves and n alone -- start
+     *  bits and ranks, J, leafLo, leafPos, the coarse table, the cleared departure / arrival counters.  It may be queued
+     *  long before the attempt it serves (Domain::sync builds it at the end of the sync before): J then lives in a
+     *  buffer of this object, not in the context's scalar slots, which other domains and calls on the context use in
+     *  between.  beginAttempt: the rest -- where the keys go, the fields' buffers, the attempt's cleared result scalars.
+     *  A table serves ONE attempt (the attempt counts in it). */
+    int prepareTable(cstone_hip_ctx* ctx, const K* tree, const uint32_t* layout, int numLeaves, size_t n,
+                     bool expectMovers);
+    int beginAttempt(cstone_hip_ctx* ctx, K* keysOut, int fieldBits = 0);
     ResortArgs<K> args() const { return args_; }
-    /*! bins the movers, new leaf sizes and offsets, limit checks; everything stays on the device: the three scalars at
+    /*! bins the movers, new leaf sizes and offsets, limit checks; everything stays on the device: the scalars at
      *  ctx->devScalars + RESORT_SCALARS tell the host how it went */
     int binMovers(cstone_hip_ctx* ctx, int leavesPerTile);
+    /*! the movers into their bins BEFORE the host has seen how binMovers went (to be queued behind the read-back of the
+     *  scalars, so that it runs while the host decides): count and flags are read on the device, nothing is placed when
+     *  the attempt failed.  sortLeaves / sortLeavesFields then leave that step out.  expectedMovers (the movers of the
+     *  sync before, say) sizes the grid: one entry per lane if it holds */
+    int placeMoversEarly(cstone_hip_ctx* ctx, uint32_t expectedMovers);
     /*! the leaf pass: keysIn = new keys at old positions; keysOut / orderOut = sorted keys and their old positions.
      *  numMovers, numMarkers, numCompactLeaves: the values read back after binMovers */
     int sortLeaves(cstone_hip_ctx* ctx, const K* keysIn, K* keysOut, uint32_t* orderOut, uint32_t numMovers,
@@ -114,6 +128,11 @@ private:
     bool carryFields_  = false;
     int boundaryNodes_ = -1;     // tree size boundaryLeaf_ was filled for
     bool haveCoarse_ = false;
+    DevBuf tableJ_;                  // J of a table built by prepareTable()
+    const uint32_t* numJ_ = nullptr; // where the kernels read J: tableJ_, or the context's slot (prepare())
+    bool moversPlaced_    = false;   // placeMoversEarly() has queued the placement for this attempt
+    int buildTable(cstone_hip_ctx* ctx, const K* tree, const uint32_t* layout, int numLeaves, size_t n, bool expectMovers,
+                   uint32_t* numJ);
     ResortArgs<K> args_{};
     int numLeaves_ = 0;
     size_t n_      = 0;

@@ -9,8 +9,10 @@
 // roundings on the reference's CPU path and must not become an FMA.
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 
 #include <limits>
+#include <type_traits>
 
 #include "ctx.hpp"
 #include "device_keys.hpp"
@@ -298,12 +300,27 @@ __global__ __launch_bounds__(256) void foldExtentsKernel(const T* __restrict__ p
     }
 }
 
+//! how encodeResortKernel walks the positions (see there): a tile is 2^ENCODE_TILE_LOG2 = 8 workgroup iterations, 2048
+//! vectors (of R = 4, 8, 16 and of the two ways to share a tile among the four waves, quarters with R = 8 measured best:
+//! DESIGN.md section 4b)
+constexpr unsigned ENCODE_TILE_LOG2      = 3;
+constexpr bool ENCODE_TILE_ORDER_DEFAULT = true;  // (what the tiled walk measured)
+
+//! CSTONE_ENCODE_ORDER=stride|tile picks the walk, per launch (the tests switch it)
+inline bool encodeInTileOrder()
+{
+    const char* order = std::getenv("CSTONE_ENCODE_ORDER");
+    return order ? std::strcmp(order, "tile") == 0 : ENCODE_TILE_ORDER_DEFAULT;
+}
+
 /*! Encode for the incremental re-sort (resort.hpp): the keys go to ra.keysOut (the caller's key array is only read, for
  *  its remove markers) and every particle is checked against the key range of the leaf its position belonged to at the
  *  previous sync.  Particles that left their leaf are counted per leaf and appended to the mover list -- staged per wave
  *  in LDS and flushed with one atomic per 128..256 movers; in ra.keysOut a hole (~0) takes their place.  The extents of x, y, z are measured like in
- *  encodeHistogramKernel.  Grid-stride, whole waves walk the iterations together. */
-template<class K, class T, int VEC, bool HILBERT>
+ *  encodeHistogramKernel.  Few, long-lived workgroups that walk the positions grid-stride or, TILED, tile by tile;
+ *  whole waves walk the iterations together.  The order of the mover list follows the walk; the result of the re-sort
+ *  does not depend on it (slots inside a bin are handed out by atomics, the leaf pass orders by (key, old index)). */
+template<class K, class T, int VEC, bool HILBERT, bool TILED>
 __global__ __launch_bounds__(256) void encodeResortKernel(const T* __restrict__ x, const T* __restrict__ y,
                                                           const T* __restrict__ z, const K* __restrict__ keysIn,
                                                           size_t n, DBox<T> box, const uint16_t* __restrict__ encTable,
@@ -380,8 +397,22 @@ __global__ __launch_bounds__(256) void encodeResortKernel(const T* __restrict__ 
 
     const size_t nVec   = n / VEC;
     const size_t stride = size_t(gridDim.x) * 256;
-    const size_t iters  = (nVec + stride - 1) / stride;
-    size_t vi           = size_t(blockIdx.x) * 256 + threadIdx.x;
+    // The walk over the vectors.  Grid-stride (!TILED): iteration `it` of a workgroup is `stride` vectors behind the one
+    // before.  Tiled: a tile is R = 2^ENCODE_TILE_LOG2 consecutive workgroup iterations, 256 R vectors; workgroup b takes
+    // the tiles b, b + grid, ..., and inside a tile every wave walks its own contiguous quarter, 64 vectors per iteration.
+    // The movers a wave stages then come from neighbouring leaves.  Either way every wave of the grid runs `iters`
+    // iterations.
+    constexpr unsigned tileL = ENCODE_TILE_LOG2;
+    const size_t tiles       = (nVec + (size_t(256) << tileL) - 1) >> (8 + tileL);
+    const size_t iters       = TILED ? ((tiles + gridDim.x - 1) / gridDim.x) << tileL : (nVec + stride - 1) / stride;
+    const size_t inTile      = (size_t(w) << (6 + tileL)) + lane;
+    auto vectorOf = [&](size_t it) -> size_t
+    {
+        if constexpr (!TILED) return size_t(blockIdx.x) * 256 + threadIdx.x + it * stride;
+        const size_t tile = size_t(blockIdx.x) + (it >> tileL) * gridDim.x;
+        return (tile << (8 + tileL)) + ((it & ((size_t(1) << tileL) - 1)) << 6) + inTile;
+    };
+    size_t vi = vectorOf(0);
     // what an iteration reads: requested one iteration ahead, so that a wave computes the keys of one vector while
     // the loads of the next are in flight.  (Worth 1-2 % only: four fifths of this kernel's traffic are reads, and
     // read-dominated streams top out near 4.7 TB/s on this machine -- the pure read of minMaxPartialKernel runs at 4.6 --
@@ -413,12 +444,14 @@ __global__ __launch_bounds__(256) void encodeResortKernel(const T* __restrict__ 
     };
     In next{};
     if (vi < nVec) fetch(vi, next);
-    for (size_t it = 0; it < iters; ++it, vi += stride)
+    for (size_t it = 0; it < iters; ++it)
     {
-        const bool valid  = vi < nVec;
-        const size_t base = vi * VEC;
-        const In in       = next;
-        if (vi + stride < nVec) fetch(vi + stride, next);
+        const bool valid   = vi < nVec;
+        const size_t base  = vi * VEC;
+        const In in        = next;
+        const size_t viNext = vectorOf(it + 1);
+        if (it + 1 < iters && viNext < nVec) fetch(viNext, next);
+        vi = viNext;
         K out[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v)
@@ -589,12 +622,23 @@ static int computeKeysResortT(cstone_hip_ctx* ctx, int curve, const T* x, const 
         CS_TRY(arenaReserve(ctx, alignUp(size_t(grid) * 6 * sizeof(T)) + 256));
         partials = (T*)arenaTake(ctx, size_t(grid) * 6 * sizeof(T));
     }
+    // (a template flag, not an argument: the grid-stride instantiation is the kernel it always was)
+    auto launch = [&](auto hilbert, auto tiled)
+    {
+        hipLaunchKernelGGL((encodeResortKernel<K, T, VEC, decltype(hilbert)::value, decltype(tiled)::value>), grid, 256, 0,
+                           ctx->stream, x, y, z, keysIn, n, box, enc, ra, partials);
+    };
+    const bool tiled = encodeInTileOrder();
     if (curve == CSTONE_HILBERT)
-        hipLaunchKernelGGL((encodeResortKernel<K, T, VEC, true>), grid, 256, 0, ctx->stream, x, y, z, keysIn, n, box, enc,
-                           ra, partials);
+    {
+        if (tiled) launch(std::true_type{}, std::true_type{});
+        else launch(std::true_type{}, std::false_type{});
+    }
     else
-        hipLaunchKernelGGL((encodeResortKernel<K, T, VEC, false>), grid, 256, 0, ctx->stream, x, y, z, keysIn, n, box,
-                           enc, ra, partials);
+    {
+        if (tiled) launch(std::false_type{}, std::true_type{});
+        else launch(std::false_type{}, std::false_type{});
+    }
     if (extentsOut)
     {
         hipLaunchKernelGGL(foldExtentsKernel<T>, 1, 256, 0, ctx->stream, partials, grid, (T*)extentsOut);

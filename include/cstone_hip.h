@@ -743,6 +743,11 @@ extern "C"
         uint32_t last_movers;         /* particles that had left their leaf at the last re-sort */
     } cstone_hip_domain_stats;
     int cstone_hip_domain_stats_get(cstone_hip_domain* dom, cstone_hip_domain_stats* out);
+    /* With CSTONE_EARLY_LEAF_TABLE=1 (an experiment, off by default) the leaf table of a re-sort (csrc/resort.hpp) is
+     * built at the end of the sync before, beside the gather of x, y, z, instead of in front of the encode.  Of the
+     * tables built that way so far: how many the following sync used, and how many it had to build again because they
+     * no longer fitted (another particle count, no re-sort attempted, a failed sync in between).  Counters only. */
+    int cstone_hip_domain_leaf_table_stats(cstone_hip_domain* dom, uint32_t* used, uint32_t* rejected);
 
     /* ---------------------------------------------------------------------------------------------
      * Domain::sync on SEVERAL ranks, one process per GPU (R/domain/domain.hpp:196-243 with the exchange steps of
