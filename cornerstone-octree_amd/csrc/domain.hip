@@ -143,6 +143,9 @@ struct DomainBase
     virtual int sphereProfiles(const void* x, const void* y, const void* z, const void* w, int massBits, const void* queryCenters,
                                const void* queryScale, uint32_t numQueries, const double* edgesHost, int numBins,
                                uint64_t* counts, double* sums, uint32_t* flags) = 0;
+    virtual int knn(const void* x, const void* y, const void* z, const void* queryCenters, const void* queryRmax,
+                    const uint32_t* querySelf, uint32_t numQueries, uint32_t k, uint32_t* neighbors, void* dist2,
+                    uint32_t* counts) = 0;
     virtual void stats(cstone_hip_domain_stats* out)     = 0;
     virtual void leafTableStats(uint32_t* used, uint32_t* rejected) = 0;
 };
@@ -309,6 +312,17 @@ public:
         return cstone_hip_sphere_profiles(ctx_, rb, massBits, x, y, z, w, startIndex_, endIndex_, &box_, fChild_.as<int32_t>(),
                                           fItl_.as<int32_t>(), layout_.as<uint32_t>(), fCenters_.p, fSizes_.p, queryCenters,
                                           queryScale, numQueries, edgesHost, numBins, counts, sums, flags);
+    }
+
+    //! cstone_hip_knn on the octree, the box and [start_index, end_index) of the last sync
+    int knn(const void* x, const void* y, const void* z, const void* queryCenters, const void* queryRmax,
+            const uint32_t* querySelf, uint32_t numQueries, uint32_t k, uint32_t* neighbors, void* dist2,
+            uint32_t* counts) override
+    {
+        if (firstCall_ || fLeaves_ < 1) return fail(ctx_, CSTONE_E_ARG, "domain_knn: no sync yet");
+        return cstone_hip_knn(ctx_, rb, x, y, z, startIndex_, endIndex_, &box_, fChild_.as<int32_t>(), fItl_.as<int32_t>(),
+                              layout_.as<uint32_t>(), fCenters_.p, fSizes_.p, queryCenters, queryRmax, querySelf, numQueries,
+                              k, neighbors, dist2, counts);
     }
 
     /*! Domain::updateExpansionCenters (R/domain/domain.hpp:415-421) on one rank = FocusedOctree::updateCenters without its
@@ -1348,6 +1362,14 @@ int cstone_hip_domain_sphere_profiles(cstone_hip_domain* dom, const void* x, con
     if (!dom) return CSTONE_E_ARG;
     return dom->impl->sphereProfiles(x, y, z, w, mass_bits, query_centers, query_scale, num_queries, edges_host, num_bins,
                                      counts, sums, flags);
+}
+
+int cstone_hip_domain_knn(cstone_hip_domain* dom, const void* x, const void* y, const void* z, const void* query_centers,
+                          const void* query_rmax, const uint32_t* query_self, uint32_t num_queries, uint32_t k,
+                          uint32_t* neighbors, void* dist2, uint32_t* counts)
+{
+    if (!dom) return CSTONE_E_ARG;
+    return dom->impl->knn(x, y, z, query_centers, query_rmax, query_self, num_queries, k, neighbors, dist2, counts);
 }
 
 int cstone_hip_domain_view_get(cstone_hip_domain* dom, cstone_hip_domain_view* out)

@@ -32,6 +32,7 @@
 #include "device_keys.hpp"
 #include "fof_mr.hpp"
 #include "fof_props.hpp"
+#include "knn.hpp"
 #include "sphere.hpp"
 #include "host_tree.hpp"
 #include "let.hpp"
@@ -378,6 +379,9 @@ struct MrBase
     virtual int sphereProfiles(const void* x, const void* y, const void* z, const void* w, int massBits, const void* queryCenters,
                                const void* queryScale, uint32_t numQueries, const double* edgesHost, int numBins,
                                uint64_t* counts, double* sums, uint32_t* flags) = 0;
+    virtual int knn(const void* x, const void* y, const void* z, const void* queryCenters, const void* queryRmax,
+                    uint32_t numQueries, uint32_t k, uint64_t* ids, void* dist2, uint32_t* counts) = 0;
+    virtual void knnLast(uint32_t* numChunks, uint64_t* gatherBytes) = 0;
     virtual int multipoles(const void** out, int32_t* numNodes)                           = 0;
     virtual int octupoles(const void** out, int32_t* numNodes)                            = 0;
     virtual int view(cstone_hip_domain_mr_view* out)                                     = 0;
@@ -706,6 +710,35 @@ public:
         if (numQueries == 0) return CSTONE_OK;
         CS_TRY(profilesLocal(s));
         return profilesReduce(s);
+    }
+
+    /*! The k nearest neighbours of arbitrary points among the particles of all ranks (cstone_hip_domain_mr_knn; the
+     *  rule: include/cstone_hip.h).  Every rank searches its assigned range on its own octree; one all-gather of {status, Q,
+     *  k, rmax given, assigned count} lets every rank fail together and gives the id ranges; the ranks' rows travel in
+     *  chunks of queries through all_gather and a merge kernel keeps the k best of them.  A list of stages that share one
+     *  KnnState. */
+    int knn(const void* x, const void* y, const void* z, const void* queryCenters, const void* queryRmax, uint32_t numQueries,
+            uint32_t k, uint64_t* ids, void* dist2, uint32_t* counts) override
+    {
+        KnnState s{x, y, z, queryCenters, queryRmax, numQueries, k, ids, dist2, counts};
+        CS_TRY(knnRefuseEverywhere(s));
+        knnLocalTrouble(s);
+        CS_TRY(knnAgree(s));
+        for (uint32_t q0 = 0; q0 < numQueries; q0 += s.chunk)
+        {
+            const uint32_t nq = std::min(s.chunk, numQueries - q0);
+            CS_TRY(knnLocal(s, q0, nq));
+            CS_TRY(knnGather(s, nq));
+            CS_TRY(knnMerge(s, q0, nq));
+            ++knnChunks_;
+        }
+        return CSTONE_OK;
+    }
+
+    void knnLast(uint32_t* numChunks, uint64_t* gatherBytes) override
+    {
+        if (numChunks) *numChunks = knnChunks_;
+        if (gatherBytes) *gatherBytes = knnGatherBytes_;
     }
 
     int multipoles(const void** out, int32_t* numNodes) override
@@ -2554,6 +2587,109 @@ private:
         return CSTONE_OK;
     }
 
+    // ---- knn(), stage by stage
+
+    //! What the stages of one knn() share: the caller's arguments and what the stages before have decided
+    struct KnnState
+    {
+        const void *x, *y, *z, *queryCenters, *queryRmax;
+        uint32_t numQueries, k;
+        uint64_t* ids;
+        void* dist2;
+        uint32_t* counts;
+        uint32_t si = 0, ei = 0, na = 0;
+        uint32_t chunk   = 0; // queries per all_gather
+        uint64_t trouble = FINE;
+        uint64_t idBase  = 0;            // the global id of my first assigned particle
+        cstone_hip_domain_mr_octree t{}; // my octree; all null on a rank without particles
+        KnnRecord *send = nullptr, *recv = nullptr;
+    };
+
+    //! the cap on the receive buffer of one all_gather: CSTONE_KNN_MR_GATHER_BYTES, or what the environment variable of
+    //! that name says (a positive number of bytes; for tests of the chunking)
+    static uint64_t knnGatherCap()
+    {
+        if (const char* e = std::getenv("CSTONE_KNN_MR_GATHER_BYTES"))
+        {
+            char* end                  = nullptr;
+            const unsigned long long v = std::strtoull(e, &end, 10);
+            if (end != e && *end == 0 && v > 0) return v;
+        }
+        return CSTONE_KNN_MR_GATHER_BYTES;
+    }
+
+    //! what is the same on every rank: refused before any collective
+    int knnRefuseEverywhere(KnnState& s)
+    {
+        knnChunks_ = 0, knnGatherBytes_ = 0;
+        if (firstCall_) return fail(ctx_, CSTONE_E_ARG, "domain_mr_knn: no sync yet");
+        if (s.k < 1 || s.k > CSTONE_KNN_MAX_K) return fail(ctx_, CSTONE_E_ARG, "domain_mr_knn: k outside 1 .. %d", CSTONE_KNN_MAX_K);
+        s.si = view_.start_index, s.ei = view_.end_index, s.na = s.ei - s.si;
+        s.chunk = knnChunkQueries(s.numQueries, s.k, P_, knnGatherCap());
+        return CSTONE_OK;
+    }
+
+    //! rank-local trouble: collected, not returned.  The buffer: my rows of a chunk, then everybody's (one rank: mine are all)
+    void knnLocalTrouble(KnnState& s)
+    {
+        const size_t rowBytes = alignUp(size_t(s.chunk) * s.k * sizeof(KnnRecord));
+        if (s.numQueries && (!s.queryCenters || !s.ids || (s.na && (!s.x || !s.y || !s.z)))) s.trouble = NULL_ARRAY;
+        else if (knnBuf_.ensure(ctx_, std::max<size_t>(rowBytes * (P_ > 1 ? size_t(P_) + 1 : 1), 256))) s.trouble = NO_MEMORY;
+        else if (s.na && octree(&s.t)) s.trouble = LOCAL_STEP;
+        s.send = knnBuf_.as<KnnRecord>();
+        s.recv = P_ > 1 ? sliceOf<KnnRecord>(knnBuf_, rowBytes) : s.send;
+        knnGatherBytes_ = P_ > 1 ? uint64_t(P_) * s.chunk * s.k * sizeof(KnnRecord) : 0;
+    }
+
+    //! one all-gather of {status, Q, k, rmax given, assigned count}: every rank fails together, also where the ranks
+    //! disagree on the middle three; the counts give the id ranges, those of friendsOfFriends()
+    int knnAgree(KnnState& s)
+    {
+        const uint64_t row[5] = {s.trouble, s.numQueries, s.k, s.queryRmax ? 1u : 0u, s.na};
+        std::vector<uint64_t> rows;
+        CS_TRY(stageRow(row, 5, rows));
+        CS_TRY(gatherRows(5, "all_gather (knn)", rows));
+        for (int p = 0; p < P_; ++p)
+        {
+            uint64_t* r = rows.data() + 5 * size_t(p);
+            if (r[0] == FINE && (r[1] != rows[1] || r[2] != rows[2] || r[3] != rows[3])) r[0] = MISMATCH;
+            if (p < rank_) s.idBase += r[4];
+        }
+        static const char* const why[NUM_TROUBLES] = {"", "null array", "", "out of device memory", "", "no octree",
+                                                      "the ranks disagree on num_queries, k or whether there is a query_rmax"};
+        return agree("domain_mr_knn", rows, 5, 0, why);
+    }
+
+    //! byte offset of query q0 in an array of `per` values of the coordinate type per query
+    const void* knnAt(const void* base, uint32_t q0, size_t per) const
+    {
+        return base ? static_cast<const char*>(base) + size_t(q0) * per * (rb / 8) : nullptr;
+    }
+
+    //! my answer for the queries [q0, q0 + nq) as records.  A rank without particles has nothing to read: its empty range
+    //! leaves every row unfilled without touching the arrays or the tree
+    int knnLocal(KnnState& s, uint32_t q0, uint32_t nq)
+    {
+        return knnLocalRecords(ctx_, rb, s.x, s.y, s.z, s.si, s.ei, view_.box, s.t.child_offsets, s.t.internal_to_leaf,
+                               s.t.layout, s.t.centers, s.t.sizes, knnAt(s.queryCenters, q0, 3), knnAt(s.queryRmax, q0, 1), nq,
+                               s.k, s.idBase, s.send);
+    }
+
+    //! everybody's rows of the chunk: recv[p][q][0 .. k)
+    int knnGather(KnnState& s, uint32_t nq)
+    {
+        if (P_ == 1) return CSTONE_OK;
+        return callComm(comm_.all_gather(comm_.user, s.send, s.recv, size_t(nq) * s.k * sizeof(KnnRecord)), "all_gather (knn rows)");
+    }
+
+    //! the k best of the P rows of every query of the chunk, into the caller's arrays
+    int knnMerge(KnnState& s, uint32_t q0, uint32_t nq)
+    {
+        void* d2 = s.dist2 ? static_cast<char*>(s.dist2) + size_t(q0) * s.k * (rb / 8) : nullptr;
+        return knnMergeRecords(ctx_, rb, s.recv, P_, knnAt(s.queryRmax, q0, 1), nq, s.k, s.ids + size_t(q0) * s.k, d2,
+                               s.counts ? s.counts + q0 : nullptr);
+    }
+
     cstone_hip_ctx* ctx_;
     int curve_, rank_, P_;
     uint32_t bucket_, bucketFocus_;
@@ -2640,6 +2776,9 @@ private:
     int fofOffsetSync_ = -1;
     DevBuf catWork_, catPart_, catRecv_, catScal_;
     DevBuf sphereBuf_; // the operand of the all-reduce of sphereProfiles: {counts as doubles, sums}
+    DevBuf knnBuf_;    // knn(): my rows of a chunk of queries, then the rows of every rank
+    uint32_t knnChunks_      = 0; // of the last knn(): all_gather rounds made, bytes its receive buffer took
+    uint64_t knnGatherBytes_ = 0;
     Out out_[2];
     int cur_ = 0;
 };
@@ -2796,6 +2935,21 @@ int cstone_hip_domain_mr_sphere_profiles(cstone_hip_domain_mr* dom, const void* 
     if (!dom) return CSTONE_E_ARG;
     return dom->impl->sphereProfiles(x, y, z, w, mass_bits, query_centers, query_scale, num_queries, edges_host, num_bins,
                                      counts, sums, flags);
+}
+
+int cstone_hip_domain_mr_knn(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z, const void* query_centers,
+                             const void* query_rmax, uint32_t num_queries, uint32_t k, uint64_t* ids, void* dist2,
+                             uint32_t* counts)
+{
+    if (!dom) return CSTONE_E_ARG;
+    return dom->impl->knn(x, y, z, query_centers, query_rmax, num_queries, k, ids, dist2, counts);
+}
+
+int cstone_hip_domain_mr_knn_last(cstone_hip_domain_mr* dom, uint32_t* num_chunks, uint64_t* gather_bytes)
+{
+    if (!dom) return CSTONE_E_ARG;
+    dom->impl->knnLast(num_chunks, gather_bytes);
+    return CSTONE_OK;
 }
 
 int cstone_hip_domain_mr_multipoles_get(cstone_hip_domain_mr* dom, const void** multipoles, int32_t* num_nodes)

@@ -80,6 +80,9 @@ EXPORTS = [
     # sphere queries at arbitrary points: radial profiles and spherical-overdensity masses (csrc/sphere.hip)
     "cstone_hip_sphere_profiles", "cstone_hip_spherical_overdensity", "cstone_hip_domain_sphere_profiles",
     "cstone_hip_domain_mr_sphere_profiles",
+    # exact k nearest neighbours at arbitrary points (csrc/knn.hip)
+    "cstone_hip_knn", "cstone_hip_domain_knn", "cstone_hip_domain_mr_knn", "cstone_hip_knn_mr_chunk_queries",
+    "cstone_hip_domain_mr_knn_last",
 ]
 
 FOF_GROUP_WIDE, FOF_GROUP_MASSLESS = 0x1, 0x2  # CSTONE_FOF_GROUP_*: the flags of the group catalogue
@@ -87,6 +90,10 @@ FOF_GROUP_WIDE, FOF_GROUP_MASSLESS = 0x1, 0x2  # CSTONE_FOF_GROUP_*: the flags o
 SPHERE_MAX_BINS = 64  # CSTONE_SPHERE_MAX_BINS
 # CSTONE_SPHERE_TOO_WIDE (profiles and overdensity), CSTONE_SO_NOT_REACHED, CSTONE_SO_UNRESOLVED (overdensity)
 SPHERE_TOO_WIDE, SO_NOT_REACHED, SO_UNRESOLVED = 0x1, 0x2, 0x4
+
+KNN_MAX_K = 256  # CSTONE_KNN_MAX_K
+KNN_MR_GATHER_BYTES = 256 << 20  # CSTONE_KNN_MR_GATHER_BYTES: the cap on the receive buffer of one all_gather of rows
+KNN_NONE = 0xFFFFFFFF  # what an unfilled slot of neighbors holds, and the query_self that excludes nothing
 
 FOF_MR_DEFAULT_ROUNDS = 4096  # CSTONE_FOF_MR_DEFAULT_ROUNDS: what max_rounds = 0 means to cstone_hip_domain_mr_fof
 
@@ -174,6 +181,22 @@ def load_library():
         fn.restype = C.c_int
         fn.argtypes = ([C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 2 + [C.c_uint32, C.POINTER(C.c_double), C.c_int] +
                        [C.c_void_p] * 3)
+    # k nearest neighbours: (ctx, real_bits, x, y, z, first, last, box*, child_offsets, internal_to_leaf, layout, centers,
+    # sizes, query_centers, query_rmax, query_self, num_queries, k, neighbors, dist2, counts); the domain's: (domain, x, y,
+    # z, query_centers, query_rmax, query_self, num_queries, k, neighbors, dist2, counts)
+    lib.cstone_hip_knn.restype = C.c_int
+    lib.cstone_hip_knn.argtypes = ([C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_uint32] * 2 + [C.c_void_p] * 9 +
+                                   [C.c_uint32] * 2 + [C.c_void_p] * 3)
+    lib.cstone_hip_domain_knn.restype = C.c_int
+    lib.cstone_hip_domain_knn.argtypes = [C.c_void_p] * 7 + [C.c_uint32] * 2 + [C.c_void_p] * 3
+    # across ranks: (domain, x, y, z, query_centers, query_rmax, num_queries, k, ids, dist2, counts); the chunk rule
+    # (num_queries, k, num_ranks, cap_bytes) -> queries per all_gather; (domain, num_chunks*, gather_bytes*) of the last call
+    lib.cstone_hip_domain_mr_knn.restype = C.c_int
+    lib.cstone_hip_domain_mr_knn.argtypes = [C.c_void_p] * 6 + [C.c_uint32] * 2 + [C.c_void_p] * 3
+    lib.cstone_hip_knn_mr_chunk_queries.restype = C.c_uint32
+    lib.cstone_hip_knn_mr_chunk_queries.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_uint64]
+    lib.cstone_hip_domain_mr_knn_last.restype = C.c_int
+    lib.cstone_hip_domain_mr_knn_last.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     return lib
 
 
@@ -724,6 +747,34 @@ class Context:
             _opt(octree["child_offsets"]), _opt(octree["internal_to_leaf"]), _opt(layout), _opt(centers), _opt(sizes),
             _opt(query_centers), _opt(query_scale), nq, e, nb, _opt(counts), _opt(sums), _opt(flags)), "sphere_profiles")
         return counts, sums, flags
+
+    def knn(self, x, y, z, first, last, box, octree, layout, centers, sizes, query_centers, k, query_rmax=None,
+            query_self=None, num_queries=None, neighbors=None, dist2=None, counts=None, with_dist2=True, with_counts=True,
+            real_bits=None):
+        """cstone_hip_knn: for every query centre (query_centers [Q, 3], the coordinates' type) the k nearest particles
+        of [first, last), ordered by (squared distance, index).  query_rmax [Q] (or None): only particles with
+        d2 < rmax * rmax; query_self [Q] int32 (or None): one index per query that is left out, KNN_NONE for none.
+        Returns (neighbors [Q, k] int32 holding absolute indices, dist2 [Q, k] in the coordinates' type, counts [Q]
+        int32); unfilled slots hold -1 (KNN_NONE) and +inf.  with_dist2 / with_counts = False pass NULL and return None
+        there.  neighbors, dist2, counts: tensors to write into instead of new ones; num_queries, real_bits: overrides of
+        what the tensors imply.  The rule: include/cstone_hip.h.  Asynchronous"""
+        torch = _torch()
+        nq = query_centers.shape[0] if num_queries is None else num_queries
+        dev = query_centers.device
+        cols = min(max(int(k), 0), KNN_MAX_K)
+        if neighbors is None:
+            neighbors = torch.full((nq, cols), -1, dtype=torch.int32, device=dev)
+        if dist2 is None and with_dist2:
+            dist2 = torch.full((nq, cols), float("inf"), dtype=query_centers.dtype, device=dev)
+        if counts is None and with_counts:
+            counts = torch.zeros(nq, dtype=torch.int32, device=dev)
+        rb = query_centers.element_size() * 8 if real_bits is None else real_bits
+        self._chk(self.lib.cstone_hip_knn(
+            self.h, rb, _opt(x), _opt(y), _opt(z), first, last, C.cast(C.byref(box), C.c_void_p),
+            _opt(octree["child_offsets"]), _opt(octree["internal_to_leaf"]), _opt(layout), _opt(centers), _opt(sizes),
+            _opt(query_centers), _opt(query_rmax), _opt(query_self), nq, k, _opt(neighbors), _opt(dist2), _opt(counts)),
+            "knn")
+        return neighbors, dist2, counts
 
     def spherical_overdensity(self, sums, edges, rho_threshold, query_scale=None, profile_flags=None, real_bits=64,
                               num_queries=None, r_delta=None, m_delta=None, flags=None):

@@ -457,6 +457,40 @@ class NativeDistributedDomain:
         self.ctx._chk(rc, "domain_mr_sphere_profiles")
         return counts, sums, flags
 
+    def knn(self, x, y, z, query_centers, k, query_rmax=None, num_queries=None, ids=None, dist2=None, counts=None,
+            with_dist2=True, with_counts=True):
+        """cstone_hip_domain_mr_knn (COLLECTIVE): the k nearest neighbours of Context.knn among the particles of all
+        ranks.  Every rank passes the same query_centers [Q, 3], query_rmax [Q] or None and k; x, y, z are laid out like
+        the result arrays of the last sync and read on the assigned range only (None on a rank without particles).
+        Returns (ids [Q, k] int64 holding global ids -- positions in the global SFC order, as fof() labels them --,
+        dist2 [Q, k], counts [Q] int32), the same on every rank; unfilled slots hold -1 and +inf.  ids, dist2, counts:
+        tensors to write into instead of new ones; num_queries: override of query_centers' rows"""
+        torch = _torch()
+        nq = query_centers.shape[0] if num_queries is None else num_queries
+        cols = min(max(int(k), 0), 256)
+        if ids is None:
+            ids = torch.full((nq, cols), -1, dtype=torch.int64, device=self.ctx.device)
+        if dist2 is None and with_dist2:
+            dist2 = torch.full((nq, cols), float("inf"), dtype=query_centers.dtype, device=self.ctx.device)
+        if counts is None and with_counts:
+            counts = torch.zeros(nq, dtype=torch.int32, device=self.ctx.device)
+        P = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        rc = self.ctx.lib.cstone_hip_domain_mr_knn(self.h, P(x), P(y), P(z), P(query_centers), P(query_rmax), nq, k, P(ids),
+                                                   P(dist2), P(counts))
+        if rc != 0 and self.coll.error is not None:
+            err, self.coll.error = self.coll.error, None
+            raise err
+        self.ctx._chk(rc, "domain_mr_knn")
+        return ids, dist2, counts
+
+    def knn_last(self):
+        """(all_gather rounds, bytes of the receive buffer) of the last knn() of this domain"""
+        import ctypes as C
+
+        chunks, nbytes = C.c_uint32(0), C.c_uint64(0)
+        self.ctx._chk(self.ctx.lib.cstone_hip_domain_mr_knn_last(self.h, C.byref(chunks), C.byref(nbytes)), "domain_mr_knn_last")
+        return chunks.value, nbytes.value
+
     def multipoles(self):
         """(num_nodes, 8) multipoles of the focus tree as the last gravity() built them (a tensor that aliases the
         domain's array), or None"""

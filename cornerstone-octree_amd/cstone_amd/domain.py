@@ -232,6 +232,24 @@ class Domain:
         self.ctx._chk(rc, "domain_sphere_profiles")
         return counts, sums, flags
 
+    def knn(self, x, y, z, query_centers, k, query_rmax=None, query_self=None):
+        """cstone_hip_domain_knn: Context.knn on the octree, the box and the particles [start_index, end_index) of the
+        last sync; x, y, z laid out like the sync's results.  Returns (neighbors [Q, k] int32, dist2 [Q, k], counts [Q]
+        int32)"""
+        import torch
+
+        nq = query_centers.shape[0]
+        dev = query_centers.device
+        cols = min(max(int(k), 0), 256)
+        neighbors = torch.full((nq, cols), -1, dtype=torch.int32, device=dev)
+        dist2 = torch.full((nq, cols), float("inf"), dtype=query_centers.dtype, device=dev)
+        counts = torch.zeros(nq, dtype=torch.int32, device=dev)
+        P = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        rc = self.ctx.lib.cstone_hip_domain_knn(self.h, P(x), P(y), P(z), P(query_centers), P(query_rmax), P(query_self), nq,
+                                                k, P(neighbors), P(dist2), P(counts))
+        self.ctx._chk(rc, "domain_knn")
+        return neighbors, dist2, counts
+
     def reapply_sync(self, field):
         """Domain::reapplySync: field (n rows of the last sync's input, 1..32 bytes each) in the order of the result"""
         import torch

@@ -833,6 +833,34 @@ void sphericalOverdensityGpu(const T* queryScale, std::size_t numQueries, const 
                    "sphericalOverdensityGpu");
 }
 
+//! the rows of a set of k-nearest-neighbour queries: neighbors and dist2 are [numQueries][k], counts one per query;
+//! unfilled slots hold 0xFFFFFFFF and +inf
+template<class T>
+struct KnnTable
+{
+    DeviceVector<unsigned> neighbors, counts;
+    DeviceVector<T> dist2;
+    void resize(std::size_t numQueries, std::size_t k) { neighbors.resize(numQueries * k), dist2.resize(numQueries * k), counts.resize(numQueries); }
+};
+
+/*! Exactly the k nearest particles of arbitrary points (cstone_hip_knn; the rule is stated in include/cstone_hip.h): for
+ *  every query centre (queryCenters: x, y, z per query, device) the k particles of [first, last) with the smallest
+ *  (squared distance, index), as absolute indices, with their squared distances.  queryRmax (device, nullable): only
+ *  particles with d2 < rmax * rmax; querySelf (device, nullable): one index per query that is left out, 0xFFFFFFFF for
+ *  none.  1 <= k <= CSTONE_KNN_MAX_K.  The table is resized.  Asynchronous. */
+template<class T, class KeyType>
+void knnGpu(const T* x, const T* y, const T* z, LocalIndex first, LocalIndex last, const Box<T>& box,
+            const OctreeNsView<T, KeyType>& tree, const T* queryCenters, const T* queryRmax, const unsigned* querySelf,
+            std::size_t numQueries, unsigned k, KnnTable<T>& table)
+{
+    table.resize(numQueries, std::min<std::size_t>(k, CSTONE_KNN_MAX_K));
+    Context::check(cstone_hip_knn(Context::get(), detail::realBits<T>(), x, y, z, first, last, &box.pod(), tree.childOffsets,
+                                  tree.internalToLeaf, tree.layout, tree.centers, tree.sizes, queryCenters, queryRmax,
+                                  querySelf, unsigned(numQueries), k, table.neighbors.data(), table.dist2.data(),
+                                  table.counts.data()),
+                   "knnGpu");
+}
+
 /*! The transport of the multi-rank Domain on a node of MI355X: RCCL, served from C++ inside libcstone_hip on the context's
  *  stream (csrc/comm_rccl.hip) -- replaces the MPI point-to-point exchanges of the reference
  *  (R/domain/domaindecomp_mpi_gpu.cuh:86-185, R/halos/exchange_halos_gpu.cuh:35-119).  One rank obtains the id
@@ -1119,6 +1147,16 @@ public:
         Context::check(cstone_hip_domain_mr_sphere_profiles(dom_, x, y, z, w, int(8 * sizeof(Tw)), queryCenters, queryScale,
                                                             numQueries, edges, numBins, counts, sums, flags),
                        "MultiRankDomain::sphereProfiles");
+    }
+    /*! The k nearest particles of arbitrary points among the particles of ALL ranks (cstone_hip_domain_mr_knn;
+     *  collective): every rank passes the same queries and k and receives the same rows.  x, y, z: laid out like the
+     *  result arrays, read on the assigned range only.  ids: numQueries * k global ids (positions in the global SFC order,
+     *  as friendsOfFriends labels them), dist2 (nullable) as many squared distances, counts (nullable) numQueries. */
+    void nearestNeighbors(const T* x, const T* y, const T* z, const T* queryCenters, const T* queryRmax, unsigned numQueries,
+                          unsigned k, std::uint64_t* ids, T* dist2, unsigned* counts)
+    {
+        Context::check(cstone_hip_domain_mr_knn(dom_, x, y, z, queryCenters, queryRmax, numQueries, k, ids, dist2, counts),
+                       "MultiRankDomain::nearestNeighbors");
     }
     //! the multipoles of the focus tree that the last computeGravity built: 8 values of T per node (device), or null
     const T* multipoles() const
@@ -1639,6 +1677,37 @@ public:
         mr_->sphereProfiles(x.data(), y.data(), z.data(), w ? w->data() : static_cast<const Tw*>(nullptr), queryCenters.data(),
                             queryScale ? queryScale->data() : nullptr, unsigned(numQueries), edges.data(), numBins,
                             table.counts.data(), w ? table.sums.data() : nullptr, table.flags.data());
+    }
+    /*! The k nearest particles of arbitrary points among the particles [startIndex(), endIndex()) of the last sync
+     *  (cstone_hip_domain_knn: knnGpu on the domain's octree and box).  x, y, z are laid out like the result arrays;
+     *  queryCenters holds x, y, z per query, queryRmax (nullable) a radius limit and querySelf (nullable) an excluded
+     *  index per query. */
+    void nearestNeighbors(const DeviceVector<T>& x, const DeviceVector<T>& y, const DeviceVector<T>& z,
+                          const DeviceVector<T>& queryCenters, const DeviceVector<T>* queryRmax,
+                          const DeviceVector<unsigned>* querySelf, unsigned k, KnnTable<T>& table)
+    {
+        if (mr_) throw std::runtime_error("Domain nearestNeighbors: on several ranks use nearestNeighborsGlobal\n");
+        const std::size_t numQueries = queryCenters.size() / 3;
+        table.resize(numQueries, std::min<std::size_t>(k, CSTONE_KNN_MAX_K));
+        Context::check(cstone_hip_domain_knn(dom_, x.data(), y.data(), z.data(), queryCenters.data(),
+                                             queryRmax ? queryRmax->data() : nullptr, querySelf ? querySelf->data() : nullptr,
+                                             unsigned(numQueries), k, table.neighbors.data(), table.dist2.data(),
+                                             table.counts.data()),
+                       "Domain::nearestNeighbors");
+    }
+    /*! The same among the particles of ALL ranks of a multi-rank domain (MultiRankDomain::nearestNeighbors, collective):
+     *  every rank passes the same queries and k and receives the same rows; ids are global ids (positions in the global
+     *  SFC order), there is no excluded index. */
+    void nearestNeighborsGlobal(const DeviceVector<T>& x, const DeviceVector<T>& y, const DeviceVector<T>& z,
+                                const DeviceVector<T>& queryCenters, const DeviceVector<T>* queryRmax, unsigned k,
+                                DeviceVector<std::uint64_t>& ids, DeviceVector<T>& dist2, DeviceVector<unsigned>& counts)
+    {
+        if (!mr_) throw std::runtime_error("Domain nearestNeighborsGlobal: a domain without collectives (nearestNeighbors)\n");
+        const std::size_t numQueries = queryCenters.size() / 3;
+        const std::size_t cols       = std::min<std::size_t>(k, CSTONE_KNN_MAX_K);
+        ids.resize(numQueries * cols), dist2.resize(numQueries * cols), counts.resize(numQueries);
+        mr_->nearestNeighbors(x.data(), y.data(), z.data(), queryCenters.data(), queryRmax ? queryRmax->data() : nullptr,
+                              unsigned(numQueries), k, ids.data(), dist2.data(), counts.data());
     }
     //! R/domain/domain.hpp:411: stores the flag like the reference does (its member convergeTrees, :661, has no reader
     //! there either: the trees converge on the first sync and take one update step per sync afterwards)

@@ -234,6 +234,22 @@ void instantiateSoftGravity()
     [[maybe_unused]] auto octGet    = &Mr::octupoles;
 }
 
+//! the k-nearest-neighbour calls of the three layers, instantiated (not run here: tests/test_knn.py and
+//! tests/test_knn_mr.py run the entry points behind them, examples/knn_example.cpp runs the first two)
+template<class KeyType, class T>
+void instantiateKnn()
+{
+    using D  = Domain<KeyType, T>;
+    using V  = DeviceVector<T>;
+    using Mr = MultiRankDomain<KeyType, T>;
+    [[maybe_unused]] auto free   = &knnGpu<T, KeyType>;
+    [[maybe_unused]] auto single = &D::nearestNeighbors;
+    [[maybe_unused]] auto global = &D::nearestNeighborsGlobal;
+    [[maybe_unused]] auto multi  = &Mr::nearestNeighbors;
+    [[maybe_unused]] KnnTable<T>* table = nullptr;
+    [[maybe_unused]] V* unused          = nullptr;
+}
+
 //! computeContinuumCsarray for the two concentration functions the oracle's reference build can name (oracle/ref_driver.cpp,
 //! cstone_ref_continuum): leaves, particles and an FNV-1a digest of leaf keys and counts, for tests/test_cpp_layer.py
 template<class KeyType>
@@ -273,6 +289,9 @@ int main()
     instantiateSoftGravity<std::uint64_t, double, float>();
     instantiateSoftGravity<std::uint64_t, float, float>();
     instantiateSoftGravity<std::uint32_t, float, double>();
+    instantiateKnn<std::uint64_t, double>();
+    instantiateKnn<std::uint64_t, float>();
+    instantiateKnn<std::uint32_t, float>();
     continuumDigest<std::uint64_t>("u64", 0);
     continuumDigest<std::uint64_t>("u64", 1);
     continuumDigest<std::uint32_t>("u32", 0);

@@ -1443,6 +1443,87 @@ extern "C"
                                              const void* query_scale, uint32_t num_queries, const double* edges_host,
                                              int num_bins, uint64_t* counts, double* sums, uint32_t* flags);
 
+    /* ---------------------------------------------------------------------------------------------
+     * K NEAREST NEIGHBOURS at arbitrary points (csrc/knn.hip): exactly the k particles nearest to every query centre, in
+     * order, with their squared distances -- densities about a centre, interpolation to probe points, seeds for h.  The
+     * searches above are radius-driven; this one is count-driven.  The rule, stated so that a restatement reproduces every
+     * output with == (tests/knn_support.py is one):
+     *
+     *   T = coordinate type (real_bits).  Query q has a centre c_q (query_centers: T[Q][3], device), optionally a radius
+     *   limit r_q (query_rmax: T[Q], device; NULL: none) and optionally one excluded index s_q (query_self: u32[Q], device;
+     *   NULL or 0xFFFFFFFF: none).
+     *   Offset   d_a = r_j,a - c_q,a in T; on a periodic axis d_a = d_a - len_a * rint(d_a * inv_a) with len and inv in T as
+     *            the neighbour walk has them, for EVERY particle, unconditionally.  d2 = dx*dx + dy*dy + dz*dz, left fold,
+     *            products not fused: offset, fold and d2 of cstone_hip_sphere_profiles.
+     *   Candidates  r2 = r_q * r_q in T, +inf when query_rmax is NULL.  Particle j of [first, last) is a candidate iff
+     *            j != s_q and d2 < r2.  Strict, as in the neighbour search: a particle at exactly r_q is out.  A NaN d2 or
+     *            a NaN r_q yields no candidate (the comparison is false); a negative r_q is not refused, its square is
+     *            used; r_q = 0 yields none.  Particles outside [first, last) never count, and an s_q outside the range
+     *            excludes nothing.
+     *   Result   the candidates ordered by the pair (d2, j) lexicographically: equal distances go to the lower index.
+     *            m = min(k, number of candidates).  neighbors[q][0 .. m) are the first m indices in that order, ABSOLUTE
+     *            indices into the particle arrays as find_neighbors returns them; dist2[q][0 .. m) their d2 in T;
+     *            counts[q] = m.  The slots m .. k hold 0xFFFFFFFF and +inf.  neighbors: u32[Q][k]; dist2: T[Q][k], nullable;
+     *            counts: u32[Q], nullable.
+     *   Flags    none.  The folded distance is defined for every pair, so there is no TOO_WIDE: the fold is 1-Lipschitz
+     *            and the node test stays a lower bound at any radius.
+     *   Tree     the call is the brute force over all (query, particle) pairs, entry for entry; the tree only prunes.  A
+     *            node is skipped when its minimum-image distance (sphere_profiles' node test) exceeds
+     *            sqrt(t2) * (1 + 16 eps) + 64 eps L, t2 the k-th best d2 so far or r2 (derived in csrc/knn.hip).  Query
+     *            centres lie within two box lengths of the particles on a periodic axis, as for the sphere queries.
+     *   Order    the result does not depend on walk order, launch shape, stream or context.  No atomics of any kind,
+     *            except the sticky error word on a traversal stack overflow (ORs 4; the stack is sized for the deepest
+     *            tree).
+     *
+     * knn    : the tree arguments of cstone_hip_sphere_profiles.  1 <= k <= CSTONE_KNN_MAX_K.  CSTONE_E_ARG with nothing
+     *            written: bad real_bits, k out of range, last < first, a null required pointer (everything but query_rmax,
+     *            query_self, dist2, counts) while num_queries > 0.  num_queries == 0: CSTONE_OK.  last == first: CSTONE_OK
+     *            with every row unfilled (0xFFFFFFFF, +inf, count 0).  Asynchronous on the context's stream.
+     *
+     * domain_knn : knn on the octree, the box and [start_index, end_index) of the domain's last sync; x, y, z laid out like
+     *            the sync's results.  CSTONE_E_ARG before the first sync.
+     *
+     * domain_mr_knn : COLLECTIVE.  Every rank passes the same num_queries, k, centres and radius limits and gets the k
+     *            nearest among the particles of ALL ranks.  ids u64[Q][k] are the global ids of cstone_hip_domain_mr_fof,
+     *            offset[rank] + (i - start_index): positions in the global SFC order.  Ties go to the lower global id, so
+     *            the result equals knn on the whole cloud in global SFC order with indices read as ids, whatever the
+     *            number of ranks; unfilled slots hold all ones and +inf.  dist2 and counts are nullable.  There is no
+     *            query_self across ranks: a caller who needs it asks for k + 1.  Each rank searches its ASSIGNED range
+     *            only, on its own octree: the halos are other ranks' assigned particles, so nothing is found twice and the
+     *            halos need no particular reach.  Refused with CSTONE_E_ARG on every rank before any collective, nothing
+     *            written: no sync yet, k out of range.  Then ONE all_gather of {status, num_queries, k, query_rmax given,
+     *            assigned count} per rank: rank-local trouble -- a null array with particles present, no memory -- or a
+     *            num_queries, k or presence of query_rmax that differs between ranks makes every rank return an error
+     *            together, with nothing written; the counts give the id ranges.  Then, per chunk of queries: the local
+     *            search, an all_gather of 16-byte records {bits of d2 widened to u64, global id} over chunk x k slots per
+     *            rank, and a merge kernel (one wave per query, the same k-best list fed from the gathered rows).  A chunk
+     *            holds floor(cap / (16 k P)) queries, at least one: it follows from Q, k and P alone, and the receive
+     *            buffer of the all_gather stays under cap = CSTONE_KNN_MR_GATHER_BYTES (unless a single query's records
+     *            exceed it).  The environment variable CSTONE_KNN_MR_GATHER_BYTES, a positive number of bytes read at
+     *            every call, replaces the cap (for tests of the chunking; it must be the same on every rank).  On a
+     *            communicator of ONE rank there is no collective and the output is that of domain_knn with indices
+     *            turned into ids.  A rank without particles may pass null particle arrays.
+     * knn_mr_chunk_queries : the chunk rule above as a function (host only): queries per all_gather for num_queries, k,
+     *            num_ranks and a cap in bytes.
+     * domain_mr_knn_last : of the domain's last domain_mr_knn call: the all_gather rounds it made (one rank: the chunks
+     *            it merged) and the bytes its receive buffer took (0 on one rank).  Outputs nullable.
+     * ------------------------------------------------------------------------------------------- */
+#define CSTONE_KNN_MAX_K 256
+#define CSTONE_KNN_MR_GATHER_BYTES (256ull << 20)
+    int cstone_hip_knn(cstone_hip_ctx* ctx, int real_bits, const void* x, const void* y, const void* z, uint32_t first,
+                       uint32_t last, const cstone_box* box_host, const int32_t* child_offsets,
+                       const int32_t* internal_to_leaf, const uint32_t* layout, const void* centers, const void* sizes,
+                       const void* query_centers, const void* query_rmax, const uint32_t* query_self, uint32_t num_queries,
+                       uint32_t k, uint32_t* neighbors, void* dist2, uint32_t* counts);
+    int cstone_hip_domain_knn(cstone_hip_domain* dom, const void* x, const void* y, const void* z, const void* query_centers,
+                              const void* query_rmax, const uint32_t* query_self, uint32_t num_queries, uint32_t k,
+                              uint32_t* neighbors, void* dist2, uint32_t* counts);
+    int cstone_hip_domain_mr_knn(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z,
+                                 const void* query_centers, const void* query_rmax, uint32_t num_queries, uint32_t k,
+                                 uint64_t* ids, void* dist2, uint32_t* counts);
+    uint32_t cstone_hip_knn_mr_chunk_queries(uint32_t num_queries, uint32_t k, int num_ranks, uint64_t cap_bytes);
+    int cstone_hip_domain_mr_knn_last(cstone_hip_domain_mr* dom, uint32_t* num_chunks, uint64_t* gather_bytes);
+
 #ifdef __cplusplus
 }
 #endif
