@@ -146,6 +146,11 @@ struct DomainBase
     virtual int knn(const void* x, const void* y, const void* z, const void* queryCenters, const void* queryRmax,
                     const uint32_t* querySelf, uint32_t numQueries, uint32_t k, uint32_t* neighbors, void* dist2,
                     uint32_t* counts) = 0;
+    virtual int pairCounts(const void* x, const void* y, const void* z, const void* w, int wBits, const double* edgesHost,
+                           int numBins, uint64_t* counts, double* sums, uint64_t* statsHost) = 0;
+    virtual int pairCountsCross(const void* x, const void* y, const void* z, const void* w, int wBits, const void* queryCenters,
+                                const void* queryW, uint32_t numQueries, const double* edgesHost, int numBins,
+                                uint64_t* counts, double* sums, uint64_t* statsHost) = 0;
     virtual void stats(cstone_hip_domain_stats* out)     = 0;
     virtual void leafTableStats(uint32_t* used, uint32_t* rejected) = 0;
 };
@@ -323,6 +328,28 @@ public:
         return cstone_hip_knn(ctx_, rb, x, y, z, startIndex_, endIndex_, &box_, fChild_.as<int32_t>(), fItl_.as<int32_t>(),
                               layout_.as<uint32_t>(), fCenters_.p, fSizes_.p, queryCenters, queryRmax, querySelf, numQueries,
                               k, neighbors, dist2, counts);
+    }
+
+    //! cstone_hip_pair_counts on the octree and the box of the last sync: targets [start_index, end_index), sources every
+    //! particle on the rank
+    int pairCounts(const void* x, const void* y, const void* z, const void* w, int wBits, const double* edgesHost, int numBins,
+                   uint64_t* counts, double* sums, uint64_t* statsHost) override
+    {
+        if (firstCall_ || fLeaves_ < 1) return fail(ctx_, CSTONE_E_ARG, "domain_pair_counts: no sync yet");
+        return cstone_hip_pair_counts(ctx_, rb, wBits, x, y, z, w, 0, bufSize_, startIndex_, endIndex_, &box_,
+                                      fChild_.as<int32_t>(), fItl_.as<int32_t>(), layout_.as<uint32_t>(), fCenters_.p, fSizes_.p,
+                                      edgesHost, numBins, counts, sums, statsHost);
+    }
+
+    //! cstone_hip_pair_counts_cross on the octree, the box and [start_index, end_index) of the last sync
+    int pairCountsCross(const void* x, const void* y, const void* z, const void* w, int wBits, const void* queryCenters,
+                        const void* queryW, uint32_t numQueries, const double* edgesHost, int numBins, uint64_t* counts,
+                        double* sums, uint64_t* statsHost) override
+    {
+        if (firstCall_ || fLeaves_ < 1) return fail(ctx_, CSTONE_E_ARG, "domain_pair_counts_cross: no sync yet");
+        return cstone_hip_pair_counts_cross(ctx_, rb, wBits, x, y, z, w, startIndex_, endIndex_, &box_, fChild_.as<int32_t>(),
+                                            fItl_.as<int32_t>(), layout_.as<uint32_t>(), fCenters_.p, fSizes_.p, queryCenters,
+                                            queryW, numQueries, edgesHost, numBins, counts, sums, statsHost);
     }
 
     /*! Domain::updateExpansionCenters (R/domain/domain.hpp:415-421) on one rank = FocusedOctree::updateCenters without its
@@ -1370,6 +1397,24 @@ int cstone_hip_domain_knn(cstone_hip_domain* dom, const void* x, const void* y, 
 {
     if (!dom) return CSTONE_E_ARG;
     return dom->impl->knn(x, y, z, query_centers, query_rmax, query_self, num_queries, k, neighbors, dist2, counts);
+}
+
+int cstone_hip_domain_pair_counts(cstone_hip_domain* dom, const void* x, const void* y, const void* z, const void* w,
+                                  int w_bits, const double* edges_host, int num_bins, uint64_t* counts, double* sums,
+                                  uint64_t* stats_host)
+{
+    if (!dom) return CSTONE_E_ARG;
+    return dom->impl->pairCounts(x, y, z, w, w_bits, edges_host, num_bins, counts, sums, stats_host);
+}
+
+int cstone_hip_domain_pair_counts_cross(cstone_hip_domain* dom, const void* x, const void* y, const void* z, const void* w,
+                                        int w_bits, const void* query_centers, const void* query_w, uint32_t num_queries,
+                                        const double* edges_host, int num_bins, uint64_t* counts, double* sums,
+                                        uint64_t* stats_host)
+{
+    if (!dom) return CSTONE_E_ARG;
+    return dom->impl->pairCountsCross(x, y, z, w, w_bits, query_centers, query_w, num_queries, edges_host, num_bins, counts,
+                                      sums, stats_host);
 }
 
 int cstone_hip_domain_view_get(cstone_hip_domain* dom, cstone_hip_domain_view* out)

@@ -33,6 +33,7 @@
 #include "fof_mr.hpp"
 #include "fof_props.hpp"
 #include "knn.hpp"
+#include "pair_counts.hpp"
 #include "sphere.hpp"
 #include "host_tree.hpp"
 #include "let.hpp"
@@ -382,6 +383,9 @@ struct MrBase
     virtual int knn(const void* x, const void* y, const void* z, const void* queryCenters, const void* queryRmax,
                     uint32_t numQueries, uint32_t k, uint64_t* ids, void* dist2, uint32_t* counts) = 0;
     virtual void knnLast(uint32_t* numChunks, uint64_t* gatherBytes) = 0;
+    virtual int pairCounts(bool cross, const void* x, const void* y, const void* z, const void* w, int wBits,
+                           const void* queryCenters, const void* queryW, uint32_t numQueries, const double* edgesHost,
+                           int numBins, uint64_t* counts, double* sums, uint64_t* statsHost) = 0;
     virtual int multipoles(const void** out, int32_t* numNodes)                           = 0;
     virtual int octupoles(const void** out, int32_t* numNodes)                            = 0;
     virtual int view(cstone_hip_domain_mr_view* out)                                     = 0;
@@ -733,6 +737,24 @@ public:
             ++knnChunks_;
         }
         return CSTONE_OK;
+    }
+
+    /*! Pair counts in radial bins over the particles of all ranks (cstone_hip_domain_mr_pair_counts and ..._cross; the
+     *  rule: include/cstone_hip.h).  Auto: targets are my assigned range, sources everything on the rank, so every ordered
+     *  pair is counted at the owner of i -- under the cover rule of friendsOfFriends.  Cross: every rank bins its assigned
+     *  range about the same queries.  One all-gather lets every rank fail together; one all-reduce of {counts as doubles,
+     *  sums} follows.  A list of stages that share one PairState. */
+    int pairCounts(bool cross, const void* x, const void* y, const void* z, const void* w, int wBits, const void* queryCenters,
+                   const void* queryW, uint32_t numQueries, const double* edgesHost, int numBins, uint64_t* counts, double* sums,
+                   uint64_t* statsHost) override
+    {
+        PairState s{cross, x, y, z, w, wBits, queryCenters, queryW, numQueries, edgesHost, numBins, counts, sums, statsHost};
+        CS_TRY(pairRefuseEverywhere(s));
+        if (P_ == 1) return pairOnOneRank(s);
+        pairLocalTrouble(s);
+        CS_TRY(pairAgree(s));
+        CS_TRY(pairLocal(s));
+        return pairReduce(s);
     }
 
     void knnLast(uint32_t* numChunks, uint64_t* gatherBytes) override
@@ -2587,6 +2609,127 @@ private:
         return CSTONE_OK;
     }
 
+    // ---- pairCounts(), stage by stage
+
+    //! What the stages of one pairCounts() share: the caller's arguments and what the stages before have decided
+    struct PairState
+    {
+        bool cross;
+        const void *x, *y, *z, *w;
+        int wBits;
+        const void *queryCenters, *queryW;
+        uint32_t numQueries;
+        const double* edgesHost;
+        int numBins;
+        uint64_t* counts;
+        double* sums;
+        uint64_t* statsHost;
+        uint32_t si = 0, ei = 0, na = 0, nh = 0;
+        uint64_t trouble = FINE;
+        cstone_hip_domain_mr_octree t{}; // my octree; all null on a rank without particles
+        bool globalW = false;            // some rank with particles has a w: the sums take part in the all-reduce
+        const char* name() const { return cross ? "domain_mr_pair_counts_cross" : "domain_mr_pair_counts"; }
+    };
+
+    //! what is the same on every rank: refused before any collective
+    int pairRefuseEverywhere(PairState& s)
+    {
+        if (firstCall_) return fail(ctx_, CSTONE_E_ARG, "%s: no sync yet", s.name());
+        if (const char* why = pairCountsRefusal(rb, s.wBits, s.w != nullptr, &view_.box, s.edgesHost, s.numBins))
+            return fail(ctx_, CSTONE_E_ARG, "%s: %s", s.name(), why);
+        s.si = view_.start_index, s.ei = view_.end_index, s.nh = view_.num_particles_with_halos, s.na = s.ei - s.si;
+        return CSTONE_OK;
+    }
+
+    //! the single-rank call on my octree, into the caller's arrays.  A rank without assigned particles has nothing to read:
+    //! its empty range zeroes the outputs
+    int pairLocal(PairState& s)
+    {
+        if (s.cross)
+            return cstone_hip_pair_counts_cross(ctx_, rb, s.wBits, s.x, s.y, s.z, s.w, s.si, s.ei, &view_.box, s.t.child_offsets,
+                                                s.t.internal_to_leaf, s.t.layout, s.t.centers, s.t.sizes, s.queryCenters,
+                                                s.w ? s.queryW : nullptr, s.numQueries, s.edgesHost, s.numBins, s.counts, s.sums,
+                                                s.statsHost);
+        return cstone_hip_pair_counts(ctx_, rb, s.wBits, s.x, s.y, s.z, s.w, 0, s.nh, s.si, s.ei, &view_.box, s.t.child_offsets,
+                                      s.t.internal_to_leaf, s.t.layout, s.t.centers, s.t.sizes, s.edgesHost, s.numBins, s.counts,
+                                      s.sums, s.statsHost);
+    }
+
+    //! one rank: no agreement, no cover rule (every particle is on the rank) and no operand
+    int pairOnOneRank(PairState& s)
+    {
+        if (s.na) CS_TRY(octree(&s.t));
+        return pairLocal(s);
+    }
+
+    //! rank-local trouble: collected, not returned
+    void pairLocalTrouble(PairState& s)
+    {
+        const bool queries = s.cross && s.numQueries;
+        if (!s.counts || (s.w && !s.sums) || (queries && !s.queryCenters) || (s.na && (!s.x || !s.y || !s.z)) ||
+            (s.na && s.queryW && !s.w))
+            s.trouble = NULL_ARRAY;
+        else if (!s.cross && viewSync_ != syncs_) s.trouble = STALE_SYNC; // the radii of the cover rule are not the view's
+        else if (sphereBuf_.ensure(ctx_, std::max<size_t>(2 * size_t(s.numBins) * sizeof(double), 256))) s.trouble = NO_MEMORY;
+        else if (s.na && octree(&s.t)) s.trouble = LOCAL_STEP;
+    }
+
+    //! one all-gather of {status, NB, w given, smallest halo radius of a non-empty assigned leaf (auto) or Q (cross)}: every
+    //! rank fails together, also where the ranks disagree or the cover rule fails on any of them
+    int pairAgree(PairState& s)
+    {
+        enum : uint64_t { W_NONE = 0, W_GIVEN = 1, W_ANY = 2 }; // a rank without particles goes with the others
+        const uint64_t INF_BITS = 0x7f800000u;
+        const uint64_t row[4]   = {s.trouble, uint64_t(s.numBins), s.w ? W_GIVEN : s.na ? W_NONE : W_ANY,
+                                   s.cross ? uint64_t(s.numQueries) : INF_BITS};
+        std::vector<uint64_t> rows;
+        CS_TRY(stageRow(row, 4, rows));
+        if (!s.cross && !s.trouble) // (low word of the last entry: the radii are floats)
+            fofMinRadius(ctx_, useLet_ ? let_->haloRadii() : radii_.as<float>(), view_.focus_leaf_counts, view_.start_cell,
+                         view_.end_cell, reinterpret_cast<uint32_t*>(gatherRow() + 3));
+        CS_TRY(gatherRows(4, "all_gather (pair counts)", rows));
+        uint64_t wMode = W_ANY;
+        for (int p = 0; p < P_; ++p)
+        {
+            uint64_t* r = rows.data() + 4 * size_t(p);
+            if (r[0] == FINE && (r[1] != rows[1] || (s.cross && r[3] != rows[3]))) r[0] = MISMATCH;
+            if (r[0] != FINE || r[2] == W_ANY) continue;
+            if (wMode == W_ANY) wMode = r[2];
+            else if (wMode != r[2]) r[0] = MISMATCH;
+        }
+        static const char* const why[NUM_TROUBLES] = {"", "null array", "the last sync was abandoned", "out of device memory", "",
+                                                      "no octree",
+                                                      "the ranks disagree on num_bins, num_queries or whether there is a w"};
+        s.globalW = wMode == W_GIVEN;
+        CS_TRY(agree(s.name(), rows, 4, 0, why));
+        for (int p = 0; p < P_ && !s.cross; ++p)
+        {
+            // the cover rule of friendsOfFriends, against the very f32 radii the halo discovery of the last sync used
+            float radius;
+            const uint32_t bits = uint32_t(rows[4 * size_t(p) + 3]);
+            std::memcpy(&radius, &bits, sizeof radius);
+            if (!(s.edgesHost[s.numBins] <= double(radius)))
+                return fail(ctx_, CSTONE_E_ARG,
+                            "%s: the outer edge %g exceeds the halo radius %g of a leaf of rank %d: a partner may be missing "
+                            "among the halos (refused on every rank)",
+                            s.name(), s.edgesHost[s.numBins], double(radius), p);
+        }
+        return CSTONE_OK;
+    }
+
+    //! one all-reduce: {counts as doubles, sums}
+    int pairReduce(PairState& s)
+    {
+        double* buf    = sphereBuf_.as<double>();
+        const size_t n = size_t(s.numBins);
+        if (s.globalW && !s.w) CS_HIP(ctx_, hipMemsetAsync(buf + n, 0, n * sizeof(double), ctx_->stream));
+        spherePackRows(ctx_, s.counts, s.w ? s.sums : nullptr, n, buf);
+        CS_TRY(callComm(comm_.all_reduce(comm_.user, buf, (s.globalW ? 2 : 1) * n, 0, 0), "all_reduce (pair counts)"));
+        sphereUnpackRows(ctx_, buf, n, s.counts, s.globalW ? s.sums : nullptr);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return fail(ctx_, CSTONE_E_HIP, "%s: %s", s.name(), hipGetErrorString(e));
+        return CSTONE_OK;
+    }
+
     // ---- knn(), stage by stage
 
     //! What the stages of one knn() share: the caller's arguments and what the stages before have decided
@@ -2935,6 +3078,24 @@ int cstone_hip_domain_mr_sphere_profiles(cstone_hip_domain_mr* dom, const void* 
     if (!dom) return CSTONE_E_ARG;
     return dom->impl->sphereProfiles(x, y, z, w, mass_bits, query_centers, query_scale, num_queries, edges_host, num_bins,
                                      counts, sums, flags);
+}
+
+int cstone_hip_domain_mr_pair_counts(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z, const void* w,
+                                     int w_bits, const double* edges_host, int num_bins, uint64_t* counts, double* sums,
+                                     uint64_t* stats_host)
+{
+    if (!dom) return CSTONE_E_ARG;
+    return dom->impl->pairCounts(false, x, y, z, w, w_bits, nullptr, nullptr, 0, edges_host, num_bins, counts, sums, stats_host);
+}
+
+int cstone_hip_domain_mr_pair_counts_cross(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z,
+                                           const void* w, int w_bits, const void* query_centers, const void* query_w,
+                                           uint32_t num_queries, const double* edges_host, int num_bins, uint64_t* counts,
+                                           double* sums, uint64_t* stats_host)
+{
+    if (!dom) return CSTONE_E_ARG;
+    return dom->impl->pairCounts(true, x, y, z, w, w_bits, query_centers, query_w, num_queries, edges_host, num_bins, counts,
+                                 sums, stats_host);
 }
 
 int cstone_hip_domain_mr_knn(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z, const void* query_centers,

@@ -83,7 +83,13 @@ EXPORTS = [
     # exact k nearest neighbours at arbitrary points (csrc/knn.hip)
     "cstone_hip_knn", "cstone_hip_domain_knn", "cstone_hip_domain_mr_knn", "cstone_hip_knn_mr_chunk_queries",
     "cstone_hip_domain_mr_knn_last",
+    # pair counts in radial bins and the two-point correlation function (csrc/pair_counts.hip)
+    "cstone_hip_pair_counts", "cstone_hip_pair_counts_cross", "cstone_hip_domain_pair_counts",
+    "cstone_hip_domain_pair_counts_cross", "cstone_hip_domain_mr_pair_counts", "cstone_hip_domain_mr_pair_counts_cross",
+    "cstone_hip_xi_natural",
 ]
+
+PAIR_MAX_BINS = 64  # CSTONE_PAIR_MAX_BINS
 
 FOF_GROUP_WIDE, FOF_GROUP_MASSLESS = 0x1, 0x2  # CSTONE_FOF_GROUP_*: the flags of the group catalogue
 
@@ -197,7 +203,50 @@ def load_library():
     lib.cstone_hip_knn_mr_chunk_queries.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_uint64]
     lib.cstone_hip_domain_mr_knn_last.restype = C.c_int
     lib.cstone_hip_domain_mr_knn_last.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    # pair counts: (ctx, real_bits, w_bits, x, y, z, w, first, last, t_first, t_last, box*, child_offsets,
+    # internal_to_leaf, layout, centers, sizes, edges*, num_bins, counts, sums, stats*); cross: (ctx, real_bits, w_bits, x,
+    # y, z, w, first, last, box*, child_offsets, internal_to_leaf, layout, centers, sizes, query_centers, query_w,
+    # num_queries, edges*, num_bins, counts, sums, stats*); the domains': (domain, x, y, z, w, w_bits, [query_centers,
+    # query_w, num_queries,] edges*, num_bins, counts, sums, stats*); xi: (counts*, edges*, num_bins, n_targets,
+    # n_partners, volume, xi*), all host
+    stats = C.POINTER(C.c_uint64)
+    lib.cstone_hip_pair_counts.restype = C.c_int
+    lib.cstone_hip_pair_counts.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_uint32] * 4 +
+                                           [C.c_void_p] * 6 + [C.POINTER(C.c_double), C.c_int] + [C.c_void_p] * 2 + [stats])
+    lib.cstone_hip_pair_counts_cross.restype = C.c_int
+    lib.cstone_hip_pair_counts_cross.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_uint32] * 2 +
+                                                 [C.c_void_p] * 8 + [C.c_uint32, C.POINTER(C.c_double), C.c_int] +
+                                                 [C.c_void_p] * 2 + [stats])
+    for fn in (lib.cstone_hip_domain_pair_counts, lib.cstone_hip_domain_mr_pair_counts):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p] * 5 + [C.c_int, C.POINTER(C.c_double), C.c_int] + [C.c_void_p] * 2 + [stats]
+    for fn in (lib.cstone_hip_domain_pair_counts_cross, lib.cstone_hip_domain_mr_pair_counts_cross):
+        fn.restype = C.c_int
+        fn.argtypes = ([C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 2 + [C.c_uint32, C.POINTER(C.c_double), C.c_int] +
+                       [C.c_void_p] * 2 + [stats])
+    lib.cstone_hip_xi_natural.restype = C.c_int
+    lib.cstone_hip_xi_natural.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.c_int, C.c_double, C.c_double,
+                                          C.c_double, C.POINTER(C.c_double)]
     return lib
+
+
+def xi_natural(counts, edges, n_targets, n_partners, volume):
+    """cstone_hip_xi_natural (host, float64): the natural estimator of the two-point correlation function in a PERIODIC
+    box of the given volume from pair counts [NB] over the bin edges [NB + 1]:
+    xi[b] = counts[b] / (n_targets * n_partners * (4 pi / 3) (edges[b+1]^3 - edges[b]^3) / volume) - 1; for auto counts
+    pass n_partners = n - 1.  A bin of zero shell volume or zero expected pairs gives NaN.  Returns a float64 array"""
+    lib = load_library()
+    e, nb = sphere_edges(edges)
+    c = [int(v) for v in (counts.tolist() if hasattr(counts, "tolist") else counts)]
+    if len(c) != nb:
+        raise CstoneError(f"xi_natural: {len(c)} counts for {nb} bins")
+    carr = (C.c_uint64 * max(nb, 1))(*c)
+    out = (C.c_double * max(nb, 1))()
+    rc = lib.cstone_hip_xi_natural(carr, e, nb, float(n_targets), float(n_partners), float(volume), out)
+    if rc != 0:
+        raise CstoneError(f"xi_natural failed ({rc}): 1 .. {PAIR_MAX_BINS} bins with finite, non-negative, strictly "
+                          f"ascending edges are taken")
+    return np.array(out[:nb], dtype=np.float64)
 
 
 def sphere_edges(edges):
@@ -747,6 +796,53 @@ class Context:
             _opt(octree["child_offsets"]), _opt(octree["internal_to_leaf"]), _opt(layout), _opt(centers), _opt(sizes),
             _opt(query_centers), _opt(query_scale), nq, e, nb, _opt(counts), _opt(sums), _opt(flags)), "sphere_profiles")
         return counts, sums, flags
+
+    def pair_counts(self, x, y, z, w, first, last, box, octree, layout, centers, sizes, edges, t_first=None, t_last=None,
+                    counts=None, sums=None, with_stats=False, real_bits=None, w_bits=None):
+        """cstone_hip_pair_counts: the ORDERED pairs (i, j), i in [t_first, t_last) (default: [first, last)), j in
+        [first, last), j != i by index, counted in the half-open distance bins [edges[b], edges[b + 1]), and the products
+        of their weights w (float32 / float64 tensor or None) summed in float64.  edges: NB + 1 host numbers.  Returns
+        (counts [NB] int64, sums [NB] float64 or None without w, stats): stats is None, or with_stats a pair (distance
+        tests issued, pairs binned) -- the call then synchronises.  The rule: include/cstone_hip.h.  counts, sums: tensors
+        to write into instead of new ones; real_bits, w_bits: overrides of what the tensors imply"""
+        torch = _torch()
+        e, nb = sphere_edges(edges)
+        t_first = first if t_first is None else t_first
+        t_last = last if t_last is None else t_last
+        if counts is None:
+            counts = torch.zeros(max(nb, 0), dtype=torch.int64, device=self.device)
+        if sums is None and w is not None:
+            sums = torch.zeros(max(nb, 0), dtype=torch.float64, device=self.device)
+        rb = x.element_size() * 8 if real_bits is None else real_bits
+        wb = (w.element_size() * 8 if w is not None else 64) if w_bits is None else w_bits
+        st = (C.c_uint64 * 2)() if with_stats else None
+        self._chk(self.lib.cstone_hip_pair_counts(
+            self.h, rb, wb, _opt(x), _opt(y), _opt(z), _opt(w), first, last, t_first, t_last,
+            C.cast(C.byref(box), C.c_void_p), _opt(octree["child_offsets"]), _opt(octree["internal_to_leaf"]), _opt(layout),
+            _opt(centers), _opt(sizes), e, nb, _opt(counts), _opt(sums), st), "pair_counts")
+        return counts, sums, (int(st[0]), int(st[1])) if with_stats else None
+
+    def pair_counts_cross(self, x, y, z, w, first, last, box, octree, layout, centers, sizes, query_centers, edges,
+                          query_w=None, num_queries=None, counts=None, sums=None, with_stats=False, real_bits=None,
+                          w_bits=None):
+        """cstone_hip_pair_counts_cross: every pair (query, particle of [first, last)) binned like pair_counts, nothing
+        excluded; query_centers [Q, 3] in the coordinates' type, in any order; query_w [Q] (the type of w) or None for 1.
+        Returns (counts [NB] int64, sums [NB] float64 or None without w, stats)"""
+        torch = _torch()
+        e, nb = sphere_edges(edges)
+        nq = query_centers.shape[0] if num_queries is None else num_queries
+        if counts is None:
+            counts = torch.zeros(max(nb, 0), dtype=torch.int64, device=self.device)
+        if sums is None and w is not None:
+            sums = torch.zeros(max(nb, 0), dtype=torch.float64, device=self.device)
+        rb = query_centers.element_size() * 8 if real_bits is None else real_bits
+        wb = (w.element_size() * 8 if w is not None else 64) if w_bits is None else w_bits
+        st = (C.c_uint64 * 2)() if with_stats else None
+        self._chk(self.lib.cstone_hip_pair_counts_cross(
+            self.h, rb, wb, _opt(x), _opt(y), _opt(z), _opt(w), first, last, C.cast(C.byref(box), C.c_void_p),
+            _opt(octree["child_offsets"]), _opt(octree["internal_to_leaf"]), _opt(layout), _opt(centers), _opt(sizes),
+            _opt(query_centers), _opt(query_w), nq, e, nb, _opt(counts), _opt(sums), st), "pair_counts_cross")
+        return counts, sums, (int(st[0]), int(st[1])) if with_stats else None
 
     def knn(self, x, y, z, first, last, box, octree, layout, centers, sizes, query_centers, k, query_rmax=None,
             query_self=None, num_queries=None, neighbors=None, dist2=None, counts=None, with_dist2=True, with_counts=True,

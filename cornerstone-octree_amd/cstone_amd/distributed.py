@@ -457,6 +457,48 @@ class NativeDistributedDomain:
         self.ctx._chk(rc, "domain_mr_sphere_profiles")
         return counts, sums, flags
 
+    def pair_counts(self, x, y, z, w, edges, num_bins=None, counts=None, sums=None, with_stats=False, w_bits=None):
+        """cstone_hip_domain_mr_pair_counts (COLLECTIVE): the ordered pair counts of Context.pair_counts over the
+        particles of all ranks -- targets the assigned range, sources everything on the rank, halos included, so the
+        outer edge must not exceed the halo radius of any leaf (refused on every rank otherwise).  x, y, z, w (or None)
+        are laid out like the result arrays of the last sync.  Returns (counts [NB] int64, sums [NB] float64 or None
+        without w, stats of this rank or None), counts and sums the same on every rank.  num_bins: override of what
+        edges implies"""
+        return self._pair_counts(self.ctx.lib.cstone_hip_domain_mr_pair_counts, "domain_mr_pair_counts", x, y, z, w, None, None,
+                                 None, edges, num_bins, counts, sums, with_stats, w_bits)
+
+    def pair_counts_cross(self, x, y, z, w, query_centers, edges, query_w=None, num_queries=None, num_bins=None,
+                          counts=None, sums=None, with_stats=False, w_bits=None):
+        """cstone_hip_domain_mr_pair_counts_cross (COLLECTIVE): Context.pair_counts_cross over the particles of all ranks;
+        every rank passes the same query_centers [Q, 3], query_w [Q] or None and edges and bins its assigned range"""
+        nq = query_centers.shape[0] if num_queries is None else num_queries
+        return self._pair_counts(self.ctx.lib.cstone_hip_domain_mr_pair_counts_cross, "domain_mr_pair_counts_cross", x, y, z, w,
+                                 query_centers, query_w, nq, edges, num_bins, counts, sums, with_stats, w_bits)
+
+    def _pair_counts(self, fn, what, x, y, z, w, query_centers, query_w, nq, edges, num_bins, counts, sums, with_stats,
+                     w_bits):
+        torch = _torch()
+        import ctypes as C
+
+        import cstone_amd
+
+        e, nb = cstone_amd.sphere_edges(edges)
+        nb = nb if num_bins is None else num_bins
+        if counts is None:
+            counts = torch.zeros(max(nb, 0), dtype=torch.int64, device=self.ctx.device)
+        if sums is None and w is not None:
+            sums = torch.zeros(max(nb, 0), dtype=torch.float64, device=self.ctx.device)
+        st = (C.c_uint64 * 2)() if with_stats else None
+        P = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        wb = (w.element_size() * 8 if w is not None else 64) if w_bits is None else w_bits
+        cross = () if nq is None else (P(query_centers), P(query_w), nq)
+        rc = fn(self.h, P(x), P(y), P(z), P(w), wb, *cross, e, nb, P(counts), P(sums), st)
+        if rc != 0 and self.coll.error is not None:
+            err, self.coll.error = self.coll.error, None
+            raise err
+        self.ctx._chk(rc, what)
+        return counts, sums, (int(st[0]), int(st[1])) if with_stats else None
+
     def knn(self, x, y, z, query_centers, k, query_rmax=None, num_queries=None, ids=None, dist2=None, counts=None,
             with_dist2=True, with_counts=True):
         """cstone_hip_domain_mr_knn (COLLECTIVE): the k nearest neighbours of Context.knn among the particles of all

@@ -232,6 +232,39 @@ class Domain:
         self.ctx._chk(rc, "domain_sphere_profiles")
         return counts, sums, flags
 
+    def pair_counts(self, x, y, z, w, edges, with_stats=False, counts=None, sums=None, w_bits=None):
+        """cstone_hip_domain_pair_counts: Context.pair_counts on the octree and the box of the last sync, targets
+        [start_index, end_index), sources every particle on the rank; x, y, z and w (or None) laid out like the sync's
+        results.  Returns (counts [NB] int64, sums [NB] float64 or None, stats or None)"""
+        return self._pair_counts(self.ctx.lib.cstone_hip_domain_pair_counts, "domain_pair_counts", x, y, z, w, None, None, edges,
+                                 with_stats, counts, sums, w_bits)
+
+    def pair_counts_cross(self, x, y, z, w, query_centers, edges, query_w=None, with_stats=False, counts=None, sums=None,
+                          w_bits=None):
+        """cstone_hip_domain_pair_counts_cross: Context.pair_counts_cross on the octree, the box and the particles
+        [start_index, end_index) of the last sync.  Returns (counts [NB] int64, sums [NB] float64 or None, stats or None)"""
+        return self._pair_counts(self.ctx.lib.cstone_hip_domain_pair_counts_cross, "domain_pair_counts_cross", x, y, z, w,
+                                 query_centers, query_w, edges, with_stats, counts, sums, w_bits)
+
+    def _pair_counts(self, fn, what, x, y, z, w, query_centers, query_w, edges, with_stats, counts, sums, w_bits):
+        import torch
+
+        from . import sphere_edges
+
+        e, nb = sphere_edges(edges)
+        dev = self.ctx.device
+        if counts is None:
+            counts = torch.zeros(max(nb, 0), dtype=torch.int64, device=dev)
+        if sums is None and w is not None:
+            sums = torch.zeros(max(nb, 0), dtype=torch.float64, device=dev)
+        st = (C.c_uint64 * 2)() if with_stats else None
+        P = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        wb = (w.element_size() * 8 if w is not None else 64) if w_bits is None else w_bits
+        cross = () if query_centers is None else (P(query_centers), P(query_w), query_centers.shape[0])
+        rc = fn(self.h, P(x), P(y), P(z), P(w), wb, *cross, e, nb, P(counts), P(sums), st)
+        self.ctx._chk(rc, what)
+        return counts, sums, (int(st[0]), int(st[1])) if with_stats else None
+
     def knn(self, x, y, z, query_centers, k, query_rmax=None, query_self=None):
         """cstone_hip_domain_knn: Context.knn on the octree, the box and the particles [start_index, end_index) of the
         last sync; x, y, z laid out like the sync's results.  Returns (neighbors [Q, k] int32, dist2 [Q, k], counts [Q]

@@ -811,6 +811,64 @@ void sphereProfilesGpu(const T* x, const T* y, const T* z, const Tw* w, LocalInd
                    "sphereProfilesGpu");
 }
 
+//! what a pair-count call leaves: counts and sums are [numBins] on the device; stats = {distance tests issued, pairs binned}
+struct PairCountTable
+{
+    DeviceVector<std::uint64_t> counts;
+    DeviceVector<double> sums;
+    std::uint64_t stats[2] = {0, 0};
+    void resize(std::size_t numBins, bool weights) { counts.resize(numBins), sums.resize(weights ? numBins : 0); }
+};
+
+/*! Pair counts in radial bins (cstone_hip_pair_counts; the rule is stated in include/cstone_hip.h): the ORDERED pairs
+ *  (i, j), i in [tFirst, tLast), j in [first, last), j != i by index, counted in the half-open distance bins [edges[b],
+ *  edges[b + 1]), and the products of their weights w (float or double, nullable) summed in double.  edges: numBins + 1
+ *  host values.  The table is resized.  withStats: table.stats is filled and the call synchronises. */
+template<class T, class Tw, class KeyType>
+void pairCountsGpu(const T* x, const T* y, const T* z, const Tw* w, LocalIndex first, LocalIndex last, LocalIndex tFirst,
+                   LocalIndex tLast, const Box<T>& box, const OctreeNsView<T, KeyType>& tree, const std::vector<double>& edges,
+                   PairCountTable& table, bool withStats = false)
+{
+    const int numBins = int(edges.size()) - 1;
+    table.resize(std::size_t(std::max(numBins, 0)), w != nullptr);
+    Context::check(cstone_hip_pair_counts(Context::get(), detail::realBits<T>(), int(8 * sizeof(Tw)), x, y, z, w, first, last,
+                                          tFirst, tLast, &box.pod(), tree.childOffsets, tree.internalToLeaf, tree.layout,
+                                          tree.centers, tree.sizes, edges.data(), numBins, table.counts.data(),
+                                          w ? table.sums.data() : nullptr, withStats ? table.stats : nullptr),
+                   "pairCountsGpu");
+}
+
+/*! The same about arbitrary points (cstone_hip_pair_counts_cross): every pair (query, particle of [first, last)), nothing
+ *  excluded.  queryCenters: x, y, z per query, device, in any order; queryW (nullable: 1) one weight per query. */
+template<class T, class Tw, class KeyType>
+void pairCountsCrossGpu(const T* x, const T* y, const T* z, const Tw* w, LocalIndex first, LocalIndex last, const Box<T>& box,
+                        const OctreeNsView<T, KeyType>& tree, const T* queryCenters, const Tw* queryW, std::size_t numQueries,
+                        const std::vector<double>& edges, PairCountTable& table, bool withStats = false)
+{
+    const int numBins = int(edges.size()) - 1;
+    table.resize(std::size_t(std::max(numBins, 0)), w != nullptr);
+    Context::check(cstone_hip_pair_counts_cross(Context::get(), detail::realBits<T>(), int(8 * sizeof(Tw)), x, y, z, w, first,
+                                                last, &box.pod(), tree.childOffsets, tree.internalToLeaf, tree.layout,
+                                                tree.centers, tree.sizes, queryCenters, queryW, unsigned(numQueries),
+                                                edges.data(), numBins, table.counts.data(), w ? table.sums.data() : nullptr,
+                                                withStats ? table.stats : nullptr),
+                   "pairCountsCrossGpu");
+}
+
+/*! The natural estimator of the two-point correlation function in a PERIODIC box (cstone_hip_xi_natural; host, double):
+ *  xi[b] = counts[b] / (nTargets * nPartners * (4 pi / 3) (edges[b+1]^3 - edges[b]^3) / volume) - 1.  For auto counts
+ *  nPartners = n - 1.  A bin without expected pairs gives NaN.  Estimators with random catalogues are the client's
+ *  arithmetic on the cross counts. */
+inline std::vector<double> xiNatural(const std::vector<std::uint64_t>& counts, const std::vector<double>& edges, double nTargets,
+                                     double nPartners, double volume)
+{
+    std::vector<double> xi(counts.size());
+    if (counts.size() + 1 != edges.size() ||
+        cstone_hip_xi_natural(counts.data(), edges.data(), int(counts.size()), nTargets, nPartners, volume, xi.data()) != CSTONE_OK)
+        throw std::runtime_error("xiNatural: one count per bin and finite, non-negative, strictly ascending edges are taken\n");
+    return xi;
+}
+
 //! what sphericalOverdensityGpu leaves: R_Delta, M_Delta and the CSTONE_SPHERE_TOO_WIDE / CSTONE_SO_* bits per query
 struct SphericalOverdensityTable
 {
@@ -1147,6 +1205,27 @@ public:
         Context::check(cstone_hip_domain_mr_sphere_profiles(dom_, x, y, z, w, int(8 * sizeof(Tw)), queryCenters, queryScale,
                                                             numQueries, edges, numBins, counts, sums, flags),
                        "MultiRankDomain::sphereProfiles");
+    }
+    /*! Pair counts in radial bins over the particles of ALL ranks (cstone_hip_domain_mr_pair_counts; collective): targets
+     *  are the assigned range, sources everything on the rank, so every ordered pair is counted once and the outer edge
+     *  must not exceed the halo radius of any leaf.  counts, sums (nullable without w): numBins; stats (nullable): this
+     *  rank's {tests issued, pairs binned}. */
+    template<class Tw>
+    void pairCounts(const T* x, const T* y, const T* z, const Tw* w, const double* edges, int numBins, std::uint64_t* counts,
+                    double* sums, std::uint64_t* stats = nullptr)
+    {
+        Context::check(cstone_hip_domain_mr_pair_counts(dom_, x, y, z, w, int(8 * sizeof(Tw)), edges, numBins, counts, sums, stats),
+                       "MultiRankDomain::pairCounts");
+    }
+    //! ... about arbitrary points (cstone_hip_domain_mr_pair_counts_cross; collective): every rank passes the same queries
+    template<class Tw>
+    void pairCountsCross(const T* x, const T* y, const T* z, const Tw* w, const T* queryCenters, const Tw* queryW,
+                         unsigned numQueries, const double* edges, int numBins, std::uint64_t* counts, double* sums,
+                         std::uint64_t* stats = nullptr)
+    {
+        Context::check(cstone_hip_domain_mr_pair_counts_cross(dom_, x, y, z, w, int(8 * sizeof(Tw)), queryCenters, queryW,
+                                                              numQueries, edges, numBins, counts, sums, stats),
+                       "MultiRankDomain::pairCountsCross");
     }
     /*! The k nearest particles of arbitrary points among the particles of ALL ranks (cstone_hip_domain_mr_knn;
      *  collective): every rank passes the same queries and k and receives the same rows.  x, y, z: laid out like the
@@ -1677,6 +1756,62 @@ public:
         mr_->sphereProfiles(x.data(), y.data(), z.data(), w ? w->data() : static_cast<const Tw*>(nullptr), queryCenters.data(),
                             queryScale ? queryScale->data() : nullptr, unsigned(numQueries), edges.data(), numBins,
                             table.counts.data(), w ? table.sums.data() : nullptr, table.flags.data());
+    }
+    /*! Pair counts in radial bins over the last sync (cstone_hip_domain_pair_counts: pairCountsGpu on the domain's octree
+     *  and box, targets [startIndex(), endIndex()), sources every particle on the rank).  x, y, z and w (nullable) are laid
+     *  out like the result arrays. */
+    template<class Tw>
+    void pairCounts(const DeviceVector<T>& x, const DeviceVector<T>& y, const DeviceVector<T>& z, const DeviceVector<Tw>* w,
+                    const std::vector<double>& edges, PairCountTable& table, bool withStats = false)
+    {
+        if (mr_) throw std::runtime_error("Domain pairCounts: on several ranks use pairCountsGlobal\n");
+        const int numBins = int(edges.size()) - 1;
+        table.resize(std::size_t(std::max(numBins, 0)), w != nullptr);
+        Context::check(cstone_hip_domain_pair_counts(dom_, x.data(), y.data(), z.data(), w ? w->data() : nullptr,
+                                                     int(8 * sizeof(Tw)), edges.data(), numBins, table.counts.data(),
+                                                     w ? table.sums.data() : nullptr, withStats ? table.stats : nullptr),
+                       "Domain::pairCounts");
+    }
+    //! ... about arbitrary points (cstone_hip_domain_pair_counts_cross); queryCenters holds x, y, z per query
+    template<class Tw>
+    void pairCountsCross(const DeviceVector<T>& x, const DeviceVector<T>& y, const DeviceVector<T>& z,
+                         const DeviceVector<Tw>* w, const DeviceVector<T>& queryCenters, const DeviceVector<Tw>* queryW,
+                         const std::vector<double>& edges, PairCountTable& table, bool withStats = false)
+    {
+        if (mr_) throw std::runtime_error("Domain pairCountsCross: on several ranks use pairCountsCrossGlobal\n");
+        const int numBins = int(edges.size()) - 1;
+        table.resize(std::size_t(std::max(numBins, 0)), w != nullptr);
+        Context::check(cstone_hip_domain_pair_counts_cross(dom_, x.data(), y.data(), z.data(), w ? w->data() : nullptr,
+                                                           int(8 * sizeof(Tw)), queryCenters.data(),
+                                                           queryW ? queryW->data() : nullptr, unsigned(queryCenters.size() / 3),
+                                                           edges.data(), numBins, table.counts.data(),
+                                                           w ? table.sums.data() : nullptr, withStats ? table.stats : nullptr),
+                       "Domain::pairCountsCross");
+    }
+    /*! The same over the particles of ALL ranks of a multi-rank domain (MultiRankDomain::pairCounts, collective) */
+    template<class Tw>
+    void pairCountsGlobal(const DeviceVector<T>& x, const DeviceVector<T>& y, const DeviceVector<T>& z,
+                          const DeviceVector<Tw>* w, const std::vector<double>& edges, PairCountTable& table,
+                          bool withStats = false)
+    {
+        if (!mr_) throw std::runtime_error("Domain pairCountsGlobal: a domain without collectives (pairCounts)\n");
+        const int numBins = int(edges.size()) - 1;
+        table.resize(std::size_t(std::max(numBins, 0)), w != nullptr);
+        mr_->pairCounts(x.data(), y.data(), z.data(), w ? w->data() : static_cast<const Tw*>(nullptr), edges.data(), numBins,
+                        table.counts.data(), w ? table.sums.data() : nullptr, withStats ? table.stats : nullptr);
+    }
+    template<class Tw>
+    void pairCountsCrossGlobal(const DeviceVector<T>& x, const DeviceVector<T>& y, const DeviceVector<T>& z,
+                               const DeviceVector<Tw>* w, const DeviceVector<T>& queryCenters, const DeviceVector<Tw>* queryW,
+                               const std::vector<double>& edges, PairCountTable& table, bool withStats = false)
+    {
+        if (!mr_) throw std::runtime_error("Domain pairCountsCrossGlobal: a domain without collectives (pairCountsCross)\n");
+        const int numBins = int(edges.size()) - 1;
+        table.resize(std::size_t(std::max(numBins, 0)), w != nullptr);
+        mr_->pairCountsCross(x.data(), y.data(), z.data(), w ? w->data() : static_cast<const Tw*>(nullptr), queryCenters.data(),
+                             queryW ? queryW->data() : static_cast<const Tw*>(nullptr), unsigned(queryCenters.size() / 3),
+                             edges.data(), numBins, table.counts.data(), w ? table.sums.data() : nullptr,
+                             withStats ? table.stats : nullptr);
     }
     /*! The k nearest particles of arbitrary points among the particles [startIndex(), endIndex()) of the last sync
      *  (cstone_hip_domain_knn: knnGpu on the domain's octree and box).  x, y, z are laid out like the result arrays;

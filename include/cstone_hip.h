@@ -1524,6 +1524,118 @@ extern "C"
     uint32_t cstone_hip_knn_mr_chunk_queries(uint32_t num_queries, uint32_t k, int num_ranks, uint64_t cap_bytes);
     int cstone_hip_domain_mr_knn_last(cstone_hip_domain_mr* dom, uint32_t* num_chunks, uint64_t* gather_bytes);
 
+    /* ---------------------------------------------------------------------------------------------
+     * PAIR COUNTS IN RADIAL BINS (csrc/pair_counts.hip): the histogram DD(r) of pair separations and, from it, the
+     * two-point correlation function xi(r).  The third kind of walk: 64 consecutive targets share one traversal, as in
+     * the neighbour search, but the pair test is the authority and the tree only prunes, as for the sphere queries -- a
+     * pair across a cell face is never lost.  The rule, stated so that a restatement reproduces the counts with == and the
+     * sums within the bound of an arbitrary order of addition (tests/pair_counts_support.py is one):
+     *
+     *   T = coordinate type (real_bits).  edges_host[0 .. NB]: HOST doubles, finite, edges[0] >= 0, strictly ascending,
+     *   1 <= NB <= CSTONE_PAIR_MAX_BINS.  e2_b = T(edges[b]) * T(edges[b]) in T for b = 0 .. NB.
+     *   Auto     every ORDERED pair (i, j) with i in the target range [t_first, t_last), j in the source range
+     *            [first, last), first <= t_first <= t_last <= last, and j != i BY INDEX.  Coincident distinct particles
+     *            are pairs; a particle is never its own partner.
+     *   Cross    every pair (query q, particle j of [first, last)); the targets are num_queries arbitrary points
+     *            (query_centers: T[Q][3], device).  Nothing is excluded: a query that coincides with a particle counts it
+     *            at d2 = 0.  The caller need not order the queries; the counts do not depend on their order.
+     *   Offset   d_a = r_j,a - r_i,a in T (r_i the target); on a periodic axis d_a = d_a - len_a * rint(d_a * inv_a) with
+     *            len and inv in T as the neighbour walk has them (len = T(hi) - T(lo), inv = T(1) / len), for EVERY pair,
+     *            unconditionally.  d2 = dx*dx + dy*dy + dz*dz, left fold, products not fused.
+     *   Bin      the pair falls in bin b iff  e2_b <= d2 < e2_{b+1}.  Half-open: a pair at exactly edges[NB] is outside,
+     *            one inside edges[0] is in no bin, d2 = 0 falls in bin 0 iff edges[0] == 0.
+     *   Outputs  counts u64[NB], exact.  sums double[NB] = sum over the bin's pairs of double(w_i) * double(w_j), present
+     *            iff w is given (w_bits: 32 or 64); w == NULL: sums is not written and may be NULL.  Cross: w_i is
+     *            query_w[q] (w_bits too), 1 when query_w is NULL; a query_w without a w is refused.  Nothing per particle
+     *            is written.
+     *   Tree     the call is the brute force over all pairs, count for count.  A wave forms the exact bounding box of its
+     *            64 targets; a node is skipped when the minimum-image distance of the two boxes -- centre offset folded,
+     *            |d| - size_node - size_box, clamped at 0 -- exceeds edges[NB] * (1 + 16 eps) + 256 eps L, L = the largest
+     *            of |lo_a|, |hi_a|, len_a, eps that of T: a relative term for the squares and an ABSOLUTE one for the
+     *            cancellation both boxes bring (derived in csrc/pair_counts.hip; it takes query centres within two box
+     *            lengths of the particles on a periodic axis).
+     *   Order    no floating-point atomics anywhere, and no integer ones.  Every lane adds to its own accumulators, the 64
+     *            lanes of a bin are combined in a fixed tree into one partial row per workgroup, and a second kernel adds
+     *            the rows in a fixed order.  The number of rows follows from the sizes of the two ranges alone: the same
+     *            input gives the same bits of sums in every run, on every stream and context.  Cross: the sums depend on
+     *            the order the caller passes the queries in (the counts do not).
+     *
+     * pair_counts : x, y, z (T), w (nullable), the tree arguments of cstone_hip_friends_of_friends.  CSTONE_E_ARG with
+     *            nothing written: bad real_bits, bad w_bits with a w, num_bins outside 1 .. CSTONE_PAIR_MAX_BINS, edges
+     *            that are not finite, negative or not strictly ascending, a null box, edges[NB] >= half of any periodic
+     *            edge of the box (as friends_of_friends refuses its linking length; there is no TOO_WIDE flag here),
+     *            ranges out of order (last < first, t_last < t_first, t_first < first, t_last > last), a null counts, a
+     *            null sums with a w, a null array with a non-empty target range.  An empty target range: CSTONE_OK with
+     *            counts (and sums with a w) zeroed.  A traversal stack overflow ORs 4 into the sticky error word; the stack
+     *            is sized for the deepest tree.  stats_host (nullable, u64[2], HOST): {distance tests issued for existing
+     *            targets, pairs binned}; the call synchronises the stream when it is given and is asynchronous otherwise.
+     *            Their quotient is the price of sharing a traversal among 64 targets.  A count per lane is kept in 32
+     *            bits; the number of partial rows grows where that could wrap.
+     *
+     * pair_counts_cross : the same with query_centers, query_w (nullable) and num_queries for the target range.  The
+     *            call encodes 64-bit Hilbert keys of the centres in the box, sorts them and gathers centres and weights
+     *            into the context's workspace, then runs the same kernel without the exclusion.  A centre outside an
+     *            open box takes the key the encode's clamping gives it: the order only serves coherence.  num_queries ==
+     *            0 or last == first: CSTONE_OK with zeroed outputs.
+     *
+     * domain_pair_counts, domain_pair_counts_cross : on the octree and the box of the domain's last sync; x, y, z, w laid
+     *            out like the sync's results.  Targets (auto) are the assigned range [start_index, end_index), sources
+     *            every particle on the rank, [0, num_particles_with_halos); the cross counts bin the assigned range.
+     *            CSTONE_E_ARG before the first sync.
+     *
+     * domain_mr_pair_counts : COLLECTIVE.  Targets are each rank's assigned range, sources everything on the rank, halos
+     *            included: every ordered pair is counted once, at the owner of i, and the counts do not depend on the
+     *            number of ranks.  That needs the COVER rule of cstone_hip_domain_mr_fof: edges[NB] <= the kept f32 halo
+     *            radius of every non-empty assigned leaf of every rank; there is no bound on a communicator of one rank.
+     *            Refused with CSTONE_E_ARG on every rank before any collective, nothing written: no sync yet, whatever
+     *            pair_counts refuses of real_bits, w_bits, bins, edges and the box.  Then ONE all_gather of {status,
+     *            num_bins, w given, smallest halo radius} per rank: rank-local trouble -- a null array with particles
+     *            present, no memory, a num_bins that differs between ranks, a w on some ranks with particles and none on
+     *            others, the cover rule failed anywhere -- makes every rank return an error together, nothing written.
+     *            Then the local counts and ONE all_reduce (f64, sum) over a single buffer with the counts as doubles
+     *            (exact below 2^53) and the sums, converted back on the device.  SUMS across ranks depend on the
+     *            collective's order of addition.  stats_host is this rank's.  A rank without particles may pass null
+     *            particle arrays.
+     * domain_mr_pair_counts_cross : COLLECTIVE.  Every rank passes the same queries and bins its ASSIGNED range only; the
+     *            halos need no reach.  One all_gather of {status, num_queries, num_bins, w given}, one all_reduce.
+     *
+     * xi_natural : HOST, no GPU, all in double.  The natural estimator for a PERIODIC box, where the expected pair count
+     *            of a shell is known in closed form:
+     *              xi[b] = counts[b] / (n_targets * n_partners * (4 pi / 3) * (edges[b+1]^3 - edges[b]^3) / volume) - 1,
+     *            pi = 3.14159265358979323846, the cubes as e * e * e.  For auto counts the caller passes n_partners =
+     *            n - 1.  A bin of zero shell volume or zero expected pairs gives NaN.  CSTONE_E_ARG: a null array, bad
+     *            edges.  Estimators with random catalogues (Landy-Szalay ...) are the client's arithmetic on the cross
+     *            counts.
+     * ------------------------------------------------------------------------------------------- */
+#define CSTONE_PAIR_MAX_BINS 64
+    int cstone_hip_pair_counts(cstone_hip_ctx* ctx, int real_bits, int w_bits, const void* x, const void* y, const void* z,
+                               const void* w, uint32_t first, uint32_t last, uint32_t t_first, uint32_t t_last,
+                               const cstone_box* box_host, const int32_t* child_offsets, const int32_t* internal_to_leaf,
+                               const uint32_t* layout, const void* centers, const void* sizes, const double* edges_host,
+                               int num_bins, uint64_t* counts, double* sums, uint64_t* stats_host);
+    int cstone_hip_pair_counts_cross(cstone_hip_ctx* ctx, int real_bits, int w_bits, const void* x, const void* y,
+                                     const void* z, const void* w, uint32_t first, uint32_t last, const cstone_box* box_host,
+                                     const int32_t* child_offsets, const int32_t* internal_to_leaf, const uint32_t* layout,
+                                     const void* centers, const void* sizes, const void* query_centers, const void* query_w,
+                                     uint32_t num_queries, const double* edges_host, int num_bins, uint64_t* counts,
+                                     double* sums, uint64_t* stats_host);
+    int cstone_hip_domain_pair_counts(cstone_hip_domain* dom, const void* x, const void* y, const void* z, const void* w,
+                                      int w_bits, const double* edges_host, int num_bins, uint64_t* counts, double* sums,
+                                      uint64_t* stats_host);
+    int cstone_hip_domain_pair_counts_cross(cstone_hip_domain* dom, const void* x, const void* y, const void* z,
+                                            const void* w, int w_bits, const void* query_centers, const void* query_w,
+                                            uint32_t num_queries, const double* edges_host, int num_bins, uint64_t* counts,
+                                            double* sums, uint64_t* stats_host);
+    int cstone_hip_domain_mr_pair_counts(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z,
+                                         const void* w, int w_bits, const double* edges_host, int num_bins, uint64_t* counts,
+                                         double* sums, uint64_t* stats_host);
+    int cstone_hip_domain_mr_pair_counts_cross(cstone_hip_domain_mr* dom, const void* x, const void* y, const void* z,
+                                               const void* w, int w_bits, const void* query_centers, const void* query_w,
+                                               uint32_t num_queries, const double* edges_host, int num_bins,
+                                               uint64_t* counts, double* sums, uint64_t* stats_host);
+    int cstone_hip_xi_natural(const uint64_t* counts, const double* edges_host, int num_bins, double n_targets,
+                              double n_partners, double volume, double* xi_host);
+
 #ifdef __cplusplus
 }
 #endif
