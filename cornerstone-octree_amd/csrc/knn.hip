@@ -36,7 +36,7 @@
 // has d2 > t2 or (d2 == t2 and j above tau's) where t2 is the d2 of tau.  The margin of sphere.hip carries over with
 // e = fl(sqrt(t2)) in the place of e_NB: per axis the node's clamped offset as computed is at most the particle's
 // + 45 u L (u = eps / 2; the roundings of the two folds, of the key normalisation and of centre and size: all ABSOLUTE,
-// derived at sphereAbsMargin), over three axes < 64 eps L; the squares, the sums, the comparison and here the square root
+// derived at sphereProfilesKernel), over three axes < 64 eps L; the squares, the sums, the comparison and here the square root
 // (one more relative rounding: a particle with d2 <= t2 has sqrt(d2) <= e (1 + u)) are covered by 1 + 16 eps.  Hence
 //     skip iff  dist2_node > (fl(sqrt(t2)) * (1 + 16 eps) + 64 eps L)^2.
 // A node at distance exactly sqrt(t2) is OPENED: a particle in it at exactly that distance with an index below tau's
@@ -44,11 +44,7 @@
 // query without radius, list not full) gives an infinite threshold: every node is opened.  !(>): a NaN anywhere opens
 // the node and the particle test decides.  tau only descends, so a test against an older tau only opens too much.
 //
-// The stack.  The bound of sphere.hip holds as it stands, since it does not look at the order inside a batch: call what
-// one step pushes a batch (at most 64 nodes) with the label 1 + the lowest level among the nodes the step popped.  A step
-// pops from the top: whole batches and at most a part of one more, B; every node it pops has a level >= label(B), so its
-// own batch carries a label above B's.  Labels of live batches ascend strictly from bottom to top and lie in 1 .. 20:
-// never more than 1 + 20 * 64 entries.  KNN_STACK = 64 * 21; an overflow ORs 4 into the sticky error word.
+// The walk, its stack and the stack's bound are those of wave_walk.hpp; the bound does not look at the order inside a batch.
 //
 // LDS per wave: the stack, 5 376 bytes.  No atomics except that error word.
 #include <cmath>
@@ -59,14 +55,13 @@
 #include "ctx.hpp"
 #include "knn.hpp"
 #include "wave_lanes.hpp"
+#include "wave_walk.hpp"
 
 namespace cship
 {
 
 namespace
 {
-
-constexpr int KNN_STACK = 64 * 21;
 
 template<class T>
 struct KnnKey
@@ -298,7 +293,7 @@ __global__ __launch_bounds__(64) void knnKernel(const T* __restrict__ x, const T
                                                 T absMargin, Out out, int* __restrict__ errors)
 {
     using Key = KnnKey<T>;
-    __shared__ int32_t stack[KNN_STACK];
+    __shared__ int32_t stack[WALK_STACK];
 
     const unsigned lane = threadIdx.x;
     const size_t q      = blockIdx.x;
@@ -318,17 +313,7 @@ __global__ __launch_bounds__(64) void knnKernel(const T* __restrict__ x, const T
         thr2        = thr * thr;
     };
     setThreshold();
-    // the squared distance of the query to the box of node n, as sphere.hip computes it
-    auto nodeD2 = [&](int32_t n) -> T
-    {
-        T dx = tree.centers[3 * n] - cx, dy = tree.centers[3 * n + 1] - cy, dz = tree.centers[3 * n + 2] - cz;
-        dx = cstone_hip::detail::foldAxis<T>(dx, box.len[0], box.inv[0], px);
-        dy = cstone_hip::detail::foldAxis<T>(dy, box.len[1], box.inv[1], py);
-        dz = cstone_hip::detail::foldAxis<T>(dz, box.len[2], box.inv[2], pz);
-        dx = fabs(dx) - tree.sizes[3 * n], dy = fabs(dy) - tree.sizes[3 * n + 1], dz = fabs(dz) - tree.sizes[3 * n + 2];
-        dx = dx > T(0) ? dx : T(0), dy = dy > T(0) ? dy : T(0), dz = dz > T(0) ? dz : T(0);
-        return dx * dx + dy * dy + dz * dz;
-    };
+    auto nodeD2 = [&](int32_t n) -> T { return walkNodeDist2(tree, box, n, cx, cy, cz); };
     // particles [jb, je) (wave-uniform), clipped to the range: the particle test, the authority
     auto scan = [&](uint32_t jb, uint32_t je)
     {
@@ -378,73 +363,28 @@ __global__ __launch_bounds__(64) void knnKernel(const T* __restrict__ x, const T
             scan(tree.layout[leaf], tree.layout[leaf + 1]);
         }
 
-        int top = 0;
-        if (seed != 0)
+        T nd = T(0); // the distance of the child this lane tested last
+        auto open = [&](int32_t child) -> bool
         {
-            if (lane == 0) stack[0] = 0;
-            top = 1;
-        }
-        while (top > 0)
+            nd = nodeD2(child);
+            return !(nd > thr2) && child != seed;
+        };
+        // what the leaves of a step brought tau down to may close nodes that were open a moment ago
+        auto still = [&]() -> bool { return !(nd > thr2); };
+        // nearest on top: sorted ascending by (distance, node), written downwards from the new top
+        auto place = [&](int32_t* dst, bool push, uint64_t, int numPush, int32_t child)
         {
-            const int take = min(top, 8);
-            const int slot = int(lane >> 3);
-            int32_t child  = 0;
-            bool go = false, isLeaf = false;
-            uint32_t jb = 0, je = 0;
-            T nd = T(0);
-            if (slot < take)
-            {
-                const int32_t par = stack[top - 1 - slot]; // LDS accesses of one wave: in program order
-                child             = tree.childOffsets[par] + int32_t(lane & 7u);
-                nd                = nodeD2(child);
-                go                = !(nd > thr2) && child != seed;
-                if (go && tree.childOffsets[child] == 0)
-                {
-                    isLeaf             = true;
-                    const int32_t leaf = tree.internalToLeaf[child];
-                    jb = tree.layout[leaf], je = tree.layout[leaf + 1];
-                }
-            }
-            top -= take;
-            // the opened leaves in lane order; ranges that touch are read as one
-            uint64_t lm = __ballot(go && isLeaf);
-            uint32_t rb = 0, re = 0;
-            while (lm)
-            {
-                const int src = __ffsll((unsigned long long)lm) - 1;
-                lm &= lm - 1;
-                const uint32_t b = uint32_t(__builtin_amdgcn_readlane(int(jb), src));
-                const uint32_t e = uint32_t(__builtin_amdgcn_readlane(int(je), src));
-                if (b == re) { re = e; }
-                else
-                {
-                    if (re > rb) scan(rb, re);
-                    rb = b, re = e;
-                }
-            }
-            if (re > rb) scan(rb, re);
-
-            // what the leaves of this step brought tau down to may close nodes that were open a moment ago
-            const bool push   = go && !isLeaf && !(nd > thr2);
-            const uint64_t pm = __ballot(push);
-            const int numPush = __popcll(pm);
-            if (top + numPush > KNN_STACK)
-            {
-                if (lane == 0) atomicOr(errors, 4);
-                break;
-            }
             if (numPush > 1)
             {
-                // nearest on top: sorted ascending by (distance, node), written downwards from the new top
                 Key n;
                 n.d = push ? knnBits<T>(nd) : ~typename Key::Bits(0);
                 n.j = push ? uint32_t(child) : ~0u;
                 knnSort64(n, lane);
-                if (int(lane) < numPush) stack[top + numPush - 1 - int(lane)] = int32_t(n.j);
+                if (int(lane) < numPush) dst[numPush - 1 - int(lane)] = int32_t(n.j);
             }
-            else if (push) { stack[top] = child; }
-            top += numPush;
-        }
+            else if (push) { dst[0] = child; }
+        };
+        walkBelowRoot(tree, stack, lane, errors, seed != 0, open, scan, still, place);
     }
     knnWriteRow(list, limit, q, k, out);
 }
@@ -492,7 +432,7 @@ int launchKnnOut(cstone_hip_ctx* ctx, const void* x, const void* y, const void* 
     cstone_hip::OctreeNsView<T> tree{childOffsets, internalToLeaf, layout, (const T*)centers, (const T*)sizes};
     hipLaunchKernelGGL((knnKernel<T, R, Out>), numQueries, 64, 0, ctx->stream, (const T*)x, (const T*)y, (const T*)z, first,
                        last, cstone_hip::makeDeviceBox<T>(box), tree, (const T*)qc, (const T*)rmax, qself, k,
-                       knnAbsMargin<T>(box), out, ctx->devScalars + 63);
+                       nodeAbsMargin<T>(box, 64), out, ctx->devScalars + 63);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return fail(ctx, CSTONE_E_HIP, "knn: %s", hipGetErrorString(e));
     return CSTONE_OK;
 }

@@ -3,11 +3,11 @@
 // include/cstone_hip.h, cstone_hip_knn.
 #pragma once
 
-#include <cmath>
 #include <cstddef>
 #include <cstdint>
 
 #include "cstone_hip.h"
+#include "node_margin.hpp" // the absolute term of the node test: nodeAbsMargin(box, 64)
 
 namespace cship
 {
@@ -25,17 +25,6 @@ inline const char* knnRefusal(int realBits, uint32_t k, uint32_t first, uint32_t
 
 //! list registers per lane for k: ceil(k / 64) rounded up to an instantiated count (1, 2, 4)
 inline int knnListRegisters(uint32_t k) { return k <= 64 ? 1 : k <= 128 ? 2 : 4; }
-
-//! the absolute term of the node test, 64 eps L with L the largest of |lo_a|, |hi_a| and len_a (derived in sphere.hip)
-template<class T>
-inline T knnAbsMargin(const cstone_box& b)
-{
-    double L = 0;
-    for (int a = 0; a < 3; ++a)
-        L = std::fmax(L, std::fmax(std::fmax(std::fabs(b.lim[2 * a]), std::fabs(b.lim[2 * a + 1])), b.lim[2 * a + 1] - b.lim[2 * a]));
-    const double eps = sizeof(T) == 4 ? 1.1920928955078125e-07 : 2.220446049250313e-16;
-    return T(64.0 * eps * L);
-}
 
 /*! How many queries one all_gather of cstone_hip_domain_mr_knn carries: every rank sends 16 k bytes per query and receives
  *  numRanks times that, so  floor(capBytes / (16 k numRanks))  queries keep the receive buffer under capBytes; at least 1

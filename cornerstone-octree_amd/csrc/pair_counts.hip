@@ -8,8 +8,8 @@
 // walk (sphere.hip) lets the pair test decide, but pays one traversal per query.  This one shares the traversal AND leaves
 // the decision to the pair test.
 //   box          the wave forms the exact bounding box of its targets by wave reductions (lanes past the end of the range
-//                repeat the wave's last target); centre and half size are rounded from it, see pairAbsMargin.  Where the
-//                64 targets are spread over far more than the bins reach, the wave walks once per aligned group of 32, 16,
+//                repeat the wave's last target); centre and half size are rounded from it, which the margin allows for.
+//                Where the 64 targets are spread over far more than the bins reach, the wave walks once per group of 32, 16,
 //                ... 1 lanes instead, each with its own box (the same butterfly gives the groups' bounds): the largest group
 //                size whose boxes all have a half extent of at most 2 e_NB.  Without this one wave of the outskirts of a
 //                Plummer sphere, whose box holds the core, tests every particle of the core for all its lanes.
@@ -34,14 +34,8 @@
 //                every sum is fixed by the octree, the ranges and this shape; no floating-point atomics anywhere, and no
 //                integer ones either (the sticky error word aside).
 //
-// The stack.  The batched walk is that of sphereProfilesKernel and so is the bound: call what one step pushes a batch (at
-// most 64 nodes) and label it with 1 + the lowest level among the nodes the step popped.  A step pops from the top: it
-// consumes whole batches and at most a part of one further batch B, and its own batch, put above what is left of B, carries
-// a label above B's.  So the labels of the live batches ascend strictly from the bottom of the stack to its top; they lie
-// in 1 .. 20 (a node of the deepest level, 21, is a leaf and has no children; the root is no batch), hence never more than
-// 1 + 20 * 64 entries, whatever the node test lets through -- also when it lets everything through (an open box with e_NB
-// beyond its diagonal).  PAIR_STACK = 64 * 21 covers that; an overflow would still be caught and ORs 4 into the sticky
-// error word like every walk here.
+// The walk, its stack and the stack's bound are those of wave_walk.hpp; the bound holds whatever the node test lets through,
+// also when it lets everything through (an open box with e_NB beyond its diagonal).
 //
 // LDS per wave: 256 NB (768 NB with weights) + 66 reals (e2) + 5 376 (stack): 21.5 KiB at NB = 64 without weights, 54 KiB
 // with them.
@@ -50,8 +44,10 @@
 
 #include "cstone_hip_device.hpp"
 #include "ctx.hpp"
+#include "node_margin.hpp"
 #include "pair_counts.hpp"
 #include "sphere.hpp"
+#include "wave_walk.hpp"
 
 namespace cship
 {
@@ -59,28 +55,19 @@ namespace cship
 namespace
 {
 
-static_assert(CSTONE_PAIR_MAX_BINS == CSTONE_SPHERE_MAX_BINS, "pairEdgesOk goes through sphereEdgesOk");
-
-constexpr int PAIR_STACK  = 64 * 21;
 constexpr int PAIR_E2_PAD = CSTONE_PAIR_MAX_BINS + 2; // e2[0 .. NB], padded to an even count: the stack stays 8-aligned
 //! partial rows of a call at most (workgroups of the walk); more only where a lane's 32-bit count could wrap otherwise
 constexpr uint32_t PAIR_ROWS = 8192;
 
 template<class T>
-struct PairEdges
-{
-    T e[CSTONE_PAIR_MAX_BINS + 1]; // T(edges[b]), converted on the host
-};
-
-template<class T>
 constexpr size_t pairLdsBytes(int nb, bool hasW)
 {
     return size_t(nb) * 64 * (sizeof(uint32_t) + (hasW ? sizeof(double) : 0)) + PAIR_E2_PAD * sizeof(T) +
-           PAIR_STACK * sizeof(int32_t);
+           WALK_STACK * sizeof(int32_t);
 }
 
-/*! The margin of the node test.  A node may be skipped only if NO particle p in it passes the pair test d2 < e2_NB of ANY
- *  of the wave's targets t.  Per axis a, with u = eps / 2 the unit roundoff of T and L the largest of |lo_a|, |hi_a| and
+/*! The margin of the node test, and why its absolute term is nodeAbsMargin(box, 256).  A node may be skipped only if NO
+ *  particle p in it passes the pair test d2 < e2_NB of ANY of the wave's targets t.  Per axis a, with u = eps / 2 the unit roundoff of T and L the largest of |lo_a|, |hi_a| and
  *  len_a over the axes:
  *
  *    In exact arithmetic the folded offset has the magnitude g(d) = distance of d to the nearest multiple of len, and g is
@@ -106,18 +93,9 @@ constexpr size_t pairLdsBytes(int nb, bool hasW)
  *    Hence:  skip iff  dist2_boxes > (e_NB * (1 + 16 eps) + 256 eps L)^2.
  *
  *  The relative term alone covers nothing when e_NB is a few ulps of the coordinates: tests/test_pair_counts.py (cell
- *  faces) counts the pairs a relative-only margin loses. */
-template<class T>
-T pairAbsMargin(const cstone_box& b)
-{
-    double L = 0;
-    for (int a = 0; a < 3; ++a)
-        L = std::fmax(L, std::fmax(std::fmax(std::fabs(b.lim[2 * a]), std::fabs(b.lim[2 * a + 1])), b.lim[2 * a + 1] - b.lim[2 * a]));
-    const double eps = sizeof(T) == 4 ? 1.1920928955078125e-07 : 2.220446049250313e-16;
-    return T(256.0 * eps * L);
-}
-
-/*! Sources: x, y, z, w over [first, last).  Targets: tx, ty, tz, tw over [tFirst, tLast) -- the same arrays for the auto
+ *  faces) counts the pairs a relative-only margin loses.
+ *
+ *  Sources: x, y, z, w over [first, last).  Targets: tx, ty, tz, tw over [tFirst, tLast) -- the same arrays for the auto
  *  counts (EXCL: a target is no partner of itself, BY INDEX), the sorted queries for the cross counts.  tw == nullptr with
  *  HAS_W: every target weighs 1. */
 template<class T, class W, bool HAS_W, bool EXCL>
@@ -126,7 +104,7 @@ __global__ __launch_bounds__(64) void pairCountsKernel(const T* __restrict__ x, 
                                                        const T* __restrict__ tx, const T* __restrict__ ty,
                                                        const T* __restrict__ tz, const W* __restrict__ tw, uint32_t tFirst,
                                                        uint32_t tLast, cstone_hip::DeviceBox<T> box,
-                                                       cstone_hip::OctreeNsView<T> tree, PairEdges<T> edges, int nb,
+                                                       cstone_hip::OctreeNsView<T> tree, WalkEdges<T> edges, int nb,
                                                        T absMargin, uint32_t numWaves,
                                                        unsigned long long* __restrict__ rowCounts,
                                                        double* __restrict__ rowSums, unsigned long long* __restrict__ rowTests,
@@ -150,7 +128,7 @@ __global__ __launch_bounds__(64) void pairCountsKernel(const T* __restrict__ x, 
     }
     __syncthreads();
 
-    // the node test (see pairAbsMargin).  !(>): a NaN anywhere opens the node, the pair test then decides
+    // the node test (its margin: above the kernel).  !(>): a NaN anywhere opens the node, the pair test then decides
     const T eps  = sizeof(T) == 4 ? T(1.1920928955078125e-07) : T(2.220446049250313e-16);
     const T thr  = edges.e[nb] * (T(1) + T(16) * eps) + absMargin;
     const T thr2 = thr * thr;
@@ -197,7 +175,7 @@ __global__ __launch_bounds__(64) void pairCountsKernel(const T* __restrict__ x, 
 
       for (uint32_t g0 = 0; g0 < nValid; g0 += gs)
       {
-        // centre and half size of the group's box, rounded from its exact bounds (see pairAbsMargin)
+        // centre and half size of the group's box, rounded from its exact bounds (the margin allows for that)
         using cstone_hip::detail::readLane;
         const T blx = readLane(gLox, g0), bly = readLane(gLoy, g0), blz = readLane(gLoz, g0);
         const T hsx = (readLane(gHix, g0) - blx) * T(0.5), hsy = (readLane(gHiy, g0) - bly) * T(0.5),
@@ -206,17 +184,7 @@ __global__ __launch_bounds__(64) void pairCountsKernel(const T* __restrict__ x, 
         const bool mine      = valid && lane >= g0 && lane < g0 + gs;
         const uint32_t nMine = min(gs, nValid - g0);
 
-        auto near = [&](int32_t n) -> bool
-        {
-            T dx = tree.centers[3 * n] - bcx, dy = tree.centers[3 * n + 1] - bcy, dz = tree.centers[3 * n + 2] - bcz;
-            dx = cstone_hip::detail::foldAxis<T>(dx, box.len[0], box.inv[0], px);
-            dy = cstone_hip::detail::foldAxis<T>(dy, box.len[1], box.inv[1], py);
-            dz = cstone_hip::detail::foldAxis<T>(dz, box.len[2], box.inv[2], pz);
-            dx = (fabs(dx) - tree.sizes[3 * n]) - hsx, dy = (fabs(dy) - tree.sizes[3 * n + 1]) - hsy,
-            dz = (fabs(dz) - tree.sizes[3 * n + 2]) - hsz;
-            dx = dx > T(0) ? dx : T(0), dy = dy > T(0) ? dy : T(0), dz = dz > T(0) ? dz : T(0);
-            return !(dx * dx + dy * dy + dz * dz > thr2);
-        };
+        auto near = [&](int32_t n) -> bool { return !(walkNodeDist2(tree, box, n, bcx, bcy, bcz, hsx, hsy, hsz) > thr2); };
         // particles [jb, je) (wave-uniform), clipped to the range: the pair test, the authority
         auto bin = [&](uint32_t jb, uint32_t je)
         {
@@ -260,84 +228,14 @@ __global__ __launch_bounds__(64) void pairCountsKernel(const T* __restrict__ x, 
             }
         };
 
-        if (!near(0)) continue;
-        int top = 0;
-        if (tree.childOffsets[0] == 0)
-        {
-            const int32_t leaf = tree.internalToLeaf[0];
-            bin(tree.layout[leaf], tree.layout[leaf + 1]);
-        }
-        else
-        {
-            if (lane == 0) stack[0] = 0;
-            top = 1;
-        }
-        while (top > 0)
-        {
-            const int take = min(top, 8);
-            const int slot = int(lane >> 3);
-            int32_t child  = 0;
-            bool go = false, isLeaf = false;
-            uint32_t jb = 0, je = 0;
-            if (slot < take)
-            {
-                const int32_t par = stack[top - 1 - slot]; // LDS accesses of one wave: in program order
-                child             = tree.childOffsets[par] + int32_t(lane & 7u);
-                go                = near(child);
-                if (go && tree.childOffsets[child] == 0)
-                {
-                    isLeaf             = true;
-                    const int32_t leaf = tree.internalToLeaf[child];
-                    jb = tree.layout[leaf], je = tree.layout[leaf + 1];
-                }
-            }
-            top -= take;
-            // the opened leaves in lane order; ranges that touch are read as one
-            uint64_t lm = __ballot(go && isLeaf);
-            uint32_t rb = 0, re = 0;
-            while (lm)
-            {
-                const int src = __ffsll((unsigned long long)lm) - 1;
-                lm &= lm - 1;
-                const uint32_t b = uint32_t(__builtin_amdgcn_readlane(int(jb), src));
-                const uint32_t e = uint32_t(__builtin_amdgcn_readlane(int(je), src));
-                if (b == re) { re = e; }
-                else
-                {
-                    if (re > rb) bin(rb, re);
-                    rb = b, re = e;
-                }
-            }
-            if (re > rb) bin(rb, re);
-
-            const bool push   = go && !isLeaf;
-            const uint64_t pm = __ballot(push);
-            const int numPush = __popcll(pm);
-            if (top + numPush > PAIR_STACK)
-            {
-                if (lane == 0) atomicOr(errors, 4);
-                break;
-            }
-            if (push) stack[top + __popcll(pm & ((1ull << lane) - 1ull))] = child;
-            top += numPush;
-        }
+        walkFromRoot(tree, stack, lane, errors, near, bin);
       }
     }
     __syncthreads();
 
-    unsigned long long myCount = 0;
-    double mySum               = 0.0;
-    for (int b = 0; b < nb; ++b)
-    {
-        unsigned long long c = cnt[b * 64 + lane];
-        double a             = HAS_W ? acc[b * 64 + lane] : 0.0;
-        for (int offset = 32; offset; offset >>= 1)
-        {
-            c += __shfl_xor(c, offset);
-            if (HAS_W) a += __shfl_xor(a, offset);
-        }
-        if (int(lane) == b) myCount = c, mySum = a;
-    }
+    unsigned long long myCount;
+    double mySum;
+    walkBinTotals<HAS_W>(cnt, acc, nb, lane, myCount, mySum);
     if (int(lane) < nb)
     {
         rowCounts[size_t(blockIdx.x) * nb + lane] = myCount;
@@ -465,7 +363,7 @@ int launchPairCounts(cstone_hip_ctx* ctx, const void* x, const void* y, const vo
                      uint32_t numRows, const PairRows& rows, uint64_t* counts, double* sums)
 {
     cstone_hip::OctreeNsView<T> tree{childOffsets, internalToLeaf, layout, (const T*)centers, (const T*)sizes};
-    PairEdges<T> edges;
+    WalkEdges<T> edges;
     std::memset(&edges, 0, sizeof edges);
     for (int b = 0; b <= nb; ++b)
         edges.e[b] = T(edgesHost[b]);
@@ -473,7 +371,7 @@ int launchPairCounts(cstone_hip_ctx* ctx, const void* x, const void* y, const vo
     const uint32_t numWaves = (tLast - tFirst + 63u) / 64u;
     hipLaunchKernelGGL((pairCountsKernel<T, W, HAS_W, EXCL>), numRows, 64, pairLdsBytes<T>(nb, HAS_W), ctx->stream, (const T*)x,
                        (const T*)y, (const T*)z, (const W*)w, first, last, (const T*)tx, (const T*)ty, (const T*)tz,
-                       (const W*)tw, tFirst, tLast, cstone_hip::makeDeviceBox<T>(box), tree, edges, nb, pairAbsMargin<T>(box),
+                       (const W*)tw, tFirst, tLast, cstone_hip::makeDeviceBox<T>(box), tree, edges, nb, nodeAbsMargin<T>(box, 256),
                        numWaves, rows.counts, rows.sums, rows.tests, ctx->devScalars + 63);
     hipLaunchKernelGGL(pairCountsFinishKernel, nb + 1, 256, 0, ctx->stream, rows.counts, HAS_W ? rows.sums : nullptr, rows.tests,
                        numRows, nb, reinterpret_cast<unsigned long long*>(counts), sums, rows.stats);

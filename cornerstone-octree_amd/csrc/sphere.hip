@@ -19,14 +19,7 @@
 //                commutative, so every lane holds the same bits); lane b keeps bin b and the row is written coalesced.
 // The order of every sum is fixed by the tree, the range and this shape; the launch shape is no argument of the call.
 //
-// The stack.  Popping 8 nodes and pushing up to 64 children is a depth-first walk in batches, and it needs more room than
-// the 160 entries of the one-node-at-a-time walks: a sphere that covers four full levels already has 176 entries pending.
-// Bound: call what one step pushes a batch (at most 64 nodes) and label it with 1 + the lowest level among the nodes the
-// step popped.  A step pops from the top: it consumes whole batches and at most a part of one further batch B, and its own
-// batch, put above what is left of B, carries a label above B's.  So the labels of the live batches ascend strictly from
-// the bottom of the stack to its top; they lie in 1 .. 20 (a node of the deepest level, 21, is a leaf and has no
-// children; the root is no batch), hence never more than 1 + 20 * 64 entries.  SPHERE_STACK = 64 * 21 covers that; an
-// overflow would still be caught and ORs 4 into the sticky error word like every walk here.
+// The walk, its stack and the stack's bound are those of wave_walk.hpp.
 //
 // LDS per wave: 768 * NB (accumulators) + 66 reals (e2) + 5 376 (stack): 6.7 KiB at NB = 1, 55 KiB at NB = 64.
 #include <cmath>
@@ -34,7 +27,9 @@
 
 #include "cstone_hip_device.hpp"
 #include "ctx.hpp"
+#include "node_margin.hpp"
 #include "sphere.hpp"
+#include "wave_walk.hpp"
 
 namespace cship
 {
@@ -42,14 +37,7 @@ namespace cship
 namespace
 {
 
-constexpr int SPHERE_STACK  = 64 * 21;
 constexpr int SPHERE_E2_PAD = CSTONE_SPHERE_MAX_BINS + 2; // e2[0 .. NB], padded to an even count: the stack stays 8-aligned
-
-template<class T>
-struct SphereEdges
-{
-    T e[CSTONE_SPHERE_MAX_BINS + 1]; // T(edges[b]), converted on the host
-};
 
 struct SphereEdgesD
 {
@@ -59,11 +47,11 @@ struct SphereEdgesD
 template<class T>
 constexpr size_t sphereLdsBytes(int nb)
 {
-    return size_t(nb) * 64 * (sizeof(double) + sizeof(uint32_t)) + SPHERE_E2_PAD * sizeof(T) + SPHERE_STACK * sizeof(int32_t);
+    return size_t(nb) * 64 * (sizeof(double) + sizeof(uint32_t)) + SPHERE_E2_PAD * sizeof(T) + WALK_STACK * sizeof(int32_t);
 }
 
-/*! The margin of the node test.  A node may be skipped only if NO particle in it passes the particle test, d2 < e2_NB.
- *  Per axis a, with u = eps / 2 the unit roundoff of T and L the largest of |lo_a|, |hi_a| and len_a over the axes:
+/*! The margin of the node test, and why its absolute term is nodeAbsMargin(box, 64).  A node may be skipped only if NO
+ *  particle in it passes the particle test, d2 < e2_NB.  Per axis a, with u = eps / 2 the unit roundoff of T and L the largest of |lo_a|, |hi_a| and len_a over the axes:
  *
  *    In exact arithmetic the folded offset has the magnitude g(d) = distance of d to the nearest multiple of len, and g
  *    is 1-Lipschitz, so for a particle p inside the node's box  g(p - c_q) >= g(c_node - c_q) - size  -- whichever images
@@ -84,22 +72,12 @@ constexpr size_t sphereLdsBytes(int nb)
  *  The relative term alone covers nothing when e_NB is a few ulps of the coordinates: the cancellation in
  *  |c_node - c_q| - size is absolute.  tests/test_sphere_profiles.py (cell faces) has queries that a relative-only margin
  *  loses in f32.  The bound takes |c_q - r| <= 2 len on a periodic axis (centres in or near the box). */
-template<class T>
-T sphereAbsMargin(const cstone_box& b)
-{
-    double L = 0;
-    for (int a = 0; a < 3; ++a)
-        L = std::fmax(L, std::fmax(std::fmax(std::fabs(b.lim[2 * a]), std::fabs(b.lim[2 * a + 1])), b.lim[2 * a + 1] - b.lim[2 * a]));
-    const double eps = sizeof(T) == 4 ? 1.1920928955078125e-07 : 2.220446049250313e-16;
-    return T(64.0 * eps * L);
-}
-
 template<class T, class W, bool HAS_W>
 __global__ __launch_bounds__(64) void sphereProfilesKernel(const T* __restrict__ x, const T* __restrict__ y,
                                                            const T* __restrict__ z, const W* __restrict__ w, uint32_t first,
                                                            uint32_t last, cstone_hip::DeviceBox<T> box,
                                                            cstone_hip::OctreeNsView<T> tree, const T* __restrict__ qc,
-                                                           const T* __restrict__ qs, SphereEdges<T> edges, int nb,
+                                                           const T* __restrict__ qs, WalkEdges<T> edges, int nb,
                                                            T absMargin, unsigned long long* __restrict__ counts,
                                                            double* __restrict__ sums, uint32_t* __restrict__ flags,
                                                            int* __restrict__ errors)
@@ -133,20 +111,11 @@ __global__ __launch_bounds__(64) void sphereProfilesKernel(const T* __restrict__
     const bool live = !wide && eN > T(0) && last > first;
     __syncthreads();
 
-    // the node test (see sphereAbsMargin).  !(>): a NaN anywhere opens the node, the particle test then decides
+    // the node test (its margin: above the kernel).  !(>): a NaN anywhere opens the node, the particle test then decides
     const T eps  = sizeof(T) == 4 ? T(1.1920928955078125e-07) : T(2.220446049250313e-16);
     const T thr  = eN * (T(1) + T(16) * eps) + absMargin;
     const T thr2 = thr * thr;
-    auto near = [&](int32_t n) -> bool
-    {
-        T dx = tree.centers[3 * n] - cx, dy = tree.centers[3 * n + 1] - cy, dz = tree.centers[3 * n + 2] - cz;
-        dx = cstone_hip::detail::foldAxis<T>(dx, box.len[0], box.inv[0], px);
-        dy = cstone_hip::detail::foldAxis<T>(dy, box.len[1], box.inv[1], py);
-        dz = cstone_hip::detail::foldAxis<T>(dz, box.len[2], box.inv[2], pz);
-        dx = fabs(dx) - tree.sizes[3 * n], dy = fabs(dy) - tree.sizes[3 * n + 1], dz = fabs(dz) - tree.sizes[3 * n + 2];
-        dx = dx > T(0) ? dx : T(0), dy = dy > T(0) ? dy : T(0), dz = dz > T(0) ? dz : T(0);
-        return !(dx * dx + dy * dy + dz * dz > thr2);
-    };
+    auto near = [&](int32_t n) -> bool { return !(walkNodeDist2(tree, box, n, cx, cy, cz) > thr2); };
     // particles [jb, je) (wave-uniform), clipped to the range: the particle test, the authority
     auto bin = [&](uint32_t jb, uint32_t je)
     {
@@ -179,84 +148,12 @@ __global__ __launch_bounds__(64) void sphereProfilesKernel(const T* __restrict__
         }
     };
 
-    if (live && near(0))
-    {
-        int top = 0;
-        if (tree.childOffsets[0] == 0)
-        {
-            const int32_t leaf = tree.internalToLeaf[0];
-            bin(tree.layout[leaf], tree.layout[leaf + 1]);
-        }
-        else
-        {
-            if (lane == 0) stack[0] = 0;
-            top = 1;
-        }
-        while (top > 0)
-        {
-            const int take = min(top, 8);
-            const int slot = int(lane >> 3);
-            int32_t child  = 0;
-            bool go = false, isLeaf = false;
-            uint32_t jb = 0, je = 0;
-            if (slot < take)
-            {
-                const int32_t par = stack[top - 1 - slot]; // LDS accesses of one wave: in program order
-                child             = tree.childOffsets[par] + int32_t(lane & 7u);
-                go                = near(child);
-                if (go && tree.childOffsets[child] == 0)
-                {
-                    isLeaf             = true;
-                    const int32_t leaf = tree.internalToLeaf[child];
-                    jb = tree.layout[leaf], je = tree.layout[leaf + 1];
-                }
-            }
-            top -= take;
-            // the opened leaves in lane order; ranges that touch are read as one
-            uint64_t lm = __ballot(go && isLeaf);
-            uint32_t rb = 0, re = 0;
-            while (lm)
-            {
-                const int src = __ffsll((unsigned long long)lm) - 1;
-                lm &= lm - 1;
-                const uint32_t b = uint32_t(__builtin_amdgcn_readlane(int(jb), src));
-                const uint32_t e = uint32_t(__builtin_amdgcn_readlane(int(je), src));
-                if (b == re) { re = e; }
-                else
-                {
-                    if (re > rb) bin(rb, re);
-                    rb = b, re = e;
-                }
-            }
-            if (re > rb) bin(rb, re);
-
-            const bool push   = go && !isLeaf;
-            const uint64_t pm = __ballot(push);
-            const int numPush = __popcll(pm);
-            if (top + numPush > SPHERE_STACK)
-            {
-                if (lane == 0) atomicOr(errors, 4);
-                break;
-            }
-            if (push) stack[top + __popcll(pm & ((1ull << lane) - 1ull))] = child;
-            top += numPush;
-        }
-    }
+    if (live) walkFromRoot(tree, stack, lane, errors, near, bin);
     __syncthreads();
 
-    unsigned long long myCount = 0;
-    double mySum               = 0.0;
-    for (int b = 0; b < nb; ++b)
-    {
-        unsigned long long c = cnt[b * 64 + lane];
-        double a             = acc[b * 64 + lane];
-        for (int offset = 32; offset; offset >>= 1)
-        {
-            c += __shfl_xor(c, offset);
-            if (HAS_W) a += __shfl_xor(a, offset);
-        }
-        if (int(lane) == b) myCount = c, mySum = a;
-    }
+    unsigned long long myCount;
+    double mySum;
+    walkBinTotals<HAS_W>(cnt, acc, nb, lane, myCount, mySum);
     if (int(lane) < nb)
     {
         counts[q * nb + lane] = myCount;
@@ -337,14 +234,14 @@ int launchProfiles(cstone_hip_ctx* ctx, const void* x, const void* y, const void
                    uint32_t numQueries, const double* edgesHost, int nb, uint64_t* counts, double* sums, uint32_t* flags)
 {
     cstone_hip::OctreeNsView<T> tree{childOffsets, internalToLeaf, layout, (const T*)centers, (const T*)sizes};
-    SphereEdges<T> edges;
+    WalkEdges<T> edges;
     std::memset(&edges, 0, sizeof edges);
     for (int b = 0; b <= nb; ++b)
         edges.e[b] = T(edgesHost[b]);
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t));
     hipLaunchKernelGGL((sphereProfilesKernel<T, W, HAS_W>), numQueries, 64, sphereLdsBytes<T>(nb), ctx->stream, (const T*)x,
                        (const T*)y, (const T*)z, (const W*)w, first, last, cstone_hip::makeDeviceBox<T>(box), tree,
-                       (const T*)qc, (const T*)qs, edges, nb, sphereAbsMargin<T>(box),
+                       (const T*)qc, (const T*)qs, edges, nb, nodeAbsMargin<T>(box, 64),
                        reinterpret_cast<unsigned long long*>(counts), sums, flags, ctx->devScalars + 63);
     if (hipError_t e = hipGetLastError(); e != hipSuccess)
         return fail(ctx, CSTONE_E_HIP, "sphere_profiles: %s", hipGetErrorString(e));

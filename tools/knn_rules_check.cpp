@@ -1,6 +1,6 @@
 // The host-only rules of the k-nearest-neighbour calls (csrc/knn.hpp: the refusals of cstone_hip_knn, the list registers
-// per k, the chunk rule of cstone_hip_domain_mr_knn, the absolute margin of the node test) called from a plain host
-// program, so that they can run under the sanitizers without a GPU:
+// per k, the chunk rule of cstone_hip_domain_mr_knn) and the absolute margin of the node tests (csrc/node_margin.hpp)
+// called from a plain host program, so that they can run under the sanitizers without a GPU:
 //   g++ -std=c++20 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I include -I cornerstone-octree_amd/csrc \
 //       tools/knn_rules_check.cpp -o knn_rules_check && ./knn_rules_check
 // Exits non-zero at the first rule that does not hold.
@@ -62,8 +62,11 @@ int main()
     cstone_box box{};
     const double lim[6] = {-1.3, 2.1, 0.2, 0.9, -5, 7};
     std::memcpy(box.lim, lim, sizeof lim);
-    expect(knnAbsMargin<float>(box) == float(64.0 * 1.1920928955078125e-07 * 12.0), "margin f32: L = the z length");
-    expect(knnAbsMargin<double>(box) == 64.0 * 2.220446049250313e-16 * 12.0, "margin f64");
+    expect(nodeAbsMargin<float>(box, 64) == float(64.0 * 1.1920928955078125e-07 * 12.0), "margin f32: L = the z length");
+    expect(nodeAbsMargin<double>(box, 64) == 64.0 * 2.220446049250313e-16 * 12.0, "margin f64");
+    expect(nodeAbsMargin<float>(box, 256) == float(256.0 * 1.1920928955078125e-07 * 12.0) &&
+               nodeAbsMargin<double>(box, 256) == 256.0 * 2.220446049250313e-16 * 12.0,
+           "margin of the pair counts: the factor 256");
 
     std::printf("knn rules: %s\n", failures ? "FAILED" : "ok");
     return failures ? 1 : 0;
