@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "device_keys.hpp"
+#include "leaf_steps.hpp"
 #include "resort.hpp"
 #include "scan.hpp"
 #include "wave_lanes.hpp"
@@ -616,10 +617,13 @@ __global__ __launch_bounds__(256) void leafSortKernel(const K* __restrict__ keys
 // (equal keys among them; about one leaf in 10^4) send the leaf to the exact path: every element counts the elements
 // in front of it by (key, old index) proper.  A leaf nothing arrived in and whose remaining keys are still in order goes
 // out as it came in, without the network.
-// The loop over the wave's leaves is ROLLED (see below), and the wave number is deliberately NOT declared wave-uniform:
-// with readfirstlane on it the leaf's table entries travel through scalar registers and every leaf starts with a chain of
-// LDS read -> s_waitcnt -> v_readfirstlane -> scalar ALU before the first load can be issued (0.74 / 0.83 ms against
-// 0.66 / 0.75 ms, 1 % movers / everything drifting).
+// The loop over the wave's leaves is ROLLED (see below).  What decides a step -- which leaves it takes, how many lanes
+// each gets, whether there is anything to sort -- depends on the leaves' slot counts only and is the same for all lanes:
+// it is worked out once per tile (leaf_steps.hpp), held one word per leaf in a lane register and taken into scalar
+// registers with v_readlane, so the loop counts and branches in scalars.  (Round 3 declared the wave number uniform
+// and read the leaf's table entries through readfirstlane instead: every leaf then started with a chain of LDS read ->
+// s_waitcnt -> v_readfirstlane -> scalar ALU before its first load could be issued, 0.74 / 0.83 ms against 0.66 /
+// 0.75 ms, 1 % movers / everything drifting.  The table entries themselves stay in vector registers here.)
 // ---------------------------------------------------------------------------------------------------------------------
 // ---- cross-lane partners on the VALU (no LDS pipe): DPP within a row of 16 lanes, v_permlane16/32_swap (gfx950) across
 //      rows; lane mappings verified with tools/dpp_probe.hip on the hardware.  dppMov, dppAll and laneXor<X> live in
@@ -820,45 +824,48 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
     constexpr K HOLE = ~K(0);
     using Real       = typename F::Real;
     using Val        = LeafVal<Real>;
-    __shared__ uint32_t posK[G + 1], inK[G + 1], outK[G + 1];
-    __shared__ K loK[G + 1];
+    //! what a step reads of a leaf, written once per tile: one record, two or three wide LDS reads
+    struct alignas(16) LeafRec
+    {
+        uint32_t pk, nOld, ik, nInc, ok, nNew, cut; // old slots, arrivals (in the bins), new content; shift of the digest
+        K lo;
+    };
+    __shared__ LeafRec recK[G + 1];    // [G]: no leaf -- nothing old, nothing arriving, nothing to store
     __shared__ uint32_t slotsK[G + 4]; // old slots + arrivals of every leaf, zeros behind the last one
-    __shared__ uint8_t cutK[G];
     __shared__ uint16_t sPlace[4][256];
 
     RESORT_TRACE(0)
     const uint32_t j0 = blockIdx.x * uint32_t(G);
     const uint32_t nl = min(uint32_t(G), J - j0);
     const uint32_t t  = threadIdx.x;
-    if (t <= nl)
-    {
-        posK[t] = leafPos[j0 + t];
-        inK[t]  = inOffset[j0 + t];
-        outK[t] = layoutNew[j0 + t];
-        loK[t]  = leafLo[j0 + t];
-    }
-    __syncthreads();
-    if (t < uint32_t(G) + 4u) slotsK[t] = t < nl ? (posK[t + 1] - posK[t]) + (inK[t + 1] - inK[t]) : 0u;
+    uint32_t slots = 0, nOld = 0, nNew = 0;
     if (t < nl)
     {
+        LeafRec r;
+        r.pk = leafPos[j0 + t], r.nOld = nOld = leafPos[j0 + t + 1] - r.pk;
+        r.ik = inOffset[j0 + t], r.nInc = inOffset[j0 + t + 1] - r.ik;
+        r.ok = layoutNew[j0 + t], r.nNew = nNew = layoutNew[j0 + t + 1] - r.ok;
+        r.lo = leafLo[j0 + t];
         // how far a leaf's keys are shifted for the 24 leading bits of the digest: once per leaf here, not once per step
-        const K span   = loK[t + 1] - loK[t] - 1;
+        const K span   = leafLo[j0 + t + 1] - r.lo - 1;
         const int bits = span ? int(8 * sizeof(K)) - clzKey(span) : 0;
-        cutK[t]        = uint8_t(bits > 24 ? bits - 24 : 0);
+        r.cut          = uint32_t(bits > 24 ? bits - 24 : 0);
+        recK[t]        = r;
+        slots          = r.nOld + r.nInc;
     }
-    const uint32_t p0 = posK[0], p1 = posK[nl], in0 = inK[0], in1 = inK[nl];
+    else if (t == uint32_t(G)) { recK[G] = LeafRec{0, 0, 0, 0, 0, 0, 0, 0}; }
+    if (t < uint32_t(G) + 4u) slotsK[t] = slots;
     if (!allTiles)
     {
         // the quiet instantiation of leafSortKernel takes the tiles in which nothing moved (same vote as there)
-        const uint32_t nOldAll = p1 - p0;
-        bool changed           = in1 != in0 || alwaysCount;
-        if (t < nl) changed = changed || (outK[t + 1] - outK[t]) != (posK[t + 1] - posK[t]);
-        const bool quiet = !__syncthreads_or(changed) && nOldAll <= RESORT_QUIET_SLOTS;
+        const uint32_t nOldAll = leafPos[j0 + nl] - leafPos[j0];
+        const bool changed     = inOffset[j0 + nl] != inOffset[j0] || alwaysCount || nNew != nOld;
+        const bool quiet       = !__syncthreads_or(changed) && nOldAll <= RESORT_QUIET_SLOTS;
         if (quiet) return;
     }
-    __syncthreads(); // (slotsK, cutK)
+    __syncthreads(); // (recK, slotsK)
     const unsigned lane = t & 63u;
-    const unsigned wave = t >> 6;
+    const unsigned wave = __builtin_amdgcn_readfirstlane(t >> 6); // (once per tile: the loops below count in scalars)
 
     //! what the loop needs to know about leaf k
     struct Leaf
@@ -869,22 +876,26 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
     };
     auto leafOf = [&](uint32_t k)
     {
+        const LeafRec r = recK[k];
         Leaf f;
-        f.pk = posK[k], f.nOld = posK[k + 1] - f.pk;
-        f.ik = inK[k], f.nInc = inK[k + 1] - f.ik;
-        f.ok = outK[k], f.nNew = outK[k + 1] - f.ok;
-        f.slots = f.nOld + f.nInc;
-        f.lo    = loK[k];
-        f.cut   = cutK[k];
+        f.pk = r.pk, f.nOld = r.nOld, f.ik = r.ik, f.nInc = r.nInc, f.ok = r.ok, f.nNew = r.nNew;
+        f.slots = r.nOld + r.nInc;
+        f.lo    = r.lo;
+        f.cut   = r.cut;
         f.k     = k;
         return f;
     };
-    // slot s of a leaf: an old position or an arrival (key and old position; requested one wave step ahead)
+    // slot s of a leaf: an old position or an arrival (key and old position; requested one wave step ahead).  Without a
+    // branch: one address per array, chosen between the old slot and the bin entry, and one load under the lane's
+    // condition; a lane without a leaf (recK[G]) loads nothing
     auto loadSlot = [&](const Leaf& f, uint32_t s, K& key, uint32_t& idx)
     {
-        key = HOLE, idx = 0;
-        if (s < f.nOld) key = keysIn[f.pk + s], idx = f.pk + s;
-        else if (s < f.slots) key = binKeys[f.ik + (s - f.nOld)], idx = binIdx[f.ik + (s - f.nOld)];
+        const bool old = s < f.nOld, have = s < f.slots;
+        const uint32_t at = old ? f.pk + s : f.ik + (s - f.nOld);
+        const K* src      = old ? keysIn : binKeys;
+        key = HOLE, idx = old ? at : 0u;
+        if (have) key = src[at];
+        if (have && !old) idx = binIdx[at];
     };
     // x, y, z, h of the particle that sat at old position idx.  They are requested only once the leaf is ordered, right
     // in front of the stores: the values then live in registers for a moment instead of across the network (with them
@@ -1014,30 +1025,38 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
         // hundred instructions and stays in the instruction cache; unrolled over the wave's 16 leaves the kernel was
         // 24-41 thousand instructions (190-330 KB of code streaming through the instruction cache) and took 0.7-0.9 ms
         // whatever the network cost.  The key of the NEXT leaf is requested before the current one is sorted.
+        // What kind of step a leaf takes follows from its slots: lane l holds those of the wave's l-th leaf, and the loop
+        // takes them from there into a scalar (v_readlane), so that it counts and branches in scalars without waiting
+        // for the leaf's record in front of every branch.
         if (wave >= nl) return;
-        Leaf cur = leafOf(wave);
-        K keyN        = HOLE;
-        uint32_t idxN = 0;
-        if (cur.slots <= 64) loadSlot(cur, lane, keyN, idxN);
+        const uint32_t numSteps = (nl - wave + 3u) / 4u; // (at most G / 4 = 16)
+        const uint32_t slotsOf  = lane < numSteps ? slotsK[wave + 4u * lane] : 0u;
+        Leaf cur        = leafOf(wave);
+        uint32_t slotsN = __builtin_amdgcn_readlane(slotsOf, 0);
+        K keyN          = HOLE;
+        uint32_t idxN   = 0;
+        if (slotsN <= 64) loadSlot(cur, lane, keyN, idxN);
     #pragma unroll 1
-        for (uint32_t k = wave; k < nl; k += 4)
+        for (uint32_t s = 0; s < numSteps; ++s)
         {
-            const Leaf f     = cur;
-            K key1[1]        = {keyN};
-            uint32_t idx1[1] = {idxN};
+            const Leaf f         = cur;
+            const uint32_t slots = slotsN;
+            K key1[1]            = {keyN};
+            uint32_t idx1[1]     = {idxN};
             keyN = HOLE, idxN = 0;
-            if (k + 4 < nl)
+            if (s + 1 < numSteps)
             {
-                cur = leafOf(k + 4);
-                if (cur.slots <= 64) loadSlot(cur, lane, keyN, idxN);
+                cur    = leafOf(wave + 4u * (s + 1));
+                slotsN = __builtin_amdgcn_readlane(slotsOf, s + 1);
+                if (slotsN <= 64) loadSlot(cur, lane, keyN, idxN);
             }
-            if (f.slots == 0)
+            if (slots == 0)
             {
                 if constexpr (F::on)
                     if (lane == 0) fl.hmax[j0 + f.k] = 0;
                 continue;
             }
-            if (f.slots <= 64)
+            if (slots <= 64)
             {
                 // nothing arrived and what stayed is still in order (a departure leaves the largest key behind, so only
                 // departures from the end of the leaf pass): the content goes out as it came in
@@ -1058,7 +1077,7 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
                 pinNext(keyN, idxN);
                 if (!finishLeaf(f, std::integral_constant<int, 1>{}, key1, idx1, d)) exactLeaf(f, 1, key1, idx1, true);
             }
-            else if (f.slots <= 128) { bigLeaf(f, std::integral_constant<int, 2>{}); }
+            else if (slots <= 128) { bigLeaf(f, std::integral_constant<int, 2>{}); }
             else { bigLeaf(f, std::integral_constant<int, 4>{}); }
         }
         return;
@@ -1083,67 +1102,52 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
         const uint32_t per    = (nl + 3u) / 4u;
         const uint32_t kBegin = min(nl, wave * per), kEnd = min(nl, kBegin + per);
         if (kBegin >= kEnd) return;
-        // log2 of the segment size in lanes for the step that starts at leaf q; 6: one leaf, more than 64 slots
-        auto segBits = [&](uint32_t q) -> unsigned
+        const uint32_t n = kEnd - kBegin; // leaves of this wave's quarter: 1 ... G / 4 = 16
+        // The step plan (leaf_steps.hpp), once per tile: lane l holds the step that starts at leaf l of the quarter.  The
+        // loop takes the word of its step into a scalar (v_readlane) and the next step starts behind the leaves this one
+        // consumes, so everything that decides a step -- its first leaf, the segment size, the kind -- lives in scalar
+        // registers, and no LDS read stands in front of a branch.
+        uint32_t stepOf = 0;
+        if (lane < n)
         {
-            const uint32_t s0 = slotsK[q];
-            const uint32_t s1 = q + 1 < kEnd ? slotsK[q + 1] : 0u;
-            const uint32_t s2 = q + 2 < kEnd ? slotsK[q + 2] : 0u;
-            const uint32_t s3 = q + 3 < kEnd ? slotsK[q + 3] : 0u;
-            if (s0 > 64u) return 6u;
-            const uint32_t m2 = max(s0, s1), m4 = max(m2, max(s2, s3));
-            // (a second leaf with more than 64 slots waits for its own step: the segment next to the first stays empty)
-            return m4 <= 32u ? 4u : 5u;
-        };
-        auto leafAt2 = [&](uint32_t q, unsigned bits, uint32_t secondSlots)
-        {
-            const uint32_t seg = bits == 6 ? 0u : (lane >> bits);
-            const uint32_t kk  = q + seg;
-            bool mine          = kk < kEnd;
-            if (bits == 5 && seg == 1 && secondSlots > 64u) mine = false;
-            Leaf f = leafOf(mine ? kk : q);
-            if (!mine) f.nOld = f.nInc = f.nNew = f.slots = 0, f.k = ~0u;
-            return f;
-        };
-        //! leaves the step at q with `bits` consumes
-        auto stepLeaves = [&](uint32_t q, unsigned bits) -> uint32_t
-        {
-            if (bits == 6) return 1u;
-            if (bits == 4) return 4u;
-            return (q + 1 < kEnd && slotsK[q + 1] > 64u) ? 1u : 2u;
-        };
-        uint32_t k    = kBegin;
-        unsigned bits = segBits(k);
-        Leaf cur      = leafAt2(k, bits, k + 1 < kEnd ? slotsK[k + 1] : 0u);
-        K keyN[2]        = {HOLE, HOLE};
-        uint32_t idxN[2] = {0, 0};
-        if (bits != 6)
-        {
-            const uint32_t sl = lane & ((1u << bits) - 1u);
-            loadSlot(cur, 2 * sl, keyN[0], idxN[0]);
-            loadSlot(cur, 2 * sl + 1, keyN[1], idxN[1]);
+            const uint32_t* s = slotsK + kBegin + lane;
+            stepOf            = leafStepAt(lane, n - lane, s[0], s[1], s[2], s[3]);
         }
-#pragma unroll 1
-        while (k < kEnd)
+        // the leaf of this lane in the step `word` (none: the zero record recK[G], so is every lane with on == false or in a
+        // step of one long leaf, which bigLeaf loads itself) and the request for the lane's two slots
+        auto requestStep = [&](uint32_t word, bool on, Leaf& f, K (&key)[2], uint32_t (&idx)[2])
         {
+            const uint32_t bits = leafStepBits(word);
+            const uint32_t seg  = lane >> bits;
+            const bool mine     = on && bits != 6u && seg < leafStepLeaves(word);
+            const uint32_t kk   = kBegin + leafStepFirst(word) + seg;
+            f                   = leafOf(mine ? kk : uint32_t(G));
+            f.k                 = mine ? kk : ~0u;
+            const uint32_t sl   = lane & ((1u << bits) - 1u);
+            loadSlot(f, 2 * sl, key[0], idx[0]);
+            loadSlot(f, 2 * sl + 1, key[1], idx[1]);
+        };
+        uint32_t q     = 0; // leaves of the quarter the steps so far have consumed
+        uint32_t wordN = __builtin_amdgcn_readlane(stepOf, 0);
+        bool more      = true;
+        Leaf cur;
+        K keyN[2];
+        uint32_t idxN[2];
+        requestStep(wordN, true, cur, keyN, idxN);
+        // (a counted loop: a step consumes at least one leaf, so n steps are enough whatever the plan says)
+#pragma unroll 1
+        for (uint32_t step = 0; step < n && more; ++step)
+        {
+            const uint32_t word   = wordN;
             const Leaf f          = cur;
-            const unsigned b      = bits;
+            const unsigned b      = leafStepBits(word);
             const K key[2]        = {keyN[0], keyN[1]};
             const uint32_t idx[2] = {idxN[0], idxN[1]};
             const uint32_t sl     = lane & ((1u << (b == 6 ? 5u : b)) - 1u);
-            k += stepLeaves(k, b);
-            keyN[0] = keyN[1] = HOLE, idxN[0] = idxN[1] = 0;
-            if (k < kEnd)
-            {
-                bits = segBits(k);
-                cur  = leafAt2(k, bits, k + 1 < kEnd ? slotsK[k + 1] : 0u);
-                if (bits != 6)
-                {
-                    const uint32_t sn = lane & ((1u << bits) - 1u);
-                    loadSlot(cur, 2 * sn, keyN[0], idxN[0]);
-                    loadSlot(cur, 2 * sn + 1, keyN[1], idxN[1]);
-                }
-            }
+            q += leafStepLeaves(word);
+            more  = q < n;
+            wordN = __builtin_amdgcn_readlane(stepOf, more ? q : 0u);
+            requestStep(wordN, more, cur, keyN, idxN);
 #ifdef CSTONE_RESORT_TRACE
             ++trSteps;
             WAVE_TRACE(trIssue)
@@ -1152,8 +1156,9 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
 #endif
             if (b == 6)
             {
-                if (f.slots <= 128) { bigLeaf(f, std::integral_constant<int, 2>{}); }
-                else { bigLeaf(f, std::integral_constant<int, 4>{}); }
+                const Leaf g = leafOf(kBegin + leafStepFirst(word));
+                if (!leafStepWide(word)) { bigLeaf(g, std::integral_constant<int, 2>{}); }
+                else { bigLeaf(g, std::integral_constant<int, 4>{}); }
                 continue;
             }
             // x, y, z, h of this lane's two elements, and the max h of every leaf of the step (a segment of 16 or 32 lanes
@@ -1173,7 +1178,7 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
                     else reportHmax(std::integral_constant<int, 4>{}, hm, writer, f.k);
                 }
             };
-            if (!__any(f.slots != 0))
+            if (leafStepEmpty(word))
             {
                 stepFields();
                 continue;
