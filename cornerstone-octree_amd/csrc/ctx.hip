@@ -269,7 +269,6 @@ int cstone_hip_ctx_destroy(cstone_hip_ctx* ctx)
         (void)hipEventDestroy(ctx->evTreeJoin);
         (void)hipStreamDestroy(ctx->tree);
     }
-    if (ctx->evReadBack) (void)hipEventDestroy(ctx->evReadBack);
     if (ctx->arena) (void)hipFree(ctx->arena);
     if (ctx->sideArena) (void)hipFree(ctx->sideArena);
     if (ctx->devScalars) (void)hipFree(ctx->devScalars);

@@ -55,9 +55,6 @@ struct cstone_hip_ctx
     hipStream_t tree       = nullptr;
     hipEvent_t evTreeFork  = nullptr;
     hipEvent_t evTreeJoin  = nullptr;
-    // behind a read-back on `stream` that the host waits for while later work of the stream runs (Domain::sync; made
-    // where it is first used)
-    hipEvent_t evReadBack  = nullptr;
 
     // -1 unknown, else result of the one-time LDS atomic ordering probe of the radix sort (sort.hip)
     int ldsOrderOk = -1;

@@ -152,7 +152,6 @@ struct DomainBase
                                 const void* queryW, uint32_t numQueries, const double* edgesHost, int numBins,
                                 uint64_t* counts, double* sums, uint64_t* statsHost) = 0;
     virtual void stats(cstone_hip_domain_stats* out)     = 0;
-    virtual void leafTableStats(uint32_t* used, uint32_t* rejected) = 0;
 };
 
 template<class K, class T>
@@ -176,14 +175,11 @@ public:
     int sync(void** keysPP, void** xPP, void** yPP, void** zPP, void** hPP, size_t n, void** scratchAll, int numScratch,
              void** props, const int* propBytes, int numProps) override
     {
-        if (n == 0 || (!firstCall_ && n != bufSize_)) earlyTableStale_ = true;
         if (n == 0) return fail(ctx_, CSTONE_E_ARG, "domain_sync: no particles");
         if (!firstCall_ && n != bufSize_)
             return fail(ctx_, CSTONE_E_ARG, "Domain sync: input array sizes are inconsistent (%zu != %u)", n, bufSize_);
         SyncState s{xPP, yPP, zPP, hPP, static_cast<K*>(*keysPP), n, scratchAll, numScratch, props, propBytes, numProps};
         const int rc = runStages(s);
-        // (a leaf table queued for the next sync is not trusted behind a sync that failed, whatever it failed at)
-        if (rc != CSTONE_OK) earlyTableStale_ = true;
         // a sync that failed behind a fork onto the tree stream joins it: nothing of this sync is in flight afterwards
         if (rc != CSTONE_OK && treeInFlight_)
         {
@@ -444,11 +440,6 @@ public:
         out->full_sort_fallbacks = uint32_t(fullSortFallbacks_);
         out->last_movers         = lastMovers_;
     }
-    void leafTableStats(uint32_t* used, uint32_t* rejected) override
-    {
-        *used     = earlyTablesUsed_;
-        *rejected = earlyTablesRejected_;
-    }
 
     float haloSearchExt_ = 1.0f;
 
@@ -479,16 +470,13 @@ private:
         size_t sortTmpBytes = 0;
         bool sorted         = false; // the re-sort has put keys and order_ into their final order
         uint32_t resortMarkers = 0;  // particles with the remove marker, as the re-sort counted them
-        bool fieldsMoved    = false; // x, y, z, h are in their new order already (and radii follow from hmax)
         bool noOverlap      = false; // CSTONE_NO_GATHER_OVERLAP
         bool xyzForked = false, xyzJoined = false; // the gather of x, y, z on the second stream
         bool noHoist        = false; // CSTONE_NO_TREE_HOIST
-        bool opsOnTree      = false; // focusOps of this sync was queued on the tree stream ...
-        bool opsTaken       = false; // ... and the host has read what it found:
+        // what the host has read of the node ops it queued on the tree stream (takeFocusOps):
         int converged       = 0;     //     every node op is "keep"
         NodeIdx newL        = 0;     //     leaves of the rebalanced tree
         bool treeDone       = false; // the focus tree, its links and its counts are those of this sync
-        bool hoistLate      = false; // CSTONE_TREE_HOIST_LATE
         bool rebuilt        = false; // focusRebuild is done or on its way on the tree stream: focusCounts is what is left
         uint32_t numAssigned = 0;    // particles without the remove marker
     };
@@ -568,20 +556,19 @@ private:
         return CSTONE_OK;
     }
 
-    //! x, y, z change places with the first three scratch arrays (and h with the fourth)
-    void swapFieldsWithScratch(SyncState& s, bool withH)
+    //! x, y, z change places with the first three scratch arrays
+    void swapFieldsWithScratch(SyncState& s)
     {
         std::swap(*s.xPP, s.scratch[0]);
         std::swap(*s.yPP, s.scratch[1]);
         std::swap(*s.zPP, s.scratch[2]);
-        if (withH) std::swap(*s.hPP, s.scratch[3]);
     }
 
     //! the gather of x, y, z for the first `count` entries of order_ starts on the second stream (once per sync, and only
     //! with three scratch arrays); the caller's pointers name the new arrays from here on
     int forkXyzGather(SyncState& s, size_t count)
     {
-        if (s.fieldsMoved || s.numScratch < 3 || s.noOverlap || s.xyzForked || count == 0) return CSTONE_OK;
+        if (s.numScratch < 3 || s.noOverlap || s.xyzForked || count == 0) return CSTONE_OK;
         CS_TRY(ensureAuxStream(ctx_));
         CS_HIP(ctx_, hipEventRecord(ctx_->evFork, ctx_->stream));
         CS_HIP(ctx_, hipStreamWaitEvent(ctx_->aux, ctx_->evFork, 0));
@@ -595,7 +582,7 @@ private:
         CS_TRY(rc);
         CS_HIP(ctx_, hipEventRecord(ctx_->evJoin, ctx_->aux));
         ctx_->sideBusy |= SIDE_AUX;
-        swapFieldsWithScratch(s, false);
+        swapFieldsWithScratch(s);
         s.xyzForked = true;
         return CSTONE_OK;
     }
@@ -611,7 +598,7 @@ private:
     /*! The incremental re-sort (resort.hpp): particles that are still inside the leaf their position belonged to at the
      *  previous sync are ordered leaf by leaf, the others are binned into their new leaves.  Same result as the sort of
      *  all keys; a box that changed, too many movers or an overfull leaf take the regular path.
-     *  Result: s.sorted (keys and order_ are final; x, y, z are then on their way or, s.fieldsMoved, in place),
+     *  Result: s.sorted (keys and order_ are final; x, y, z are then on their way),
      *  s.resortMarkers, and s.speculate -- switched off when the attempt has read the extents back and failed, with
      *  box_ being the box this sync needs from then on.  One read-back. */
     int tryResort(SyncState& s)
@@ -620,38 +607,11 @@ private:
         const bool attempt   = !firstCall_ && tileLeaves > 0 && layoutLeaves_ == fLeaves_ && fLeaves_ > 0 &&
                              resortBackoff_ == 0 && !s.boxMoved && mayResort(sortMode_);
         if (resortBackoff_ > 0) --resortBackoff_;
-        // The field-carrying leaf pass (resort.hpp, sortLeavesFields; CSTONE_FUSED_LEAF_PASS=1 and four scratch arrays): x,
-        // y, z, h move with the keys in ONE pass over the particle arrays instead of the leaf pass and the gathers of h and
-        // of x, y, z.  Measured at 1e8 particles, every particle drifting: 2.14 ms against 0.66 + 0.37 + 0.91 ms for the
-        // three passes it replaces (it saves 8 of their 92 bytes per particle, and the ordering network -- bound by
-        // instruction issue -- and the data movement do not overlap inside one wave the way separate kernels on two streams
-        // do): kept selectable, not the default.
-        const bool fusedLeafPass = std::getenv("CSTONE_FUSED_LEAF_PASS") != nullptr; // (read per sync: tests switch it)
-        const bool carryFields   = s.numScratch >= 4 && fusedLeafPass;
-        // The leaf table: the one the previous sync queued behind its halo search (queueLeafTable) if it was built for
-        // exactly the state this attempt starts from -- the same n and leaves, no failed sync since; a sync that does not
-        // attempt leaves it unused (it would describe a tree and a layout that this sync replaces).  Otherwise the table
-        // is built here, in front of the encode -- always, unless CSTONE_EARLY_LEAF_TABLE=1 (earlyLeafTableOn).
-        const bool tableQueued = earlyTable_;
-        const bool tableFits   = tableQueued && !earlyTableStale_ && attempt && earlyTableN_ == s.n &&
-                               earlyTableLeaves_ == fLeaves_ && earlyLeafTableOn();
-        earlyTable_ = earlyTableStale_ = false;
-        if (tableQueued) ++(tableFits ? earlyTablesUsed_ : earlyTablesRejected_);
         if (!attempt) return CSTONE_OK;
         if (!s.noHoist) CS_TRY(ensureTreeStream(ctx_));
-        if (tableFits)
-        {
-            // (nothing of this attempt reads the old tree on this stream: the tree stream may start at once)
-            if (!s.noHoist) CS_HIP(ctx_, hipEventRecord(ctx_->evTreeFork, ctx_->stream));
-            CS_TRY(resort_.beginAttempt(ctx_, keysAlt_.as<K>(), carryFields ? rb : 0));
-        }
-        else
-        {
-            CS_TRY(resort_.prepare(ctx_, fTree_.as<K>(), layout_.as<uint32_t>(), fLeaves_, s.n, keysAlt_.as<K>(), true,
-                                   carryFields ? rb : 0));
-            // (fillCompactLeavesKernel was the last reader of the old tree on this stream: the tree stream starts here)
-            if (!s.noHoist) CS_HIP(ctx_, hipEventRecord(ctx_->evTreeFork, ctx_->stream));
-        }
+        CS_TRY(resort_.prepare(ctx_, fTree_.as<K>(), layout_.as<uint32_t>(), fLeaves_, s.n, keysAlt_.as<K>(), true));
+        // (fillCompactLeavesKernel was the last reader of the old tree on this stream: the tree stream starts here)
+        if (!s.noHoist) CS_HIP(ctx_, hipEventRecord(ctx_->evTreeFork, ctx_->stream));
         const ResortArgs<K> ra = resort_.args();
         bool done              = false;
         CS_TRY(computeKeysResort(ctx_, curve_, kb, rb, *s.xPP, *s.yPP, *s.zPP, s.keys, s.n, box_, &ra,
@@ -660,37 +620,18 @@ private:
         CS_TRY(resort_.binMovers(ctx_, tileLeaves));
         // one read-back: the extents (slots 16..27) and what the re-sort found (28..31)
         CS_TRY(copyToPinned(ctx_, ctx_->hostScalars + 16, ctx_->devScalars + 16, 16 * sizeof(int)));
-        // The movers go into their bins behind that copy, while the host looks at what it brought: the kernel reads the
-        // count and the flags itself and needs nothing from the host.  The host then waits for the copy alone, not for the
-        // stream.  Only with CSTONE_EARLY_PLACE=1 (it did not measure as a gain); by default the
-        // movers are placed from the leaf pass's launch sequence, once the host knows the count
-        const bool earlyPlace = switchOn("CSTONE_EARLY_PLACE", "CSTONE_NO_EARLY_PLACE");
-        if (earlyPlace)
-        {
-            if (!ctx_->evReadBack) CS_HIP(ctx_, hipEventCreateWithFlags(&ctx_->evReadBack, hipEventDisableTiming));
-            CS_HIP(ctx_, hipEventRecord(ctx_->evReadBack, ctx_->stream));
-            CS_TRY(resort_.placeMoversEarly(ctx_, lastMovers_));
-        }
         // The device is busy with the encode and the mover bins from here on, and the host has nothing more to queue
         // before it has seen what they found.  The structural half of the focus-tree update follows from the tree and the counts of
         // the previous sync alone, and whatever becomes of the re-sort, this sync needs it: the node ops go to the tree
         // stream now (not before the encode is queued: the idle device would wait for the host), the host takes their result
         // and queues the rebalance and the linked octree behind them -- all of it beside the encode.
-        // CSTONE_TREE_HOIST_LATE=1 (tuning): the rebuild beside the leaf pass instead, once the re-sort is accepted
         if (!s.noHoist)
         {
-            s.hoistLate = std::getenv("CSTONE_TREE_HOIST_LATE") != nullptr;
-            CS_TRY(forkFocusOps(s));
-            if (!s.hoistLate)
-            {
-                CS_TRY(takeFocusOps(s));
-                CS_TRY(forkFocusRebuild(s));
-            }
+            CS_TRY(forkFocusOps());
+            CS_TRY(takeFocusOps(s));
+            CS_TRY(forkFocusRebuild(s));
         }
-        if (earlyPlace) { CS_HIP(ctx_, hipEventSynchronize(ctx_->evReadBack)); }
-        else { CS_HIP(ctx_, hipStreamSynchronize(ctx_->stream)); }
-        // (CSTONE_TREE_HOIST_LATE: the node ops on the tree stream have long finished, no wait of its own)
-        if (s.opsOnTree && !s.opsTaken) CS_TRY(takeFocusOps(s));
+        CS_HIP(ctx_, hipStreamSynchronize(ctx_->stream));
         cstone_box next = box_;
         if (s.speculate)
         {
@@ -708,24 +649,10 @@ private:
         {
             // (stepGlobalTree would find this too, further down: no leaf pass, gather or tree step for nothing.  With
             //  the rebuild on its way already, sync() puts the domain back to its first-call state)
-            if (s.opsTaken && markers >= s.n) return fail(ctx_, CSTONE_E_ARG, "domain_sync: all particles removed");
-            if (carryFields)
-            {
-                ResortFields rf{rb, {*s.xPP, *s.yPP, *s.zPP, *s.hPP}, {s.scratch[0], s.scratch[1], s.scratch[2], s.scratch[3]}};
-                CS_TRY(resort_.sortLeavesFields(ctx_, keysAlt_.as<K>(), s.keys, order_.as<uint32_t>(), rf, movers, markers,
-                                                J, tileLeaves));
-                swapFieldsWithScratch(s, true);
-                s.fieldsMoved = true;
-            }
-            else
-            {
-                CS_TRY(resort_.sortLeaves(ctx_, keysAlt_.as<K>(), s.keys, order_.as<uint32_t>(), movers, markers, J,
-                                          tileLeaves, (flags & RESORT_LARGE_QUIET_TILES) != 0));
-                CS_TRY(forkXyzGather(s, s.n - markers)); // (the ordering is final: x, y, z follow on the second stream)
-            }
-            // placeMovers and the leaf pass are queued: the rebalance and the linked octree run beside them.  Everything
-            // that read the old tree (prepare's fillCompactLeavesKernel; `attempt` above) lies before the read-back
-            if (s.opsTaken && !s.rebuilt) CS_TRY(forkFocusRebuild(s));
+            if (s.rebuilt && markers >= s.n) return fail(ctx_, CSTONE_E_ARG, "domain_sync: all particles removed");
+            CS_TRY(resort_.sortLeaves(ctx_, keysAlt_.as<K>(), s.keys, order_.as<uint32_t>(), movers, markers, J,
+                                      tileLeaves, (flags & RESORT_LARGE_QUIET_TILES) != 0));
+            CS_TRY(forkXyzGather(s, s.n - markers)); // (the ordering is final: x, y, z follow on the second stream)
             CS_HIP(ctx_, hipMemsetAsync(ctx_->devScalars + 3, 0, sizeof(int), ctx_->stream));
             s.sorted    = true;
             lastMovers_ = movers;
@@ -872,21 +799,12 @@ private:
             CS_TRY(joinTreeStream());
             return focusCounts(s.keys, s.numAssigned, s.converged);
         }
-        if (s.opsOnTree)
-        {
-            // the re-sort fell back (or never started) behind the fork of the node ops: they are not made again, the
-            // rest keeps its place and its stream.  The radix passes saturate the memory system as the gather does
-            // here, so there is no better place for the rebuild on this path
-            if (!s.opsTaken) CS_TRY(takeFocusOps(s));
-            CS_TRY(focusRebuild(s.converged, s.newL));
-            return focusCounts(s.keys, s.numAssigned, s.converged);
-        }
         return updateFocus(s.keys, s.numAssigned, &conv);
     }
 
     //! focusOps of this sync on the tree stream, behind the leaf-table prepare of the main stream (evTreeFork stands
     //! behind its fillCompactLeavesKernel, the last reader of the old tree)
-    int forkFocusOps(SyncState& s)
+    int forkFocusOps()
     {
         CS_HIP(ctx_, hipStreamWaitEvent(ctx_->tree, ctx_->evTreeFork, 0));
         int rc;
@@ -897,7 +815,6 @@ private:
         }
         CS_TRY(rc);
         CS_HIP(ctx_, hipEventRecord(ctx_->evTreeJoin, ctx_->tree));
-        s.opsOnTree = true;
         return CSTONE_OK;
     }
     //! the host waits for the node ops on the tree stream and reads {changed, new leaf count}
@@ -905,7 +822,6 @@ private:
     {
         CS_HIP(ctx_, hipEventSynchronize(ctx_->evTreeJoin));
         treeInFlight_ = false;
-        s.opsTaken    = true;
         return readFocusOps(&s.converged, &s.newL);
     }
     //! focusRebuild on the tree stream (the host knows the new leaf count), behind the node ops and with them behind the
@@ -946,69 +862,19 @@ private:
         layoutLeaves_ = L;
         // gatherArrays(h) + segmentMax + scale in one pass over h (every leaf is assigned on one rank: the leaves' particles
         // are all the assigned particles)
-        static const bool splitGather = std::getenv("CSTONE_SPLIT_H_GATHER") != nullptr; // tuning: the two-pass form
-        if (s.fieldsMoved)
-        {
-            // h is in SFC order already; the radii follow from the maxima the leaf pass folded per OLD leaf
-            CS_TRY(resort_.radiiOfLeaves(ctx_, L, layout_.as<uint32_t>(), *s.hPP, rb, haloSearchExt_, radii_.as<float>()));
-        }
-        else
-        {
-            // where h goes: the first scratch array -- unless x, y, z are still on their way there on the second stream; a
-            // fourth scratch array then takes h (no waiting), with three the gather of h waits for them
-            void** hDst = s.scratch;
-            if (s.xyzForked && s.numScratch >= 4) { hDst = &s.scratch[3]; }
-            else { CS_TRY(joinXyzGather(s)); }
-            if (splitGather)
-            {
-                CS_TRY(cstone_hip_gather(ctx_, sizeof(T), order_.as<uint32_t>(), s.numAssigned, *s.hPP, *hDst));
-                std::swap(*s.hPP, *hDst);
-                CS_TRY(cstone_hip_halo_radii(ctx_, rb, *s.hPP, layout_.as<uint32_t>(), 0, L, L, haloSearchExt_,
-                                             radii_.as<float>()));
-            }
-            else
-            {
-                CS_TRY(gatherWithHaloRadii(ctx_, rb, *s.hPP, order_.as<uint32_t>(), *hDst, layout_.as<uint32_t>(), L,
-                                           haloSearchExt_, radii_.as<float>()));
-                std::swap(*s.hPP, *hDst);
-            }
-        }
+        // where h goes: the first scratch array -- unless x, y, z are still on their way there on the second stream; a
+        // fourth scratch array then takes h (no waiting), with three the gather of h waits for them
+        void** hDst = s.scratch;
+        if (s.xyzForked && s.numScratch >= 4) { hDst = &s.scratch[3]; }
+        else { CS_TRY(joinXyzGather(s)); }
+        CS_TRY(gatherWithHaloRadii(ctx_, rb, *s.hPP, order_.as<uint32_t>(), *hDst, layout_.as<uint32_t>(), L,
+                                   haloSearchExt_, radii_.as<float>()));
+        std::swap(*s.hPP, *hDst);
         CS_HIP(ctx_, hipMemsetAsync(flags_.p, 0, size_t(L) * sizeof(int), ctx_->stream));
         // one rank: every leaf is assigned, no halo leaves: layout = exclusive scan of the leaf counts (layout.hpp:150-165),
         // which is the inclusive scan written above shifted by one.
         CS_TRY(cstone_hip_find_halos(ctx_, curve_, kb, rb, fPrefixes_.p, fChild_.as<int32_t>(), fItl_.as<int32_t>(),
                                      fTree_.p, radii_.as<float>(), &box_, 0, L, flags_.as<int32_t>()));
-        return queueLeafTable(s);
-    }
-
-    //! an experiment that is off unless `on` is set to 1 (and `off`, the switch's first name, is not set)
-    static bool switchOn(const char* on, const char* off)
-    {
-        const char* e = std::getenv(on);
-        return e && e[0] == '1' && std::getenv(off) == nullptr;
-    }
-    static bool earlyLeafTableOn() { return switchOn("CSTONE_EARLY_LEAF_TABLE", "CSTONE_NO_EARLY_LEAF_TABLE"); }
-
-    /*! The leaf table of the NEXT sync's re-sort (resort.hpp, prepareTable).  It follows from the tree, the layout and
-     *  the particle count this sync leaves behind, and the main stream has nothing more to do from here on but wait for
-     *  the gather of x, y, z on the second stream: built here, the table's six small launches are off the next sync's
-     *  critical path, where nothing can run beside them (beside the gather they take 200 us instead of 75).  It stands behind the halo search and with it behind
-     *  countLeaves and radiiOfLeaves, the last readers of the table this sync was re-sorted with; finishSync
-     *  synchronises, so it is complete before the next sync's tree stream may touch the tree.  Queued only when the next
-     *  sync may attempt a re-sort as far as is known now; tryResort decides whether the table still fits.
-     *  OFF by default: the headline did not move by more than its noise; CSTONE_EARLY_LEAF_TABLE=1
-     *  turns it on, read per sync. */
-    int queueLeafTable(const SyncState& s)
-    {
-        earlyTable_ = false;
-        if (!earlyLeafTableOn()) return CSTONE_OK;
-        if (LeafResort<K>::leavesPerTile(bucketFocus_) == 0 || !mayResort(sortMode_) || resortBackoff_ != 0) return CSTONE_OK;
-        if (fLeaves_ <= 0 || layoutLeaves_ != fLeaves_ || s.numAssigned == 0) return CSTONE_OK;
-        CS_TRY(resort_.prepareTable(ctx_, fTree_.as<K>(), layout_.as<uint32_t>(), fLeaves_, s.numAssigned, true));
-        earlyTable_       = true;
-        earlyTableStale_  = false;
-        earlyTableN_      = s.numAssigned;
-        earlyTableLeaves_ = fLeaves_;
         return CSTONE_OK;
     }
 
@@ -1016,7 +882,7 @@ private:
     int gatherFields(SyncState& s)
     {
         CS_TRY(joinXyzGather(s)); // (the property gathers below go through the buffers x, y, z were read from)
-        if (s.fieldsMoved || s.xyzForked) {} // (x, y, z went with the leaf pass, or on the second stream)
+        if (s.xyzForked) {} // (x, y, z went on the second stream)
         else if (s.numScratch >= 3)
         {
             // three free buffers (the caller's scratch tuple, R/domain/domain.hpp:196-206 has three as well): x, y, z go
@@ -1024,7 +890,7 @@ private:
             const void* src[3] = {*s.xPP, *s.yPP, *s.zPP};
             void* dst[3]       = {s.scratch[0], s.scratch[1], s.scratch[2]};
             CS_TRY(cstone_hip_gather_multi(ctx_, sizeof(T), order_.as<uint32_t>(), s.numAssigned, src, dst, 3));
-            swapFieldsWithScratch(s, false);
+            swapFieldsWithScratch(s);
         }
         else
         {
@@ -1206,13 +1072,6 @@ private:
     LeafResort<K> resort_;
     int resortBackoff_ = 0, resorts_ = 0, resortFallbacks_ = 0;
     bool resortedThisSync_ = false;
-    // the leaf table the last sync queued for this one (queueLeafTable): the state it was built for, and how the tables
-    // built so far fared
-    bool earlyTable_       = false;
-    bool earlyTableStale_  = false; // a sync failed since it was queued
-    size_t earlyTableN_    = 0;
-    int earlyTableLeaves_  = 0;
-    uint32_t earlyTablesUsed_ = 0, earlyTablesRejected_ = 0;
     DevBuf gTree_, gCounts_;
     int gCap_ = 0, gLeaves_ = 0;
     GlobalTreeHost<K> gHost_; // host copies of the global tree and its counts (the host makes its update step)
@@ -1427,13 +1286,6 @@ int cstone_hip_domain_stats_get(cstone_hip_domain* dom, cstone_hip_domain_stats*
 {
     if (!dom || !out) return CSTONE_E_ARG;
     dom->impl->stats(out);
-    return CSTONE_OK;
-}
-
-int cstone_hip_domain_leaf_table_stats(cstone_hip_domain* dom, uint32_t* used, uint32_t* rejected)
-{
-    if (!dom || !used || !rejected) return CSTONE_E_ARG;
-    dom->impl->leafTableStats(used, rejected);
     return CSTONE_OK;
 }
 

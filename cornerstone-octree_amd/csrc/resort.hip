@@ -1,7 +1,6 @@
 // Incremental re-sort of Domain::sync: leaf table, mover binning and the leaf pass (see resort.hpp for the scheme).
 // Replaces, for a sync whose particles mostly stayed in their leaves, the reference's full sort of all keys
 // (sortByKeyGpu, R/primitives/primitives_gpu.cu:305-353).  gfx950: wave64, 160 KB LDS per CU.
-#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
@@ -193,8 +192,6 @@ __global__ __launch_bounds__(256) void checkTilesKernel(const uint32_t* __restri
     uint32_t t       = blockIdx.x * 256 + threadIdx.x;
     if (t == 0)
     {
-        // (J of a table that keeps it in a buffer of its own goes to the slot the host reads)
-        if (numCompact != (const uint32_t*)scalars + 2) scalars[2] = int(J);
         scalars[0] = int(inOffset[J + 1] - inOffset[J]);
         if (*moverCount > moverCap) atomicOr(&scalars[1], 4);
     }
@@ -203,8 +200,8 @@ __global__ __launch_bounds__(256) void checkTilesKernel(const uint32_t* __restri
     uint32_t j1    = min(j0 + uint32_t(leavesPerTile), J);
     const uint32_t old = leafPos[j1] - leafPos[j0], arrivals = inOffset[j1] - inOffset[j0];
     if (old + arrivals > RESORT_TILE_SLOTS) atomicOr(&scalars[1], 2);
-    // a tile in which nothing moved but with more slots than the quiet instantiation of the leaf pass has: the other
-    // instantiation has to be launched for it even without movers
+    // a tile in which nothing moved but with more slots than the quiet-tile kernel of the leaf pass has: the wave
+    // kernel has to be launched for it even without movers
     if (arrivals == 0 && layoutNew[j1] - layoutNew[j0] == old && old > RESORT_QUIET_SLOTS) atomicOr(&scalars[1], 8);
 }
 
@@ -223,66 +220,26 @@ __global__ __launch_bounds__(256) void placeMoversKernel(const K* __restrict__ m
     binIdx[at]  = moverIdx[m];
 }
 
-//! placeMoversKernel queued before the host has seen the count: the count and the flags are read here (scalars: [1]
-//! flags, [3] movers), a grid sized by the movers the caller expects strides over the list, and an attempt that failed
-//! places nothing
-template<class K>
-__global__ __launch_bounds__(256) void placeMoversEarlyKernel(const K* __restrict__ moverKeys,
-                                                              const uint32_t* __restrict__ moverIdx,
-                                                              const uint32_t* __restrict__ dest,
-                                                              const uint32_t* __restrict__ slot,
-                                                              const int* __restrict__ scalars, uint32_t moverCap,
-                                                              const uint32_t* __restrict__ inOffset,
-                                                              K* __restrict__ binKeys, uint32_t* __restrict__ binIdx)
-{
-    const uint32_t M = uint32_t(scalars[3]);
-    if (M > moverCap || (scalars[1] & 7)) return;
-    for (uint32_t m = blockIdx.x * 256 + threadIdx.x; m < M; m += gridDim.x * 256)
-    {
-        uint32_t at = inOffset[dest[m]] + slot[m];
-        binKeys[at] = moverKeys[m];
-        binIdx[at]  = moverIdx[m];
-    }
-}
-
-/*! The leaf pass.  A workgroup takes G consecutive (non-empty) leaves of the previous sync.  Its LDS slots:
- *  [the old positions of its leaves, in place | the movers arriving in its leaves, leaf by leaf].  The encode pass has
- *  replaced the key of every particle that left its leaf by a hole (key ~0, sorts last), so the old positions are
- *  copied as they are.  Then, per tile:
- *   - nothing left or arrived (the common case of a quiet region): one lane per leaf insertion-sorts the leaf in LDS
- *     -- the particles come in the order of the previous sync, i.e. almost sorted: one LDS read per element --, and the
- *     tile is written back slot by slot;
- *   - otherwise every particle counts the elements of its leaf (old positions and arrivals) that sort in front of it,
- *     by (key, old index): LDS broadcast reads, all 256 lanes busy, cost independent of the disorder.  The count is the
- *     particle's place in the leaf; holes rank last and are dropped.
- *  Either way leaf j's new content lands at layoutNew[j]...: ascending keys, ties by old index = the stable sort. */
-template<class K, int G, bool COUNTING>
-__global__ __launch_bounds__(256) void leafSortKernel(const K* __restrict__ keysIn, const uint64_t* __restrict__ mask,
-                                                      const uint32_t* __restrict__ rank, const K* __restrict__ leafLo,
-                                                      const uint32_t* __restrict__ leafPos,
+/*! The leaf pass for QUIET tiles.  A workgroup takes G consecutive (non-empty) leaves of the previous sync, a tile.  The
+ *  encode pass has replaced the key of every particle that left its leaf by a hole (key ~0, sorts last).  A tile is
+ *  quiet when nothing arrived in its leaves and every leaf keeps its size, i.e. nobody left either: the common case of
+ *  a region at rest.  Its keys (the old positions of its leaves, as they are) go to LDS with the 16-bit slot they came
+ *  from -- up to RESORT_QUIET_SLOTS of them, 39 KB: four workgroups per CU --, one lane per leaf insertion-sorts the
+ *  leaf there by (key, old index) -- the particles come in the order of the previous sync, i.e. almost sorted: one LDS
+ *  read per element --, and the tile is written back slot by slot to layoutNew[first leaf] ...: ascending keys, ties
+ *  by old index = the stable sort.  A workgroup whose tile is not quiet, or quiet but longer than that, leaves after
+ *  the vote: leafSortWaveKernel below takes those tiles (same grid, same vote). */
+template<class K, int G>
+__global__ __launch_bounds__(256) void leafSortKernel(const K* __restrict__ keysIn, const uint32_t* __restrict__ leafPos,
                                                       const uint32_t* __restrict__ inOffset,
-                                                      const uint32_t* __restrict__ layoutNew,
-                                                      const K* __restrict__ binKeys, const uint32_t* __restrict__ binIdx,
-                                                      uint32_t J, bool alwaysCount, K* __restrict__ keysOut,
+                                                      const uint32_t* __restrict__ layoutNew, uint32_t J,
+                                                      bool alwaysCount, K* __restrict__ keysOut,
                                                       uint32_t* __restrict__ orderOut)
 {
     constexpr int ITER = (RESORT_TILE_SLOTS + 255) / 256;
-    constexpr K HOLE   = ~K(0);
-    // Two instantiations share this body and the grid: COUNTING = false takes the quiet tiles (keys and old indices in
-    // LDS, up to RESORT_QUIET_SLOTS of them = 39 KB: four workgroups per CU), COUNTING = true the tiles in which something
-    // moved, and the few quiet ones with more slots than that (digests and the new
-    // order's key bits folded to 16, 27 KB: five per CU); a workgroup whose tile is of the other kind leaves after the
-    // setup.
-    __shared__ __attribute__((aligned(8))) uint32_t sWordsA[COUNTING ? RESORT_TILE_SLOTS / 2 : RESORT_QUIET_SLOTS * sizeof(K) / 4];
-    __shared__ uint32_t sWordsB[COUNTING ? RESORT_TILE_SLOTS : RESORT_QUIET_SLOTS / 2];
-    K* const sKey        = reinterpret_cast<K*>(sWordsA);        // quiet tiles: the keys ...
-    uint16_t* const sIdx = reinterpret_cast<uint16_t*>(sWordsB); // ... and the slots of the tile they came from
+    __shared__ __attribute__((aligned(8))) K sKey[RESORT_QUIET_SLOTS]; // the keys ...
+    __shared__ uint16_t sIdx[RESORT_QUIET_SLOTS];                      // ... and the slots of the tile they came from
     __shared__ uint32_t posK[G + 1], inK[G + 1], outK[G + 1];
-    // tiles that count: first key of every leaf, the low key bits a digest leaves out, first 4-slot chunk of every leaf
-    __shared__ K loK[G + 1];
-    __shared__ uint8_t cutK[G];
-    __shared__ uint32_t chunkK[G + 1];
-    static_assert(G <= 64, "the chunk prefix of a tile is one wave scan");
 
     const uint32_t j0 = blockIdx.x * uint32_t(G);
     const uint32_t nl = min(uint32_t(G), J - j0);
@@ -292,24 +249,8 @@ __global__ __launch_bounds__(256) void leafSortKernel(const K* __restrict__ keys
         posK[t] = leafPos[j0 + t];
         inK[t]  = inOffset[j0 + t];
         outK[t] = layoutNew[j0 + t];
-        if constexpr (COUNTING) loK[t] = leafLo[j0 + t];
     }
     __syncthreads();
-    if (COUNTING && t < 64)
-    {
-        // chunks of four old slots, leaf by leaf: a lane of the counting path takes one chunk at a time
-        const uint32_t mine = t < nl ? (posK[t + 1] - posK[t] + 3) / 4 : 0u;
-        const uint32_t incl = waveInclusiveScan(mine, t);
-        if (t < nl) chunkK[t] = incl - mine;
-        if (t == 63) chunkK[nl] = incl;
-        if (t < nl)
-        {
-            // 24 leading bits of key - loK[t] tell the particles of a leaf apart in all but a few cases
-            const K span   = loK[t + 1] - loK[t] - 1;
-            const int bits = span ? int(8 * sizeof(K)) - clzKey(span) : 0;
-            cutK[t]        = uint8_t(bits > 24 ? bits - 24 : 0);
-        }
-    }
     const uint32_t p0 = posK[0], p1 = posK[nl], in0 = inK[0], in1 = inK[nl];
     const uint32_t nOldAll = p1 - p0, slots = nOldAll + (in1 - in0);
     // guarded by checkTilesKernel: a launch only happens when every workgroup fits
@@ -317,282 +258,76 @@ __global__ __launch_bounds__(256) void leafSortKernel(const K* __restrict__ keys
     // quiet tile: no arrivals, and every leaf keeps its size (without arrivals: nobody left)
     bool changed = in1 != in0 || alwaysCount;
     if (t < nl) changed = changed || (outK[t + 1] - outK[t]) != (posK[t + 1] - posK[t]);
-    // (a quiet tile beyond the slots of the quiet instantiation goes the other way: it can hold RESORT_TILE_SLOTS)
+    // (a quiet tile beyond RESORT_QUIET_SLOTS goes the other way as well: the wave kernel holds no keys in LDS)
     const bool quiet = !__syncthreads_or(changed) && nOldAll <= RESORT_QUIET_SLOTS;
-    if (quiet == COUNTING) return; // the other instantiation's tile
+    if (!quiet) return;
 
-    // Tiles that count keep no keys in LDS, only 32-bit digests: 24 leading bits of (key - first key of the leaf), then
-    // the slot in the leaf (old slots first, then arrivals; at most 256).  The digests of a leaf are distinct, and
-    // ordered like (key, old index) as long as the leading key bits of its elements differ -- checked afterwards.
-    uint32_t* const sDig = sWordsB; // digests by slot
-    uint16_t* const sNew = reinterpret_cast<uint16_t*>(sWordsA); // leading key bits in the NEW order, folded to 16 bits
-    auto fold            = [](uint32_t dig) { return uint16_t((dig >> 8) ^ (dig >> 24)); }; // equal bits -> equal folds
-    auto digest          = [&](K key, uint32_t k, uint32_t slot)
-    { return (uint32_t((key - loK[k]) >> cutK[k]) << 8) | slot; };
-    // leaf of bin entry m: last k with inK[k] <= m
-    auto leafOfArrival = [&](uint32_t m)
-    {
-        uint32_t lo = 0, hi = nl;
-        while (hi - lo > 1)
-        {
-            uint32_t mid = (lo + hi) / 2;
-            if (inK[mid] <= m) lo = mid;
-            else hi = mid;
-        }
-        return lo;
-    };
-    if constexpr (!COUNTING)
-    {
-        // old positions: all loads of a thread are issued before the first is used
-        K key[ITER];
+    // old positions: all loads of a thread are issued before the first is used
+    K key[ITER];
 #pragma unroll
-        for (int i = 0; i < ITER; ++i)
-        {
-            const uint32_t p = p0 + t + 256u * i;
-            if (p < p1) key[i] = keysIn[p];
-        }
-#pragma unroll
-        for (int i = 0; i < ITER; ++i)
-        {
-            const uint32_t p = p0 + t + 256u * i;
-            if (p < p1)
-            {
-                sKey[p - p0] = key[i];
-                sIdx[p - p0] = uint16_t(p - p0);
-            }
-        }
+    for (int i = 0; i < ITER; ++i)
+    {
+        const uint32_t p = p0 + t + 256u * i;
+        if (p < p1) key[i] = keysIn[p];
     }
-    else
+#pragma unroll
+    for (int i = 0; i < ITER; ++i)
     {
-        // old positions -> digests, in two batches (registers: key, leaf-start word and rank of every load in flight)
-        constexpr int HALF = (ITER + 1) / 2;
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
+        const uint32_t p = p0 + t + 256u * i;
+        if (p < p1)
         {
-            K key[HALF];
-            uint64_t word[HALF];
-            uint32_t rk[HALF];
-#pragma unroll
-            for (int i = 0; i < HALF; ++i)
-            {
-                const uint32_t p = p0 + t + 256u * (h * HALF + i);
-                if (p < p1)
-                {
-                    key[i]  = keysIn[p];
-                    word[i] = mask[p >> 6];
-                    rk[i]   = rank[p >> 6];
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < HALF; ++i)
-            {
-                const uint32_t p = p0 + t + 256u * (h * HALF + i);
-                if (p < p1)
-                {
-                    const uint32_t k = rk[i] + uint32_t(__popcll(word[i] & ((2ull << (p & 63u)) - 1))) - 1u - j0;
-                    sDig[p - p0]     = key[i] == HOLE ? ~0u : digest(key[i], k, p - posK[k]);
-                }
-            }
-        }
-    }
-    if constexpr (COUNTING)
-    {
-        for (uint32_t m = in0 + t; m < in1; m += 256)
-        {
-            const uint32_t k          = leafOfArrival(m);
-            sDig[nOldAll + (m - in0)] = digest(binKeys[m], k, (posK[k + 1] - posK[k]) + (m - inK[k]));
+            sKey[p - p0] = key[i];
+            sIdx[p - p0] = uint16_t(p - p0);
         }
     }
     __syncthreads();
 
-    if constexpr (!COUNTING)
+    if (t < nl)
     {
-        if (t < nl)
+        const uint32_t s = posK[t] - p0, nOld = posK[t + 1] - posK[t];
+        if (nOld > 1)
         {
-            const uint32_t s = posK[t] - p0, nOld = posK[t + 1] - posK[t];
-            if (nOld > 1)
+            const uint32_t e = s + nOld;
+            K pk             = sKey[s];
+            K nk             = sKey[s + 1];
+            for (uint32_t a = s + 1; a < e; ++a)
             {
-                const uint32_t e = s + nOld;
-                K pk             = sKey[s];
-                K nk             = sKey[s + 1];
-                for (uint32_t a = s + 1; a < e; ++a)
+                const K ka = nk;
+                if (a + 1 < e) nk = sKey[a + 1];
+                if (ka > pk)
                 {
-                    const K ka = nk;
-                    if (a + 1 < e) nk = sKey[a + 1];
-                    if (ka > pk)
-                    {
-                        pk = ka;
-                        continue;
-                    }
-                    const uint32_t ia = sIdx[a];
-                    if (ka == pk && ia > sIdx[a - 1]) continue;
-                    uint32_t b = a;
-                    while (b > s)
-                    {
-                        const K kb        = sKey[b - 1];
-                        const uint32_t ib = sIdx[b - 1];
-                        if (kb < ka || (kb == ka && ib < ia)) break;
-                        sKey[b] = kb;
-                        sIdx[b] = ib;
-                        --b;
-                    }
-                    sKey[b] = ka;
-                    sIdx[b] = ia;
+                    pk = ka;
+                    continue;
                 }
+                const uint32_t ia = sIdx[a];
+                if (ka == pk && ia > sIdx[a - 1]) continue;
+                uint32_t b = a;
+                while (b > s)
+                {
+                    const K kb        = sKey[b - 1];
+                    const uint32_t ib = sIdx[b - 1];
+                    if (kb < ka || (kb == ka && ib < ia)) break;
+                    sKey[b] = kb;
+                    sIdx[b] = ib;
+                    --b;
+                }
+                sKey[b] = ka;
+                sIdx[b] = ia;
             }
         }
-        __syncthreads();
-        // every leaf kept its size: slot e of the tile goes to layoutNew[first leaf] + e
-        const uint32_t out0 = outK[0];
-#pragma unroll
-        for (int i = 0; i < ITER; ++i)
-        {
-            const uint32_t e = t + 256u * i;
-            if (e < nOldAll)
-            {
-                keysOut[out0 + e]  = sKey[e];
-                orderOut[out0 + e] = p0 + sIdx[e];
-            }
-        }
-        return;
-    }
-
-    if constexpr (COUNTING)
-    {
-    // ---- counting.  A lane takes a chunk of four consecutive old slots of ONE leaf and scans the leaf's digests once
-    // for all four: LDS reads / 4, two 32-bit vector instructions per comparison.
-    constexpr int CHUNK_ITER = (RESORT_TILE_SLOTS / 4 + G + 255) / 256;
-    const uint32_t numChunks = chunkK[nl];
-    uint32_t chunkLeaf[CHUNK_ITER], chunkSlot[CHUNK_ITER], place[CHUNK_ITER][4];
-#pragma unroll
-    for (int i = 0; i < CHUNK_ITER; ++i)
-    {
-        const uint32_t c = t + 256u * i;
-        if (c < numChunks)
-        {
-            uint32_t lo = 0, hi = nl; // leaf of the chunk: last k with chunkK[k] <= c
-            while (hi - lo > 1)
-            {
-                uint32_t mid = (lo + hi) / 2;
-                if (chunkK[mid] <= c) lo = mid;
-                else hi = mid;
-            }
-            const uint32_t k  = lo;
-            const uint32_t o0 = posK[k] - p0, nOld = posK[k + 1] - posK[k];
-            const uint32_t a0 = nOldAll + (inK[k] - in0), nInc = inK[k + 1] - inK[k];
-            const uint32_t s0 = 4 * (c - chunkK[k]); // first slot of the chunk inside the leaf
-            chunkLeaf[i] = k, chunkSlot[i] = s0;
-            uint32_t d[4], cnt[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                d[j] = s0 + j < nOld ? sDig[o0 + s0 + j] : ~0u; // (slots behind the leaf's end count as holes)
-            uint32_t q = 0;
-            for (; q + 4 <= nOld; q += 4)
-            {
-                const uint32_t v0 = sDig[o0 + q], v1 = sDig[o0 + q + 1], v2 = sDig[o0 + q + 2], v3 = sDig[o0 + q + 3];
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    cnt[j] += (v0 < d[j]) + (v1 < d[j]) + (v2 < d[j]) + (v3 < d[j]);
-            }
-            for (; q < nOld; ++q)
-            {
-                const uint32_t v0 = sDig[o0 + q];
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    cnt[j] += v0 < d[j];
-            }
-            for (q = 0; q < nInc; ++q)
-            {
-                const uint32_t v0 = sDig[a0 + q];
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    cnt[j] += v0 < d[j];
-            }
-            const uint32_t base = outK[k] - outK[0];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-            {
-                place[i][j] = cnt[j];
-                if (d[j] != ~0u) sNew[base + cnt[j]] = fold(d[j]);
-            }
-        }
-    }
-    auto placeByDigest = [&](uint32_t k, uint32_t dx)
-    {
-        const uint32_t o0 = posK[k] - p0, nOld = posK[k + 1] - posK[k];
-        const uint32_t a0 = nOldAll + (inK[k] - in0), nInc = inK[k + 1] - inK[k];
-        uint32_t less = 0;
-        for (uint32_t q = 0; q < nOld; ++q)
-            less += sDig[o0 + q] < dx;
-        for (uint32_t q = 0; q < nInc; ++q)
-            less += sDig[a0 + q] < dx;
-        return less;
-    };
-    for (uint32_t m = in0 + t; m < in1; m += 256)
-    {
-        const uint32_t k = leafOfArrival(m), d = sDig[nOldAll + (m - in0)];
-        sNew[(outK[k] - outK[0]) + placeByDigest(k, d)] = fold(d);
     }
     __syncthreads();
-
-    // an element whose neighbour in the new order of its leaf has the same (folded) leading key bits is placed again, by
-    // key and old index proper, from global memory (the others are where they belong: leading bits that differ decide)
-    auto clashes = [&](uint32_t k, uint32_t pl, uint16_t bitsX)
-    {
-        const uint32_t base = outK[k] - outK[0], cnt = outK[k + 1] - outK[k];
-        return (pl > 0 && sNew[base + pl - 1] == bitsX) || (pl + 1 < cnt && sNew[base + pl + 1] == bitsX);
-    };
-    auto placeExact = [&](uint32_t k, K kx, uint32_t ix)
-    {
-        const uint32_t nOld = posK[k + 1] - posK[k], nInc = inK[k + 1] - inK[k];
-        uint32_t less = 0;
-        for (uint32_t q = 0; q < nOld; ++q)
-        {
-            const K kq = keysIn[posK[k] + q]; // (a hole is larger than any key)
-            less += (kq < kx || (kq == kx && posK[k] + q < ix)) ? 1u : 0u;
-        }
-        for (uint32_t q = 0; q < nInc; ++q)
-        {
-            const K kq = binKeys[inK[k] + q];
-            less += (kq < kx || (kq == kx && binIdx[inK[k] + q] < ix)) ? 1u : 0u;
-        }
-        return less;
-    };
+    // every leaf kept its size: slot e of the tile goes to layoutNew[first leaf] + e
+    const uint32_t out0 = outK[0];
 #pragma unroll
-    for (int i = 0; i < CHUNK_ITER; ++i)
+    for (int i = 0; i < ITER; ++i)
     {
-        const uint32_t c = t + 256u * i;
-        if (c < numChunks)
+        const uint32_t e = t + 256u * i;
+        if (e < nOldAll)
         {
-            const uint32_t k = chunkLeaf[i], nOld = posK[k + 1] - posK[k];
-            const uint32_t p = posK[k] + chunkSlot[i]; // position of the chunk's first slot
-            K kx[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                kx[j] = chunkSlot[i] + j < nOld ? keysIn[p + j] : HOLE;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-            {
-                if (kx[j] != HOLE)
-                {
-                    uint32_t pl = place[i][j];
-                    if (clashes(k, pl, fold(sDig[p - p0 + j]))) pl = placeExact(k, kx[j], p + j);
-                    keysOut[outK[k] + pl]  = kx[j];
-                    orderOut[outK[k] + pl] = p + j;
-                }
-            }
+            keysOut[out0 + e]  = sKey[e];
+            orderOut[out0 + e] = p0 + sIdx[e];
         }
-    }
-    for (uint32_t m = in0 + t; m < in1; m += 256)
-    {
-        const uint32_t k = leafOfArrival(m), d = sDig[nOldAll + (m - in0)];
-        const K kx        = binKeys[m];
-        const uint32_t ix = binIdx[m];
-        uint32_t pl       = placeByDigest(k, d);
-        if (clashes(k, pl, fold(d))) pl = placeExact(k, kx, ix);
-        keysOut[outK[k] + pl]  = kx;
-        orderOut[outK[k] + pl] = ix;
-    }
     }
 }
 
@@ -757,73 +492,14 @@ __device__ __forceinline__ void pairSort(uint32_t (&d)[2], unsigned lane)
     if constexpr (SEG >= 32) { mirrorExchange<31, 16u>(d, lane), halfClean<8, 2>(d, lane), inLaneExchange(d); } // 64
 }
 
-#ifdef CSTONE_WAVE_OCC4
-#define CSTONE_WAVE_OCC __attribute__((amdgpu_waves_per_eu(4, 4)))
-#else
-#define CSTONE_WAVE_OCC
-#endif
-// ---- the FIELD-CARRYING flavour of the leaf pass (round 4).  A sync used to make four passes over the particle arrays:
-//      encode (x, y, z read), leaf pass (keys), gather of h, gather of x, y, z -- 132 bytes per particle.  The lane that
-//      holds slot s of a leaf knows where that slot goes as soon as the leaf is ordered, so it can carry x, y, z, h of the
-//      slot along: they are loaded with the key (the stayers' from the old arrays at the slot's own position: coalesced;
-//      the arrivals' from their bins, where the encode kernel and placeMoversKernel have put them) and stored at the new
-//      place with the key.  The gathers disappear: 8 + 32 bytes read, 12 + 32 written per particle, and the maximum of h
-//      over the leaf's new content -- what Halos::discover wants per leaf -- is folded by the wave on the way.
-template<class T>
-struct LeafFields
-{
-    static constexpr bool on = true;
-    using Real               = T;
-    const T *x, *y, *z, *h;     // the old order (an arrival's values are fetched from its old position)
-    T *ox, *oy, *oz, *oh;       // the new order
-    T* hmax;                    // [J]: max h over the new content of every compact leaf (0 for an empty one)
-};
-struct NoLeafFields
-{
-    static constexpr bool on = false;
-    using Real               = float;
-};
-template<class T>
-struct LeafVal
-{
-    T x, y, z, h;
-};
-
-//! value of lane ^ X for a float or a double (both halves through the VALU permutations above)
-template<int X, class T>
-__device__ __forceinline__ T laneXorReal(T v, unsigned lane)
-{
-    if constexpr (sizeof(T) == 4) { return __uint_as_float(laneXor<X>(__float_as_uint(v), lane)); }
-    else
-    {
-        const uint64_t u  = uint64_t(__double_as_longlong(v));
-        const uint32_t lo = laneXor<X>(uint32_t(u), lane), hi = laneXor<X>(uint32_t(u >> 32), lane);
-        return __longlong_as_double((long long)((uint64_t(hi) << 32) | lo));
-    }
-}
-//! maximum over the 2^BITS lanes of every aligned lane segment
-template<int BITS, class T>
-__device__ __forceinline__ T segmentMaxLanes(T v, unsigned lane)
-{
-    v = fmax(v, laneXorReal<1>(v, lane));
-    v = fmax(v, laneXorReal<2>(v, lane));
-    v = fmax(v, laneXorReal<4>(v, lane));
-    v = fmax(v, laneXorReal<8>(v, lane));
-    if constexpr (BITS >= 5) v = fmax(v, laneXorReal<16>(v, lane));
-    if constexpr (BITS >= 6) v = fmax(v, laneXorReal<32>(v, lane));
-    return v;
-}
-
-template<class K, int G, int MODE, class F>
-__global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
+template<class K, int G, int MODE>
+__global__ __launch_bounds__(256) void leafSortWaveKernel(
     const K* __restrict__ keysIn, const K* __restrict__ leafLo, const uint32_t* __restrict__ leafPos,
     const uint32_t* __restrict__ inOffset, const uint32_t* __restrict__ layoutNew, const K* __restrict__ binKeys,
     const uint32_t* __restrict__ binIdx, uint32_t J, bool alwaysCount, bool allTiles, K* __restrict__ keysOut,
-    uint32_t* __restrict__ orderOut, F fl)
+    uint32_t* __restrict__ orderOut)
 {
     constexpr K HOLE = ~K(0);
-    using Real       = typename F::Real;
-    using Val        = LeafVal<Real>;
     //! what a step reads of a leaf, written once per tile: one record, two or three wide LDS reads
     struct alignas(16) LeafRec
     {
@@ -857,7 +533,7 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
     if (t < uint32_t(G) + 4u) slotsK[t] = slots;
     if (!allTiles)
     {
-        // the quiet instantiation of leafSortKernel takes the tiles in which nothing moved (same vote as there)
+        // leafSortKernel takes the tiles in which nothing moved (same vote as there)
         const uint32_t nOldAll = leafPos[j0 + nl] - leafPos[j0];
         const bool changed     = inOffset[j0 + nl] != inOffset[j0] || alwaysCount || nNew != nOld;
         const bool quiet       = !__syncthreads_or(changed) && nOldAll <= RESORT_QUIET_SLOTS;
@@ -870,7 +546,7 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
     //! what the loop needs to know about leaf k
     struct Leaf
     {
-        uint32_t pk, nOld, ik, nInc, ok, nNew, slots, k;
+        uint32_t pk, nOld, ik, nInc, ok, nNew, slots;
         K lo;
         unsigned cut;
     };
@@ -882,7 +558,6 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
         f.slots = r.nOld + r.nInc;
         f.lo    = r.lo;
         f.cut   = r.cut;
-        f.k     = k;
         return f;
     };
     // slot s of a leaf: an old position or an arrival (key and old position; requested one wave step ahead).  Without a
@@ -897,45 +572,19 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
         if (have) key = src[at];
         if (have && !old) idx = binIdx[at];
     };
-    // x, y, z, h of the particle that sat at old position idx.  They are requested only once the leaf is ordered, right
-    // in front of the stores: the values then live in registers for a moment instead of across the network (with them
-    // prefetched like the keys the kernel needed 101-116 VGPRs, four waves per SIMD, and the network -- a chain of
-    // dependent cross-lane operations -- starved: 2.3-2.6 ms at 1e8 particles); the latency of these loads is covered
-    // by the other seven waves of the SIMD
-    auto loadFields = [&](uint32_t idx, bool have) -> Val
-    {
-        Val v{0, 0, 0, 0};
-        if constexpr (F::on)
-        {
-            if (have) v = Val{fl.x[idx], fl.y[idx], fl.z[idx], fl.h[idx]};
-        }
-        return v;
-    };
     // the values requested for the NEXT step are pinned (an empty asm that "uses" them) before the stores of this step go
     // out: the compiler then waits for those loads HERE, where they have had the whole step to return, instead of at the
     // top of the next step behind this step's stores -- vmcnt counts loads and stores in one in-order queue, and a wait
     // placed there has to cover the path of the loop that stores nothing, i.e. it waits for the stores as well
     auto pinNext = [&](K& key, uint32_t& idx) { asm volatile("" : "+v"(key), "+v"(idx)); };
-    auto storeAt = [&](uint32_t at, K key, uint32_t idx, const Val& val)
+    auto storeAt = [&](uint32_t at, K key, uint32_t idx)
     {
         keysOut[at]  = key;
         orderOut[at] = idx;
-        if constexpr (F::on) fl.ox[at] = val.x, fl.oy[at] = val.y, fl.oz[at] = val.z, fl.oh[at] = val.h;
     };
     auto digestOf = [&](const Leaf& f, K key, uint32_t slot) -> uint32_t
     { return key == HOLE ? ~0u : ((uint32_t((key - f.lo) >> f.cut) << 8) | slot); };
 
-    // the maximum of h over the new content of a leaf whose elements lie in the 2^BITS lanes of a segment (hm: this
-    // lane's candidate, 0 for a lane without an element -- the reference's segmentMax starts from 0 as well); `writer`:
-    // this lane reports for leaf k
-    auto reportHmax = [&](auto bitsTag, Real hm, bool writer, uint32_t k)
-    {
-        if constexpr (F::on)
-        {
-            const Real m = segmentMaxLanes<decltype(bitsTag)::value>(hm, lane);
-            if (writer) fl.hmax[j0 + k] = m;
-        }
-    };
     // the sorted digests of a leaf -> its new content: the place of every slot in the new order goes back to the lane that
     // loaded the slot (and still holds its key) through a 16-bit table per wave in LDS, two LDS accesses per element; that
     // lane stores key and old index at layoutNew[leaf] + place.  false: two neighbours in the new order have equal leading
@@ -959,37 +608,22 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
         for (int r = 0; r < R; ++r)
             if (d[r] != ~0u) place[d[r] & 0xFFu] = uint16_t(lane + 64u * r);
         __builtin_amdgcn_wave_barrier();
-        // (register after register: a leaf of more than 64 slots is rare, and four sets of values at once would set the
-        //  register budget -- i.e. the occupancy -- of the whole kernel)
-        Real hm = 0;
 #pragma unroll
         for (int r = 0; r < R; ++r)
         {
-            const Val val = loadFields(idx[r], key[r] != HOLE);
             if (key[r] == HOLE) continue;
-            hm                = fmax(hm, val.h);
             const uint32_t at = place[lane + 64u * r];
-            if (at < f.nNew) storeAt(f.ok + at, key[r], idx[r], val);
+            if (at < f.nNew) storeAt(f.ok + at, key[r], idx[r]);
         }
-        reportHmax(std::integral_constant<int, 6>{}, hm, lane == 0, f.k);
         __builtin_amdgcn_wave_barrier();
         return true;
     };
     // exact path: every loaded element counts the elements of its leaf in front of it by (key, old index)
-    // (rHmax: also fold the leaf's maximum of h -- the caller has not)
-    auto exactLeaf = [&](const Leaf& f, int R, const K* key, const uint32_t* idx, bool wholeWave)
+    auto exactLeaf = [&](const Leaf& f, int R, const K* key, const uint32_t* idx)
     {
-        Real hm = 0;
-        for (int r = 0; r < R; ++r)
-        {
-            const Val v = loadFields(idx[r], key[r] != HOLE);
-            if (key[r] != HOLE) hm = fmax(hm, v.h);
-        }
-        if (wholeWave) reportHmax(std::integral_constant<int, 6>{}, hm, lane == 0, f.k);
         for (int r = 0; r < R; ++r)
         {
             if (key[r] == HOLE) continue;
-            const Val val_r = loadFields(idx[r], true);
             uint32_t less = 0;
             for (uint32_t q = 0; q < f.nOld; ++q)
             {
@@ -1001,7 +635,7 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
                 const K kq = binKeys[f.ik + q];
                 less += (kq < key[r] || (kq == key[r] && binIdx[f.ik + q] < idx[r])) ? 1u : 0u;
             }
-            storeAt(f.ok + less, key[r], idx[r], val_r);
+            storeAt(f.ok + less, key[r], idx[r]);
         }
     };
     auto bigLeaf = [&](const Leaf& f, auto rTag)
@@ -1016,7 +650,7 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
             d[r] = digestOf(f, key[r], lane + 64u * r);
         }
         waveBitonicSort<R>(d, lane);
-        if (!finishLeaf(f, rTag, key, idx, d)) exactLeaf(f, R, key, idx, true);
+        if (!finishLeaf(f, rTag, key, idx, d)) exactLeaf(f, R, key, idx);
     };
 
     if constexpr (MODE == 0)
@@ -1050,12 +684,7 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
                 slotsN = __builtin_amdgcn_readlane(slotsOf, s + 1);
                 if (slotsN <= 64) loadSlot(cur, lane, keyN, idxN);
             }
-            if (slots == 0)
-            {
-                if constexpr (F::on)
-                    if (lane == 0) fl.hmax[j0 + f.k] = 0;
-                continue;
-            }
+            if (slots == 0) continue;
             if (slots <= 64)
             {
                 // nothing arrived and what stayed is still in order (a departure leaves the largest key behind, so only
@@ -1065,17 +694,15 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
                     const bool behind = lane != 0 && key1[0] < below;
                     if (f.nInc == 0 && !__any(behind))
                     {
-                        const Val v = loadFields(idx1[0], key1[0] != HOLE);
-                        reportHmax(std::integral_constant<int, 6>{}, key1[0] != HOLE ? v.h : Real(0), lane == 0, f.k);
                         pinNext(keyN, idxN);
-                        if (lane < f.nNew) storeAt(f.ok + lane, key1[0], idx1[0], v);
+                        if (lane < f.nNew) storeAt(f.ok + lane, key1[0], idx1[0]);
                         continue;
                     }
                 }
                 uint32_t d[1] = {digestOf(f, key1[0], lane)};
                 waveBitonicSort<1>(d, lane);
                 pinNext(keyN, idxN);
-                if (!finishLeaf(f, std::integral_constant<int, 1>{}, key1, idx1, d)) exactLeaf(f, 1, key1, idx1, true);
+                if (!finishLeaf(f, std::integral_constant<int, 1>{}, key1, idx1, d)) exactLeaf(f, 1, key1, idx1);
             }
             else if (slots <= 128) { bigLeaf(f, std::integral_constant<int, 2>{}); }
             else { bigLeaf(f, std::integral_constant<int, 4>{}); }
@@ -1122,7 +749,6 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
             const bool mine     = on && bits != 6u && seg < leafStepLeaves(word);
             const uint32_t kk   = kBegin + leafStepFirst(word) + seg;
             f                   = leafOf(mine ? kk : uint32_t(G));
-            f.k                 = mine ? kk : ~0u;
             const uint32_t sl   = lane & ((1u << bits) - 1u);
             loadSlot(f, 2 * sl, key[0], idx[0]);
             loadSlot(f, 2 * sl + 1, key[1], idx[1]);
@@ -1161,41 +787,19 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
                 else { bigLeaf(g, std::integral_constant<int, 4>{}); }
                 continue;
             }
-            // x, y, z, h of this lane's two elements, and the max h of every leaf of the step (a segment of 16 or 32 lanes
-            // each; empty leaves report 0)
-            Val val[2];
-            auto stepFields = [&]()
-            {
-                val[0] = loadFields(idx[0], key[0] != HOLE);
-                val[1] = loadFields(idx[1], key[1] != HOLE);
-                if constexpr (F::on)
-                {
-                    Real hm = 0;
-                    if (key[0] != HOLE) hm = fmax(hm, val[0].h);
-                    if (key[1] != HOLE) hm = fmax(hm, val[1].h);
-                    const bool writer = sl == 0 && f.k != ~0u;
-                    if (b == 5) reportHmax(std::integral_constant<int, 5>{}, hm, writer, f.k);
-                    else reportHmax(std::integral_constant<int, 4>{}, hm, writer, f.k);
-                }
-            };
-            if (leafStepEmpty(word))
-            {
-                stepFields();
-                continue;
-            }
+            if (leafStepEmpty(word)) continue;
             // the element in front of (lane, 0) is (lane - 1, 1), the one in front of (lane, 1) is (lane, 0)
             const K front = K(__shfl_up((unsigned long long)key[1], 1));
             // nothing arrived and what stayed is still in order: the content goes out as it came in
             const bool behind = (sl != 0 && key[0] < front) || key[1] < key[0];
             if (!__any(f.nInc != 0 || behind))
             {
-                stepFields();
                 pinNext(keyN[0], idxN[0]);
                 pinNext(keyN[1], idxN[1]);
 #pragma unroll
                 for (int r = 0; r < 2; ++r)
                 {
-                    if (2 * sl + r < f.nNew) storeAt(f.ok + 2 * sl + r, key[r], idx[r], val[r]);
+                    if (2 * sl + r < f.nNew) storeAt(f.ok + 2 * sl + r, key[r], idx[r]);
                 }
                 continue;
             }
@@ -1217,7 +821,6 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
             if (d[0] != ~0u) place[d[0] & 0xFFu] = uint16_t(2 * sl);
             if (d[1] != ~0u) place[d[1] & 0xFFu] = uint16_t(2 * sl + 1);
             __builtin_amdgcn_wave_barrier();
-            stepFields(); // (behind the network: the values live in registers from here to the stores only)
             if (!exact)
             {
 #pragma unroll
@@ -1225,11 +828,11 @@ __global__ __launch_bounds__(256) CSTONE_WAVE_OCC void leafSortWaveKernel(
                 {
                     if (key[r] == HOLE) continue;
                     const uint32_t at = place[2 * sl + r];
-                    if (at < f.nNew) storeAt(f.ok + at, key[r], idx[r], val[r]);
+                    if (at < f.nNew) storeAt(f.ok + at, key[r], idx[r]);
                 }
             }
             __builtin_amdgcn_wave_barrier();
-            if (exact) exactLeaf(f, 2, key, idx, false);
+            if (exact) exactLeaf(f, 2, key, idx);
             WAVE_TRACE(trFinish)
         }
 #ifdef CSTONE_RESORT_TRACE
@@ -1256,8 +859,7 @@ __global__ __launch_bounds__(256) void bracketedPositionsKernel(const K* __restr
                                                                 const uint32_t* __restrict__ numCompact,
                                                                 const uint32_t* __restrict__ coarse,
                                                                 const uint32_t* __restrict__ layoutNew,
-                                                                uint32_t* __restrict__ pos,
-                                                                uint32_t* __restrict__ boundaryLeaf)
+                                                                uint32_t* __restrict__ pos)
 {
     NodeIdx i = blockIdx.x * 256 + threadIdx.x;
     if (i > numNodes) return;
@@ -1280,8 +882,6 @@ __global__ __launch_bounds__(256) void bracketedPositionsKernel(const K* __restr
     // first index with keys[index] >= key, inside that leaf's new range -- its start, without looking at any key, when
     // the boundary is that of the old leaf itself (most leaves of a tree outlive an update)
     const bool onBoundary = leafLo[lo] == key;
-    // (for radiiOfLeaves: the compact leaf the boundary falls into, top bit: it IS that leaf's first key)
-    if (boundaryLeaf) boundaryLeaf[i] = lo | (onBoundary ? 0x80000000u : 0u);
     uint32_t a = layoutNew[lo], len = onBoundary ? 0u : layoutNew[lo + 1] - a;
     while (len > 0)
     {
@@ -1301,35 +901,6 @@ __global__ __launch_bounds__(256) void countsOfPositionsKernel(const uint32_t* _
     counts[i]  = c < maxCount ? c : maxCount;
 }
 
-/*! Halo radii of the leaves of any tree from the per-leaf maxima of h the field-carrying leaf pass folded (hmax, by
- *  compact leaf of the OLD tree).  A leaf whose two boundaries are first keys of compact leaves a and b holds exactly the
- *  new content of the compact leaves [a, b): its maximum is theirs.  Any other leaf (a split old leaf, a leaf that starts
- *  inside the key range of an old one) scans its own particles.  radii = float(max * 2 * ext), 0 for
- *  an empty leaf: cstone_hip_halo_radii's rule (Halos::discover, R/halos/halos.hpp:128-160). */
-template<class T>
-__global__ __launch_bounds__(256) void radiiFromOldLeavesKernel(const uint32_t* __restrict__ boundaryLeaf, NodeIdx numNodes,
-                                                                const uint32_t* __restrict__ layout,
-                                                                const T* __restrict__ hmax, const T* __restrict__ hSorted,
-                                                                float ext, float* __restrict__ radii)
-{
-    // one lane per leaf: nearly every leaf of the new tree IS an old leaf (one value to fetch); the others loop
-    const NodeIdx i = NodeIdx(blockIdx.x) * 256 + NodeIdx(threadIdx.x);
-    if (i >= numNodes) return;
-    const uint32_t ba = boundaryLeaf[i], bb = boundaryLeaf[i + 1];
-    T m = 0;
-    if ((ba & bb & 0x80000000u) != 0)
-    {
-        for (uint32_t j = ba & 0x7FFFFFFFu; j < (bb & 0x7FFFFFFFu); ++j)
-            m = fmax(m, hmax[j]);
-    }
-    else
-    {
-        for (uint32_t p = layout[i]; p < layout[i + 1]; ++p)
-            m = fmax(m, hSorted[p]);
-    }
-    radii[i] = float(m * 2 * ext);
-}
-
 //! the particles that carry the remove marker: behind every leaf, by ascending old position (idx sorted by the caller)
 template<class K>
 __global__ __launch_bounds__(256) void placeMarkersKernel(const uint32_t* __restrict__ idx, uint32_t count,
@@ -1344,15 +915,23 @@ __global__ __launch_bounds__(256) void placeMarkersKernel(const uint32_t* __rest
     orderOut[at]      = idx[r];
 }
 
+//! where J, the number of non-empty leaves of the table, lives on the device: the kernels read it there, the host reads
+//! it back with the other scalars of the attempt
+uint32_t* compactLeafCount(cstone_hip_ctx* ctx) { return (uint32_t*)(ctx->devScalars + RESORT_SCALARS) + 2; }
+
 } // namespace
 
 template<class K>
-int LeafResort<K>::buildTable(cstone_hip_ctx* ctx, const K* tree, const uint32_t* layout, int numLeaves, size_t n,
-                              bool expectMovers, uint32_t* numJ)
+int LeafResort<K>::prepare(cstone_hip_ctx* ctx, const K* tree, const uint32_t* layout, int numLeaves, size_t n,
+                           K* keysOut, bool expectMovers)
 {
+    // (the attempt's result scalars are cleared first, the table's scan writes J behind that; [3]: the mover counter)
+    CS_HIP(ctx, hipMemsetAsync(ctx->devScalars + RESORT_SCALARS, 0, 4 * sizeof(int), ctx->stream));
+    args_.keysOut = keysOut;
     StageTimer timer(ctx, CSTONE_STAGE_RESORT_BINS);
     numLeaves_         = numLeaves;
     n_                 = n;
+    uint32_t* numJ     = compactLeafCount(ctx);
     const size_t words = (n + 63) / 64 + 1;
     const size_t ent   = size_t(numLeaves) + 3; // J + 2 <= numLeaves + 2 table entries, one more for the scans' totals
     const size_t cap   = n / 8 + 1024;
@@ -1372,7 +951,6 @@ int LeafResort<K>::buildTable(cstone_hip_ctx* ctx, const K* tree, const uint32_t
     CS_TRY(moverSlot_.ensure(ctx, cap * 4));
     CS_TRY(binKeys_.ensure(ctx, cap * sizeof(K)));
     CS_TRY(binIdx_.ensure(ctx, cap * 4));
-    numJ_ = numJ;
 
     hipLaunchKernelGGL(leafStartWordsKernel, gridFor(numLeaves, 256), 256, 0, ctx->stream, layout, numLeaves, uint32_t(n),
                        mask_.as<uint64_t>(), popc_.as<uint32_t>(), uint32_t(words));
@@ -1382,7 +960,7 @@ int LeafResort<K>::buildTable(cstone_hip_ctx* ctx, const K* tree, const uint32_t
     arenaReset(ctx);
     CS_TRY(rc);
     hipLaunchKernelGGL(fillCompactLeavesKernel<K>, gridFor(size_t(numLeaves) + 3, 256), 256, 0, ctx->stream, tree, layout,
-                       numLeaves, mask_.as<uint64_t>(), rank_.as<uint32_t>(), numJ_, uint32_t(n), leafLo_.as<K>(),
+                       numLeaves, mask_.as<uint64_t>(), rank_.as<uint32_t>(), numJ, uint32_t(n), leafLo_.as<K>(),
                        leafPos_.as<uint32_t>(), outCount_.as<uint32_t>(), incoming_.as<uint32_t>());
     // many movers expected (the previous sync had them): the coarse table that shortens their searches
     haveCoarse_ = expectMovers;
@@ -1390,7 +968,7 @@ int LeafResort<K>::buildTable(cstone_hip_ctx* ctx, const K* tree, const uint32_t
     CS_TRY(coarse_.ensure(ctx, size_t(cells) * 4)); // (4 MB, once: no allocation in the middle of a run)
     if (haveCoarse_)
     {
-        hipLaunchKernelGGL(coarseLeafTableKernel<K>, gridFor(cells, 256), 256, 0, ctx->stream, leafLo_.as<K>(), numJ_,
+        hipLaunchKernelGGL(coarseLeafTableKernel<K>, gridFor(cells, 256), 256, 0, ctx->stream, leafLo_.as<K>(), numJ,
                            coarse_.as<uint32_t>());
     }
     CS_HIP(ctx, hipGetLastError());
@@ -1407,43 +985,12 @@ int LeafResort<K>::buildTable(cstone_hip_ctx* ctx, const K* tree, const uint32_t
 }
 
 template<class K>
-int LeafResort<K>::prepareTable(cstone_hip_ctx* ctx, const K* tree, const uint32_t* layout, int numLeaves, size_t n,
-                                bool expectMovers)
-{
-    CS_TRY(tableJ_.ensure(ctx, 4 * sizeof(uint32_t)));
-    return buildTable(ctx, tree, layout, numLeaves, n, expectMovers, tableJ_.as<uint32_t>());
-}
-
-template<class K>
-int LeafResort<K>::beginAttempt(cstone_hip_ctx* ctx, K* keysOut, int fieldBits)
-{
-    if (fieldBits) CS_TRY(hmax_.ensure(ctx, (size_t(numLeaves_) + 3) * size_t(fieldBits / 8)));
-    carryFields_   = fieldBits != 0;
-    boundaryNodes_ = -1;
-    moversPlaced_  = false;
-    // ([2] is J: checkTilesKernel copies it there from the table; [3]: the mover counter)
-    CS_HIP(ctx, hipMemsetAsync(ctx->devScalars + RESORT_SCALARS, 0, 4 * sizeof(int), ctx->stream));
-    args_.keysOut = keysOut;
-    return CSTONE_OK;
-}
-
-template<class K>
-int LeafResort<K>::prepare(cstone_hip_ctx* ctx, const K* tree, const uint32_t* layout, int numLeaves, size_t n,
-                           K* keysOut, bool expectMovers, int fieldBits)
-{
-    // (J in the context's slot: the slots are cleared first, the table's scan writes J behind that)
-    numLeaves_ = numLeaves;
-    CS_TRY(beginAttempt(ctx, keysOut, fieldBits));
-    return buildTable(ctx, tree, layout, numLeaves, n, expectMovers, (uint32_t*)(ctx->devScalars + RESORT_SCALARS) + 2);
-}
-
-template<class K>
 int LeafResort<K>::binMovers(cstone_hip_ctx* ctx, int leavesPerTile)
 {
     StageTimer timer(ctx, CSTONE_STAGE_RESORT_BINS);
     int* scalars          = ctx->devScalars + RESORT_SCALARS;
     const uint32_t ent    = uint32_t(numLeaves_) + 3;
-    const uint32_t* numJ  = numJ_;
+    const uint32_t* numJ  = compactLeafCount(ctx);
     const uint32_t* count = (const uint32_t*)scalars + 3;
     hipLaunchKernelGGL(binMoversKernel<K>, unsigned(ctx->numCu) * 16, 256, 0, ctx->stream, moverKeys_.as<K>(), count,
                        args_.moverCap, leafLo_.as<K>(), numJ, haveCoarse_ ? coarse_.as<uint32_t>() : nullptr,
@@ -1463,29 +1010,10 @@ int LeafResort<K>::binMovers(cstone_hip_ctx* ctx, int leavesPerTile)
 }
 
 template<class K>
-int LeafResort<K>::placeMoversEarly(cstone_hip_ctx* ctx, uint32_t expectedMovers)
-{
-    StageTimer timer(ctx, CSTONE_STAGE_RESORT_BINS);
-    // one list entry per lane when the guess holds, like placeMoversKernel (a fixed grid of numCu * 16 workgroups striding
-    // over 7 * 10^6 movers took 173 us against 137 us: 100 against 86 bytes of HBM traffic per mover); more movers than
-    // guessed take further strides, fewer leave workgroups without work
-    const size_t lanes  = std::min<size_t>(args_.moverCap, std::max<size_t>(size_t(expectedMovers) + expectedMovers / 4,
-                                                                         size_t(ctx->numCu) * 16 * 256));
-    const unsigned grid = unsigned((lanes + 255) / 256);
-    hipLaunchKernelGGL(placeMoversEarlyKernel<K>, grid, 256, 0, ctx->stream, moverKeys_.as<K>(),
-                       moverIdx_.as<uint32_t>(), moverDest_.as<uint32_t>(), moverSlot_.as<uint32_t>(),
-                       ctx->devScalars + RESORT_SCALARS, args_.moverCap, inOffset_.as<uint32_t>(), binKeys_.as<K>(),
-                       binIdx_.as<uint32_t>());
-    CS_HIP(ctx, hipGetLastError());
-    moversPlaced_ = true;
-    return CSTONE_OK;
-}
-
-template<class K>
 int LeafResort<K>::sortLeaves(cstone_hip_ctx* ctx, const K* keysIn, K* keysOut, uint32_t* orderOut, uint32_t numMovers,
                               uint32_t numMarkers, uint32_t J, int leavesPerTile, bool largeQuietTiles)
 {
-    if (numMovers && !moversPlaced_)
+    if (numMovers)
     {
         StageTimer timer(ctx, CSTONE_STAGE_RESORT_BINS);
         hipLaunchKernelGGL(placeMoversKernel<K>, gridFor(numMovers, 256), 256, 0, ctx->stream, moverKeys_.as<K>(),
@@ -1500,142 +1028,42 @@ int LeafResort<K>::sortLeaves(cstone_hip_ctx* ctx, const K* keysIn, K* keysOut, 
         uint32_t* idx = binIdx_.as<uint32_t>() + (numMovers - numMarkers);
         CS_TRY(cstone_hip_sort_keys(ctx, 32, idx, numMarkers));
         hipLaunchKernelGGL(placeMarkersKernel<K>, gridFor(numMarkers, 256), 256, 0, ctx->stream, idx, numMarkers,
-                           layoutNew_.as<uint32_t>(), numJ_, keysOut,
-                           orderOut);
+                           layoutNew_.as<uint32_t>(), compactLeafCount(ctx), keysOut, orderOut);
     }
     if (J == 0) return CSTONE_OK;
     StageTimer timer(ctx, CSTONE_STAGE_RESORT_LEAVES);
     const unsigned grid    = (J + unsigned(leavesPerTile) - 1) / unsigned(leavesPerTile);
     const bool alwaysCount = std::getenv("CSTONE_RESORT_COUNT") != nullptr; // tuning/tests: no quiet-tile shortcut
-#define CSTONE_LEAF_SORT(G, COUNTING)                                                                                  \
-    hipLaunchKernelGGL((leafSortKernel<K, G, COUNTING>), grid, 256, 0, ctx->stream, keysIn, mask_.as<uint64_t>(),      \
-                       rank_.as<uint32_t>(), leafLo_.as<K>(), leafPos_.as<uint32_t>(), inOffset_.as<uint32_t>(),       \
-                       layoutNew_.as<uint32_t>(), binKeys_.as<K>(), binIdx_.as<uint32_t>(), J, alwaysCount, keysOut,  \
-                       orderOut)
     // quiet tiles and tiles in which something moved: one launch each over all tiles (without movers there are none of
     // the second kind)
     const bool someMoved = numMovers > 0 || alwaysCount || largeQuietTiles;
-    // tiles in which something moved: one wave per leaf (the default), or counting over the whole leaf (the round-2
-    // formulation, kept for comparison: CSTONE_RESORT_SCAN=1).  With at least one mover per tile on average hardly a
-    // tile is quiet: the wave kernel then takes all tiles and the launch for quiet tiles is left out (at 10^8 particles
-    // 0.56 / 0.72 ms instead of 0.59 / 0.77 ms; CSTONE_RESORT_WAVE_ALL=0/1 forces either)
-    static const bool scanLeaves  = std::getenv("CSTONE_RESORT_SCAN") != nullptr;
+    // With at least one mover per tile on average hardly a tile is quiet: the wave kernel then takes all tiles and the
+    // launch for quiet tiles is left out (at 10^8 particles 0.56 / 0.72 ms instead of 0.59 / 0.77 ms;
+    // CSTONE_RESORT_WAVE_ALL=0/1 forces either)
     static const char* waveAllEnv = std::getenv("CSTONE_RESORT_WAVE_ALL");
-    const bool waveAll = !scanLeaves && !alwaysCount && (waveAllEnv ? waveAllEnv[0] == '1' : numMovers >= grid);
+    const bool waveAll            = !alwaysCount && (waveAllEnv ? waveAllEnv[0] == '1' : numMovers >= grid);
     // leaves that are less than half full on average: two or four of them per wave step, two elements per lane (the
     // kernel's flavour 1, pairSort; with fuller leaves it saves a few per cent when everything moves and loses more when
     // most leaves are still in order -- a step then sorts two leaves if either needs it; CSTONE_RESORT_PAIRS=0/1 forces)
     const char* pairsEnv        = std::getenv("CSTONE_RESORT_PAIRS"); // (read at every launch: the tests switch it)
     // (... and with fuller leaves when more than 3 % of the particles changed their leaf: hardly a leaf is still in order then)
     const bool pairs = pairsEnv ? pairsEnv[0] == '1' : (n_ < size_t(J) * 32u || size_t(numMovers) * 32u > n_);
-#define CSTONE_LEAF_WAVE_MODE(G, MODE)                                                                                 \
-    hipLaunchKernelGGL((leafSortWaveKernel<K, G, MODE, NoLeafFields>), grid, 256, 0, ctx->stream, keysIn,              \
-                       leafLo_.as<K>(), leafPos_.as<uint32_t>(), inOffset_.as<uint32_t>(), layoutNew_.as<uint32_t>(),  \
-                       binKeys_.as<K>(), binIdx_.as<uint32_t>(), J, alwaysCount, waveAll, keysOut, orderOut,           \
-                       NoLeafFields{})
-#define CSTONE_LEAF_WAVE(G)                                                                                            \
-    if (pairs) CSTONE_LEAF_WAVE_MODE(G, 1);                                                                            \
-    else CSTONE_LEAF_WAVE_MODE(G, 0)
-    if (leavesPerTile == 64)
+    auto launch = [&](auto gTag)
     {
-        if (!waveAll) CSTONE_LEAF_SORT(64, false);
-        if (someMoved && scanLeaves) CSTONE_LEAF_SORT(64, true);
-        else if (someMoved || waveAll) { CSTONE_LEAF_WAVE(64); }
-    }
-    else if (leavesPerTile == 32)
-    {
-        if (!waveAll) CSTONE_LEAF_SORT(32, false);
-        if (someMoved && scanLeaves) CSTONE_LEAF_SORT(32, true);
-        else if (someMoved || waveAll) { CSTONE_LEAF_WAVE(32); }
-    }
-    else if (leavesPerTile == 16)
-    {
-        if (!waveAll) CSTONE_LEAF_SORT(16, false);
-        if (someMoved && scanLeaves) CSTONE_LEAF_SORT(16, true);
-        else if (someMoved || waveAll) { CSTONE_LEAF_WAVE(16); }
-    }
-    else return fail(ctx, CSTONE_E_INTERNAL, "resort: %d leaves per workgroup not instantiated", leavesPerTile);
-#undef CSTONE_LEAF_SORT
-#undef CSTONE_LEAF_WAVE
-#undef CSTONE_LEAF_WAVE_MODE
-    CS_HIP(ctx, hipGetLastError());
-    return CSTONE_OK;
-}
-
-template<class K>
-int LeafResort<K>::sortLeavesFields(cstone_hip_ctx* ctx, const K* keysIn, K* keysOut, uint32_t* orderOut,
-                                    const ResortFields& fields, uint32_t numMovers, uint32_t numMarkers, uint32_t J,
-                                    int leavesPerTile)
-{
-    if (fields.realBits != 32 && fields.realBits != 64) return fail(ctx, CSTONE_E_ARG, "resort: field width %d", fields.realBits);
-    if (!carryFields_) return fail(ctx, CSTONE_E_INTERNAL, "resort: prepare() was not asked for the fields");
-    auto run = [&](auto tTag) -> int
-    {
-        using T = decltype(tTag);
-        if (numMovers && !moversPlaced_)
-        {
-            StageTimer timer(ctx, CSTONE_STAGE_RESORT_BINS);
-            hipLaunchKernelGGL(placeMoversKernel<K>, gridFor(numMovers, 256), 256, 0, ctx->stream, moverKeys_.as<K>(),
-                               moverIdx_.as<uint32_t>(), moverDest_.as<uint32_t>(), moverSlot_.as<uint32_t>(), numMovers,
-                               inOffset_.as<uint32_t>(), binKeys_.as<K>(), binIdx_.as<uint32_t>());
-        }
-        if (numMarkers)
-        {
-            // (particles that leave the domain: keys and old positions behind the last leaf; their fields stay behind)
-            StageTimer timer(ctx, CSTONE_STAGE_RESORT_BINS);
-            uint32_t* idx = binIdx_.as<uint32_t>() + (numMovers - numMarkers);
-            CS_TRY(cstone_hip_sort_keys(ctx, 32, idx, numMarkers));
-            hipLaunchKernelGGL(placeMarkersKernel<K>, gridFor(numMarkers, 256), 256, 0, ctx->stream, idx, numMarkers,
-                               layoutNew_.as<uint32_t>(), numJ_,
-                               keysOut, orderOut);
-        }
-        if (J == 0) return CSTONE_OK;
-        StageTimer timer(ctx, CSTONE_STAGE_RESORT_LEAVES);
-        const unsigned grid = (J + unsigned(leavesPerTile) - 1) / unsigned(leavesPerTile);
-        LeafFields<T> fl;
-        fl.x = static_cast<const T*>(fields.in[0]), fl.y = static_cast<const T*>(fields.in[1]);
-        fl.z = static_cast<const T*>(fields.in[2]), fl.h = static_cast<const T*>(fields.in[3]);
-        fl.ox = static_cast<T*>(fields.out[0]), fl.oy = static_cast<T*>(fields.out[1]);
-        fl.oz = static_cast<T*>(fields.out[2]), fl.oh = static_cast<T*>(fields.out[3]);
-        fl.hmax = hmax_.as<T>();
-        // the flavour by the fill of the leaves, as in sortLeaves(); every tile goes through this kernel
-        const char* pairsEnv = std::getenv("CSTONE_RESORT_PAIRS");
-        const bool pairs     = pairsEnv ? pairsEnv[0] == '1' : (n_ < size_t(J) * 32u || size_t(numMovers) * 32u > n_);
-#define CSTONE_LEAF_FIELDS_MODE(G, MODE)                                                                               \
-    hipLaunchKernelGGL((leafSortWaveKernel<K, G, MODE, LeafFields<T>>), grid, 256, 0, ctx->stream, keysIn,             \
-                       leafLo_.as<K>(), leafPos_.as<uint32_t>(), inOffset_.as<uint32_t>(), layoutNew_.as<uint32_t>(),  \
-                       binKeys_.as<K>(), binIdx_.as<uint32_t>(), J, false, true, keysOut, orderOut, fl)
-#define CSTONE_LEAF_FIELDS(G)                                                                                          \
-    if (pairs) CSTONE_LEAF_FIELDS_MODE(G, 1);                                                                          \
-    else CSTONE_LEAF_FIELDS_MODE(G, 0)
-        if (leavesPerTile == 64) { CSTONE_LEAF_FIELDS(64); }
-        else if (leavesPerTile == 32) { CSTONE_LEAF_FIELDS(32); }
-        else if (leavesPerTile == 16) { CSTONE_LEAF_FIELDS(16); }
-        else return fail(ctx, CSTONE_E_INTERNAL, "resort: %d leaves per workgroup not instantiated", leavesPerTile);
-#undef CSTONE_LEAF_FIELDS
-#undef CSTONE_LEAF_FIELDS_MODE
-        CS_HIP(ctx, hipGetLastError());
-        return CSTONE_OK;
+        constexpr int G = decltype(gTag)::value;
+        if (!waveAll)
+            hipLaunchKernelGGL((leafSortKernel<K, G>), grid, 256, 0, ctx->stream, keysIn, leafPos_.as<uint32_t>(),
+                               inOffset_.as<uint32_t>(), layoutNew_.as<uint32_t>(), J, alwaysCount, keysOut, orderOut);
+        if (!(someMoved || waveAll)) return;
+        auto* wave = pairs ? leafSortWaveKernel<K, G, 1> : leafSortWaveKernel<K, G, 0>;
+        hipLaunchKernelGGL(wave, grid, 256, 0, ctx->stream, keysIn, leafLo_.as<K>(), leafPos_.as<uint32_t>(),
+                           inOffset_.as<uint32_t>(), layoutNew_.as<uint32_t>(), binKeys_.as<K>(), binIdx_.as<uint32_t>(),
+                           J, alwaysCount, waveAll, keysOut, orderOut);
     };
-    return fields.realBits == 32 ? run(float{}) : run(double{});
-}
-
-template<class K>
-int LeafResort<K>::radiiOfLeaves(cstone_hip_ctx* ctx, int numNodes, const uint32_t* layout, const void* hSorted,
-                                 int realBits, float ext, float* radii)
-{
-    if (numNodes <= 0) return CSTONE_OK;
-    if (boundaryNodes_ != numNodes || !carryFields_)
-        return fail(ctx, CSTONE_E_INTERNAL, "resort: radiiOfLeaves without countLeaves for this tree");
-    StageTimer timer(ctx, CSTONE_STAGE_HALOS);
-    if (realBits == 32)
-        hipLaunchKernelGGL(radiiFromOldLeavesKernel<float>, gridFor(size_t(numNodes), 256), 256, 0, ctx->stream,
-                           boundaryLeaf_.as<uint32_t>(), NodeIdx(numNodes), layout, hmax_.as<float>(),
-                           static_cast<const float*>(hSorted), ext, radii);
-    else
-        hipLaunchKernelGGL(radiiFromOldLeavesKernel<double>, gridFor(size_t(numNodes), 256), 256, 0, ctx->stream,
-                           boundaryLeaf_.as<uint32_t>(), NodeIdx(numNodes), layout, hmax_.as<double>(),
-                           static_cast<const double*>(hSorted), ext, radii);
+    if (leavesPerTile == 64) launch(std::integral_constant<int, 64>{});
+    else if (leavesPerTile == 32) launch(std::integral_constant<int, 32>{});
+    else if (leavesPerTile == 16) launch(std::integral_constant<int, 16>{});
+    else return fail(ctx, CSTONE_E_INTERNAL, "resort: %d leaves per workgroup not instantiated", leavesPerTile);
     CS_HIP(ctx, hipGetLastError());
     return CSTONE_OK;
 }
@@ -1648,17 +1076,9 @@ int LeafResort<K>::countLeaves(cstone_hip_ctx* ctx, const K* tree, int numNodes,
     StageTimer timer(ctx, CSTONE_STAGE_NODE_COUNTS);
     CS_TRY(arenaReserve(ctx, alignUp(size_t(numNodes + 1) * sizeof(uint32_t)) + 1024));
     auto* pos = (uint32_t*)arenaTake(ctx, size_t(numNodes + 1) * sizeof(uint32_t));
-    // (the field-carrying pass wants to know where every boundary fell: radiiOfLeaves)
-    uint32_t* boundaryLeaf = nullptr;
-    if (carryFields_)
-    {
-        CS_TRY(boundaryLeaf_.ensure(ctx, size_t(numNodes + 1) * sizeof(uint32_t)));
-        boundaryLeaf   = boundaryLeaf_.as<uint32_t>();
-        boundaryNodes_ = numNodes;
-    }
     hipLaunchKernelGGL(bracketedPositionsKernel<K>, gridFor(size_t(numNodes) + 1, 256), 256, 0, ctx->stream, tree,
-                       NodeIdx(numNodes), keys, leafLo_.as<K>(), numJ_,
-                       haveCoarse_ ? coarse_.as<uint32_t>() : nullptr, layoutNew_.as<uint32_t>(), pos, boundaryLeaf);
+                       NodeIdx(numNodes), keys, leafLo_.as<K>(), compactLeafCount(ctx),
+                       haveCoarse_ ? coarse_.as<uint32_t>() : nullptr, layoutNew_.as<uint32_t>(), pos);
     hipLaunchKernelGGL(countsOfPositionsKernel, gridFor(numNodes, 256), 256, 0, ctx->stream, pos, NodeIdx(numNodes),
                        maxCount, counts);
     arenaReset(ctx);

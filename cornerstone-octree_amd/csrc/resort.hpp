@@ -7,9 +7,10 @@
 //      layout): a "stayer" keeps its leaf, a "mover" is appended to a list (resort.hpp: ResortArgs, sfc.hip:
 //      encodeResortKernel)
 //   2. the movers are binned by the leaf their new key falls into (binary search, one atomic each)
-//   3. one pass over the leaves (leafSortKernel): the stayers of a leaf plus its incoming movers are brought into the
-//      order of (key, old index) -- tiles in which nothing moved by one lane per leaf sorting in LDS, the others by
-//      counting on 32-bit digests -- and written to the leaf's new place
+//   3. one pass over the leaves: the stayers of a leaf plus its incoming movers are brought into the order of (key, old
+//      index) and written to the leaf's new place -- tiles (a workgroup's leaves) in which nothing moved by one lane per
+//      leaf sorting in LDS (leafSortKernel), the others by one wave per leaf sorting 32-bit digests in registers, one or
+//      two elements per lane (leafSortWaveKernel)
 // The result is the stable sort of the keys (ties by old index), whatever the particles did: a particle is a stayer
 // only if its key lies in the range of the leaf its position claims, everything else goes through the bins, and the
 // leaf ranges are disjoint and ascending.  Too many movers or an overfull leaf make the caller fall back to the radix sort.
@@ -38,18 +39,8 @@ struct ResortArgs
     uint32_t moverCap;
 };
 
-//! the particle arrays a field-carrying leaf pass moves together with the keys: x, y, z, h of the old order (device, n
-//! elements of real_bits / 8 bytes) and where the new order goes; hmaxOut / radii: see LeafResort::sortLeavesFields
-struct ResortFields
-{
-    int realBits;
-    const void* in[4];
-    void* out[4];
-};
-
 //! limits of the leaf pass
-constexpr uint32_t RESORT_TILE_SLOTS = 4224; // slots (old positions + arrivals) of a workgroup's leaves: key + index in
-                                             // LDS for quiet tiles (three workgroups per CU), digests for the others
+constexpr uint32_t RESORT_TILE_SLOTS = 4224; // slots (old positions + arrivals) a workgroup's leaves may have
 constexpr uint32_t RESORT_QUIET_SLOTS = 3840; // a tile in which nothing moved is sorted in LDS if it has at most this many
                                               // slots: key + 16-bit slot number, 39 KB, four workgroups per CU
 constexpr int RESORT_COARSE_BITS      = 20;  // leading key bits of the movers' search table (binMoversKernel)
@@ -76,45 +67,15 @@ public:
      *  leading key bits to the leaves, which shortens the search of every mover for its new leaf (worth its 20 us from
      *  some 10^5 movers on) */
     int prepare(cstone_hip_ctx* ctx, const K* tree, const uint32_t* layout, int numLeaves, size_t n, K* keysOut,
-                bool expectMovers = false, int fieldBits = 0 /* 32 | 64: the leaf pass will carry x, y, z, h */);
-    /*! prepare() in two halves.  prepareTable: everything that follows from tree, layout, numLeaves and n alone -- start
-     *  bits and ranks, J, leafLo, leafPos, the coarse table, the cleared departure / arrival counters.  It may be queued
-     *  long before the attempt it serves (Domain::sync builds it at the end of the sync before): J then lives in a
-     *  buffer of this object, not in the context's scalar slots, which other domains and calls on the context use in
-     *  between.  beginAttempt: the rest -- where the keys go, the fields' buffers, the attempt's cleared result scalars.
-     *  A table serves ONE attempt (the attempt counts in it). */
-    int prepareTable(cstone_hip_ctx* ctx, const K* tree, const uint32_t* layout, int numLeaves, size_t n,
-                     bool expectMovers);
-    int beginAttempt(cstone_hip_ctx* ctx, K* keysOut, int fieldBits = 0);
+                bool expectMovers = false);
     ResortArgs<K> args() const { return args_; }
     /*! bins the movers, new leaf sizes and offsets, limit checks; everything stays on the device: the scalars at
      *  ctx->devScalars + RESORT_SCALARS tell the host how it went */
     int binMovers(cstone_hip_ctx* ctx, int leavesPerTile);
-    /*! the movers into their bins BEFORE the host has seen how binMovers went (to be queued behind the read-back of the
-     *  scalars, so that it runs while the host decides): count and flags are read on the device, nothing is placed when
-     *  the attempt failed.  sortLeaves / sortLeavesFields then leave that step out.  expectedMovers (the movers of the
-     *  sync before, say) sizes the grid: one entry per lane if it holds */
-    int placeMoversEarly(cstone_hip_ctx* ctx, uint32_t expectedMovers);
     /*! the leaf pass: keysIn = new keys at old positions; keysOut / orderOut = sorted keys and their old positions.
      *  numMovers, numMarkers, numCompactLeaves: the values read back after binMovers */
     int sortLeaves(cstone_hip_ctx* ctx, const K* keysIn, K* keysOut, uint32_t* orderOut, uint32_t numMovers,
                    uint32_t numMarkers, uint32_t numCompactLeaves, int leavesPerTile, bool largeQuietTiles);
-
-    /*! The leaf pass that also MOVES x, y, z, h (one pass over the particle arrays instead of the leaf pass plus a gather
-     *  per array): lane s of a leaf's wave loads key and fields of slot s, the wave orders the leaf in registers, every
-     *  lane stores key, old index and fields at the leaf's new place.  A mover's fields are fetched from its old position
-     *  (known from its bin one wave step before they are needed).  On the way the wave folds the
-     *  maximum of h over the leaf's new content (hmax per compact leaf): radiiOfLeaves() turns them into the halo radii
-     *  of whatever tree the sync ends up with.  Requires prepare(..., fieldBits). */
-    int sortLeavesFields(cstone_hip_ctx* ctx, const K* keysIn, K* keysOut, uint32_t* orderOut, const ResortFields& fields,
-                         uint32_t numMovers, uint32_t numMarkers, uint32_t numCompactLeaves, int leavesPerTile);
-    /*! radii[i] = float(2 * ext * max h of the particles of leaf i of `tree`) (Halos::discover's rule, as
-     *  cstone_hip_halo_radii) from the maxima sortLeavesFields folded: a leaf whose boundaries both are boundaries of
-     *  the old (compact) leaf table takes the maximum of the old leaves it is made of, any other leaf scans its
-     *  particles in hSorted.  Must follow countLeaves() for the same tree (which notes where every boundary falls);
-     *  layout: offsets of the leaves among the sorted particles. */
-    int radiiOfLeaves(cstone_hip_ctx* ctx, int numNodes, const uint32_t* layout, const void* hSorted, int realBits,
-                      float ext, float* radii);
 
     /*! computeNodeCounts for any cornerstone leaf array over the keys the last sortLeaves ordered (valid until the next
      *  prepare): every boundary is searched inside the one old leaf that holds its key.  counts[i] = min(#keys in
@@ -124,15 +85,7 @@ public:
 private:
     DevBuf mask_, rank_, popc_, leafLo_, leafPos_, outCount_, incoming_, newCount_, layoutNew_, inOffset_;
     DevBuf moverKeys_, moverIdx_, moverDest_, moverSlot_, binKeys_, binIdx_, coarse_;
-    DevBuf hmax_, boundaryLeaf_; // the field-carrying pass: max h per compact leaf, where the new tree's boundaries fall
-    bool carryFields_  = false;
-    int boundaryNodes_ = -1;     // tree size boundaryLeaf_ was filled for
     bool haveCoarse_ = false;
-    DevBuf tableJ_;                  // J of a table built by prepareTable()
-    const uint32_t* numJ_ = nullptr; // where the kernels read J: tableJ_, or the context's slot (prepare())
-    bool moversPlaced_    = false;   // placeMoversEarly() has queued the placement for this attempt
-    int buildTable(cstone_hip_ctx* ctx, const K* tree, const uint32_t* layout, int numLeaves, size_t n, bool expectMovers,
-                   uint32_t* numJ);
     ResortArgs<K> args_{};
     int numLeaves_ = 0;
     size_t n_      = 0;

@@ -38,7 +38,7 @@ EXPORTS = [
     "cstone_hip_domain_create", "cstone_hip_domain_destroy", "cstone_hip_domain_sync", "cstone_hip_domain_view_get",
     "cstone_hip_domain_set_halo_factor", "cstone_hip_domain_mr_create", "cstone_hip_domain_mr_destroy",
     "cstone_hip_domain_mr_sync", "cstone_hip_domain_mr_sync_props", "cstone_hip_domain_mr_sync_keys", "cstone_hip_domain_mr_view_get", "cstone_hip_domain_mr_set_halo_factor", "cstone_hip_domain_mr_exchange_halos", "cstone_hip_domain_mr_reapply_sync",
-    "cstone_hip_domain_reapply_sync", "cstone_hip_domain_stats_get", "cstone_hip_domain_leaf_table_stats",
+    "cstone_hip_domain_reapply_sync", "cstone_hip_domain_stats_get",
     "cstone_hip_domain_mr_octree_get",
     "cstone_hip_fill", "cstone_hip_scale", "cstone_hip_increment", "cstone_hip_count_equal", "cstone_hip_reduce_sum",
     "cstone_hip_max_norm_square", "cstone_hip_segment_max", "cstone_hip_gather_ranges", "cstone_hip_lower_bound_value",

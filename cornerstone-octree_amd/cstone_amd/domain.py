@@ -317,14 +317,6 @@ class Domain:
         self.ctx._chk(self.ctx.lib.cstone_hip_domain_stats_get(self.h, C.byref(st)), "domain_stats_get")
         return {k: getattr(st, k) for k, _ in DomainStats._fields_}
 
-    def leaf_table_stats(self):
-        """(used, rejected): of the re-sort's leaf tables built a sync early, how many the next sync used and how many it
-        had to build again (cstone_hip_domain_leaf_table_stats)"""
-        used, rejected = C.c_uint32(0), C.c_uint32(0)
-        self.ctx._chk(self.ctx.lib.cstone_hip_domain_leaf_table_stats(self.h, C.byref(used), C.byref(rejected)),
-                      "domain_leaf_table_stats")
-        return used.value, rejected.value
-
     def fetch(self, ptr, count, dtype):
         """device array behind a view pointer -> numpy"""
         a = np.empty(count, dtype=dtype)

@@ -687,9 +687,7 @@ extern "C"
      * x, y and z are brought into SFC order by ONE kernel that reads the ordering once (cstone_hip_gather_multi: 52
      * instead of 60 bytes per particle for f64); with fewer the arrays rotate through scratch[0] one after the other.
      * From three buffers on that gather runs on a second stream of the context, next to the tree update; with FOUR, h
-     * goes through the fourth while x, y, z are still on their way.  (CSTONE_FUSED_LEAF_PASS=1 with four buffers selects
-     * the field-carrying leaf pass of the incremental re-sort instead -- x, y, z, h moved with the keys, 84 instead of
-     * 92 bytes per particle behind the encode; measured slower, DESIGN.md 4c, kept for comparison.)
+     * goes through the fourth while x, y, z are still on their way.
      * All buffers take part in the pointer exchange: on return *x, *y, *z, *h, props[i] and scratch[q] are a
      * permutation of the buffers passed in.  Same results whatever num_scratch is. */
     int cstone_hip_domain_sync_scratch(cstone_hip_domain* dom, void** keys, void** x, void** y, void** z, void** h,
@@ -743,11 +741,6 @@ extern "C"
         uint32_t last_movers;         /* particles that had left their leaf at the last re-sort */
     } cstone_hip_domain_stats;
     int cstone_hip_domain_stats_get(cstone_hip_domain* dom, cstone_hip_domain_stats* out);
-    /* With CSTONE_EARLY_LEAF_TABLE=1 (an experiment, off by default) the leaf table of a re-sort (csrc/resort.hpp) is
-     * built at the end of the sync before, beside the gather of x, y, z, instead of in front of the encode.  Of the
-     * tables built that way so far: how many the following sync used, and how many it had to build again because they
-     * no longer fitted (another particle count, no re-sort attempted, a failed sync in between).  Counters only. */
-    int cstone_hip_domain_leaf_table_stats(cstone_hip_domain* dom, uint32_t* used, uint32_t* rejected);
 
     /* ---------------------------------------------------------------------------------------------
      * Domain::sync on SEVERAL ranks, one process per GPU (R/domain/domain.hpp:196-243 with the exchange steps of

@@ -12,20 +12,26 @@ import pytest
 _NUM_SCRATCH = [1]  # scratch arrays a _Stepper hands to its syncs (set by the fixture below)
 
 
-@pytest.fixture(autouse=True, params=["auto", "one-per-lane", "two-per-lane", "auto-fields", "one-per-lane-fields",
-                                      "two-per-lane-fields"])
+# case -> (CSTONE_RESORT_PAIRS or None: the leaf pass chooses by the fill of the leaves, scratch arrays)
+_CASES = {
+    "auto": (None, 1),
+    "one-per-lane": ("0", 1),
+    "two-per-lane": ("1", 1),
+    "auto-4-scratch": (None, 4),
+    "one-per-lane-fields": ("0", 4),
+    "two-per-lane-fields": ("1", 4),
+}
+
+
+@pytest.fixture(autouse=True, params=list(_CASES))
 def leaf_pass_flavour(request, monkeypatch):
-    """every test of this module runs with the leaf pass choosing its flavour itself (by the fill of the leaves) and with
-    either flavour of leafSortWaveKernel forced (CSTONE_RESORT_PAIRS, csrc/resort.hip) -- and each of these once with ONE
-    scratch array (the leaf pass orders keys and indices, the fields follow in gather passes) and once with FOUR and
-    CSTONE_FUSED_LEAF_PASS (the field-carrying leaf pass: x, y, z, h move with the keys, the halo radii come from the
-    maxima it folds)"""
-    flavour = request.param.replace("-fields", "")
-    if flavour != "auto":
-        monkeypatch.setenv("CSTONE_RESORT_PAIRS", "0" if flavour == "one-per-lane" else "1")
-    _NUM_SCRATCH[0] = 4 if request.param.endswith("-fields") else 1
-    if request.param.endswith("-fields"):
-        monkeypatch.setenv("CSTONE_FUSED_LEAF_PASS", "1")
+    """every test of this module runs with the leaf pass choosing its flavour itself and with either flavour of
+    leafSortWaveKernel forced (CSTONE_RESORT_PAIRS, csrc/resort.hip) -- each with ONE scratch array (the fields rotate
+    through it in gather passes) and with FOUR (x, y, z are gathered on the second stream, h goes through the fourth
+    array while they are on their way)"""
+    pairs, _NUM_SCRATCH[0] = _CASES[request.param]
+    if pairs is not None:
+        monkeypatch.setenv("CSTONE_RESORT_PAIRS", pairs)
     yield
     _NUM_SCRATCH[0] = 1
 

@@ -15,7 +15,6 @@ SETTINGS = [
     {"CSTONE_D2H_BLIT": "1", "CSTONE_UPLOAD_BLIT": "1"},  # the runtime's copies instead of the copy kernels
     {"CSTONE_NO_GATHER_OVERLAP": "1", "CSTONE_MR_NO_PLACE_OVERLAP": "1"},  # one stream
     {"CSTONE_DEVICE_GLOBAL_STEP": "1", "CSTONE_MR_DEVICE_GLOBAL_STEP": "1", "CSTONE_MR_NO_SPECULATIVE_CUTS": "1"},
-    {"CSTONE_FUSED_LEAF_PASS": "1"},  # the field-carrying leaf pass (four scratch arrays)
     {"CSTONE_NO_RESORT": "1"},  # no incremental re-sort: radix passes
 ]
 

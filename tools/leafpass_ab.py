@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """stage timers of the steady-state Domain::sync for three kinds of motion between the syncs -- none, 1 % of the particles
 displaced by <= 2h (bench.py's extras.moving_particles), every particle displaced by <= 0.1 h (the headline workload) --
-with the displacement OUTSIDE the timed interval.  usage: leafpass_ab.py [particles]; environment as for bench.py
-(CSTONE_RESORT_SCAN=1: the round-2 formulation of the leaf pass for tiles with movers)"""
+with the displacement OUTSIDE the timed interval.  usage: leafpass_ab.py [particles]; environment as for bench.py"""
 import os
 import sys
 import time

@@ -1,4 +1,4 @@
-# timing of the leaf pass on static particles (quiet path / counting path forced), per build variant
+# timing of the leaf pass on static particles (quiet-tile kernel / CSTONE_RESORT_COUNT=1: every tile through the wave kernel), per build variant
 # (tools/build_variant.sh NAME FLAGS resort)
 R=$GRAFT_REPO_ROOT
 for lib in "" $RESORT_VARIANTS; do

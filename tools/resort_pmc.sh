@@ -1,4 +1,5 @@
-# PMC counters of leafSortKernel's counting path (static particles, CSTONE_RESORT_COUNT=1), one group per run
+# PMC counters of the leaf pass with every tile taken as one in which something moved: leafSortWaveKernel on static
+# particles (CSTONE_RESORT_COUNT=1), one group per run
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out/resort_pmc
@@ -14,7 +15,7 @@ import csv,glob,collections
 for f in sorted(glob.glob("$O/pmc_*/**/*counter_collection.csv", recursive=True)):
     acc=collections.defaultdict(list)
     for r in csv.DictReader(open(f)):
-        if "leafSortKernel" in r["Kernel_Name"]:
+        if "leafSortWaveKernel" in r["Kernel_Name"]:
             acc[r["Counter_Name"]].append(float(r["Counter_Value"]))
     for k,v in acc.items(): print(k, len(v), sum(v)/len(v))
 PY

@@ -5,8 +5,7 @@
 python tools/resort_timeline.py <tag> <trace dir> [<FETCH_SIZE dir> <WRITE_SIZE dir>] [out.json]
 
 The sync is the last one of the trace whose gather of h is in it, taken from the first of the library's kernels behind the
-caller's own (torch's) kernels to the last one before them: with the leaf table built a sync early, the table's kernels
-are at its end.  Times are relative to the sync's first kernel."""
+caller's own (torch's) kernels to the last one before them.  Times are relative to the sync's first kernel."""
 import csv
 import glob
 import json
@@ -65,7 +64,7 @@ def at(names, which):
 
 LEAF = ("leafSortWaveKernel", "leafSortKernel")
 TABLE = ("leafStartWordsKernel", "fillCompactLeavesKernel", "coarseLeafTableKernel")
-PLACE = ("placeMoversKernel", "placeMoversEarlyKernel")
+PLACE = ("placeMoversKernel",)
 summary = {
     "setting": tag,
     "encode_start_us": at(("encodeResortKernel",), "start"),
