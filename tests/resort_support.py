@@ -1,4 +1,4 @@
-"""What the tests of the re-sort's schedule share (test_resort_scenarios.py, test_encode_tile_order.py): a client's
+"""What the tests of the re-sort's schedule share (test_resort_scenarios.py, test_encode_tile_order.py, test_resort_plan.py): a client's
 time-stepping loop on device arrays, the motion of the issue's common comparison, and the bit-for-bit comparison of two
 domains.  Not a test module."""
 import contextlib

@@ -296,7 +296,8 @@ def test_resort_random_walk(hip, oracle, seed):
             assert np.array_equal(a[f], b[f]), (step, kind, f)
         m = va.end_index
         assert np.array_equal(sa_.dom.fetch(va.sfc_order, m, np.uint32), sb_.dom.fetch(vb.sfc_order, m, np.uint32)), step
-    # (how often it re-sorted depends on the draw: collapses leave overfull leaves behind; the other tests pin that down)
+    # (how often it re-sorted depends on the draw: collapses leave overfull leaves behind; which syncs attempt, how many
+    #  movers they find and which attempts are accepted is pinned by test_resort_plan.py, against a model of the rule)
     assert sb_.dom.stats()["resorts"] == 0 and sa_.dom.stats()["resorts"] >= 1, sa_.dom.stats()
 
 
